@@ -2,7 +2,13 @@
 """bench.py - env-steps/s of the fused D3IL step() on MI355X (headline: BASELINE.json configs[1], Avoiding, 4096 envs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--task avoiding|pushing|sorting] [--envs 4096]
-                    [--policy random|mlp|scripted_push] [--no-cpu-baseline] [--no-preroll]
+                    [--policy random|mlp|scripted_push] [--full [--no-cpu-baseline]] [--no-preroll] [--dump-outputs DIR]
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the line.  --full adds what the headline figure does not need:
+the CPU baseline of the oracle (`cpu_baseline`, unless --no-cpu-baseline) and, for the ddpm / beso policies, the event-timed policy
+kernel (`policy_roofline`).  --dump-outputs DIR writes what the last timed step left for a caller (state, observations, actions,
+done / success / mode, flags, step counters, episode counts, tally) as DIR/<name>.npy in float32 / float64: two builds run with the
+same arguments can be compared output for output.
 
 A "step" is one pass of the hot path over one batch: for every one of the 4096 environments per GPU the policy writes the
 action (Avoiding: device-side Philox random policy, seed 42, counter = global env index x t; Pushing / Sorting: torch policy on
@@ -383,6 +389,45 @@ def _beso_policy_roofline(pol, n, dev):
                     "matrix pipe is busy a fifth of the kernel" % calls}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, shards, states, episodes, table):
+    """--dump-outputs: what the last timed step left for a caller of the path, as <out_dir>/<name>.npy (float32 / float64; the integer outputs
+    converted exactly).  Per-environment arrays hold this rank's environments in sub-batch order (state: [state_rows, envs], the others: envs first);
+    episodes = (finished, successful) of the timed region, tally = the reduced per-context table.  Should the per-environment arrays exceed
+    DUMP_LIMIT_BYTES, a fixed seeded sample of the environments is written instead and its indices go to env_index.npy."""
+    import numpy as np
+    import torch
+
+    def cat(xs, dtype):
+        return torch.cat(xs).cpu().numpy().astype(dtype)
+    per_env = {      # name -> (array, environment axis)
+        "state": (np.concatenate([s[0] for s in states], axis=1).astype(np.float64), 1),
+        "flags": (np.concatenate([s[1] for s in states]).astype(np.float64), 0),
+        "step_count": (np.concatenate([s[2] for s in states]).astype(np.float64), 0),
+        "obs": (cat([sh.env.obs for sh in shards], np.float32), 0),
+        "actions": (cat([sh.actions for sh in shards], np.float64), 0),
+        "done": (cat([sh.env.done for sh in shards], np.float32), 0),
+        "success": (cat([sh.env.success for sh in shards], np.float32), 0),
+        "mode": (cat([sh.env.mode for sh in shards], np.float32), 0),
+    }
+    n = per_env["obs"][0].shape[0]
+    total = sum(a.nbytes for a, _ in per_env.values())
+    os.makedirs(out_dir, exist_ok=True)
+    index_path = os.path.join(out_dir, "env_index.npy")
+    if total > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, max(1, n * (DUMP_LIMIT_BYTES // 2) // total), replace=False))
+        per_env = {name: (np.take(a, idx, axis=ax), ax) for name, (a, ax) in per_env.items()}
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.remove(index_path)
+    for name, (a, _) in per_env.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    np.save(os.path.join(out_dir, "episodes.npy"), episodes.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "tally.npy"), table.cpu().numpy().astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------- the benchmark
 def _make_env(args, task, dev, n):
     if task == "avoiding":
@@ -705,6 +750,8 @@ def run(args):
         torch.distributed.all_reduce(t_max, op=torch.distributed.ReduceOp.MAX)
     dt = float(t_max.item())
     states = [sh.env.get_state() for sh in shards]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shards, states, episodes, table)
     st = np.concatenate([x[0] for x in states], axis=1)
     fl = np.concatenate([x[1] for x in states])
     n_state = env.state_rows - (2 if task in ("sorting", "inserting") else 0)
@@ -810,13 +857,13 @@ def run(args):
                                  "`valu` the binding resource",
                          "valu": valu},
         }
-        if policy == "beso":
+        if args.full and policy == "beso":
             line["policy_roofline"] = _beso_policy_roofline(pol, n, dev)
-        if policy == "ddpm":
+        if args.full and policy == "ddpm":
             pr = _ddpm_policy_roofline(pol, n // S, dev)
             if pr is not None:
                 line["policy_roofline"] = pr
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(task, env.blob, q, ctx60)
         print(json.dumps(line))
     for sh in shards:
@@ -835,7 +882,10 @@ def main():
     ap.add_argument("--policy", default=None, choices=["random", "mlp", "scripted_push", "scripted_stack", "scripted_align", "ddpm", "beso"],
                     help="default: random (Avoiding), mlp (Pushing / Sorting), scripted_stack (Stacking: pick-and-place, the contact regime of the task)")
     ap.add_argument("--max-steps", type=int, default=None, help="Sorting: episode cap (default 700 = configs/sorting_4_config.yaml:80; the Sim class default is 500)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline of the oracle (cpu_baseline) "
+                    "and, for the ddpm / beso policies, the event-timed policy kernel (policy_roofline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--stack-contexts", type=int, default=16, help="Stacking: number of reference test contexts in the tile (host IK of the scripted policy: ~1.3 s each)")
     ap.add_argument("--no-auto-reset", action="store_true")
     ap.add_argument("--no-preroll", action="store_true", help="measure from a freshly reset batch (round-1 behaviour)")

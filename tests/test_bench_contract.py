@@ -56,7 +56,7 @@ def test_algorithmic_bytes_follow_the_survey():
 
 @pytest.mark.gpu
 def test_json_line_of_a_short_run():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--preroll", "10", "--envs", "512"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--preroll", "10", "--envs", "512", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -76,6 +76,28 @@ def test_json_line_of_a_short_run():
     assert r["algorithmic_bytes_per_step"] == 704 * 512 and abs(r["achieved"] - 704 * 512 / (line["ms_per_step"] * 1e-3) / 1e9) / r["achieved"] < 1e-9
     assert abs(r["achieved_per_launch"] - r["algorithmic_bytes_per_launch"] / (r["kernel_ms"] * 1e-3) / 1e9) / r["achieved_per_launch"] < 1e-9
     assert abs(r["frac_per_launch"] - r["achieved_per_launch"] / r["peak"]) < 1e-12
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries no CPU baseline; --dump-outputs writes the last timed step's outputs, and two runs with the same arguments
+    write the same arrays."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--preroll", "20", "--envs", "512",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+        assert line["config"]["finite"]
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert {"state", "obs", "actions", "done", "success", "mode", "flags", "step_count", "episodes", "tally"} <= set(a) and set(a) == set(b)
+    assert a["state"].shape[1] == 512 and a["obs"].shape[0] == 512 and np.isfinite(a["state"]).all()
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
 
 
 @pytest.mark.gpu

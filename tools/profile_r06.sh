@@ -15,9 +15,9 @@ for C in $CASES; do
   PA="--policy $P"; if [ $T = avoiding ]; then PA=""; fi
   for S in ${DEFS[$T]} 1; do
     if [ -f profiles/r06/pmc/${T}_${P}_sb$S.json ] && [ -z "$FORCE" ]; then continue; fi
-    CMD="python bench.py --task $T $PA $X --sub-batches $S --no-cpu-baseline"
+    CMD="python bench.py --task $T $PA $X --sub-batches $S --full --no-cpu-baseline"
     PX="$X"; if [ -z "$X" ]; then PX="--steps 40"; fi            # counter passes: fewer timed steps are enough (same pre-roll, same phase mix)
-    PCMD="python bench.py --task $T $PA $PX --sub-batches $S --no-cpu-baseline"
+    PCMD="python bench.py --task $T $PA $PX --sub-batches $S --full --no-cpu-baseline"
     timeout 900 rocprofv3 --kernel-include-regex "$K" --pmc FETCH_SIZE --output-format csv -d $O/pa -- $PCMD > $O/pmc_a.log 2>&1
     timeout 900 rocprofv3 --kernel-include-regex "$K" --pmc WRITE_SIZE --output-format csv -d $O/pw -- $PCMD > $O/pmc_w.log 2>&1
     timeout 900 rocprofv3 --kernel-include-regex "$K" --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $O/pb -- $PCMD > $O/pmc_b.log 2>&1
@@ -27,11 +27,11 @@ for C in $CASES; do
   done
   S=${DEFS[$T]}
   if [ ! -f $O/kernel_stats_${T}_${P}.csv ] || [ -n "$FORCE" ]; then
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --task $T $PA $X --no-cpu-baseline > $O/prof.log 2>&1
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --task $T $PA $X --full --no-cpu-baseline > $O/prof.log 2>&1
     f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_${T}_${P}.csv; rm -rf $O/prof
   fi
-  CB="--no-cpu-baseline"; if [ $P = random ] || [ $P = mlp ] || [ $P = scripted_stack ] || [ $P = scripted_align ]; then CB=""; fi      # one cpu_baseline leg per task
-  if [ $T = inserting ]; then CB=""; fi
+  CB="--full --no-cpu-baseline"; if [ $P = random ] || [ $P = mlp ] || [ $P = scripted_stack ] || [ $P = scripted_align ]; then CB="--full"; fi      # one cpu_baseline leg per task (--full: also policy_roofline)
+  if [ $T = inserting ]; then CB="--full"; fi
   python bench.py --task $T $PA $X $CB 2>/dev/null | tail -1 > $O/bench_line_${T}_${P}.json
 done
 python - <<'PY'
