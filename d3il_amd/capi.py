@@ -27,6 +27,8 @@ FLAG_IK_VALID, FLAG_SOLVER_FAIL, FLAG_MULTI_CONTACT = 1 << 15, 1 << 16, 1 << 17
 # Pushing (D3IL_PUSH_STATE_* / D3IL_PFLAG_* in include/d3il_rollout.h)
 PUSH_STATE_BOX, PUSH_STATE_WARM, PUSH_STATE_TASK, PUSH_STATE_F64 = 42, 68, 89, 91
 PFLAG_FIRST_MASK, PFLAG_MODE_MASK, PFLAG_WARM_VALID, PFLAG_CON_OVERFLOW, PFLAG_OFF_TABLE = 0x7, 0x38, 1 << 6, 1 << 18, 1 << 19
+PFLAG_LINK_NEAR = 1 << 20       # link-near guard of the generic engine (d3il_set_link_guard); the bit of SFLAG_HAND_NEAR
+LINK_GUARD_SLACK = 1.25e-4      # how far the guard's distance may lie below the true one (csrc/link_guard.h LG_SLACK)
 TASK_AVOIDING, TASK_PUSHING, TASK_SORTING, TASK_STACKING, TASK_ALIGNING, TASK_INSERTING = 0, 1, 2, 3, 4, 5
 ALIGN_STATE_BOX, ALIGN_STATE_WARM, ALIGN_STATE_TARGET, ALIGN_STATE_F64 = 42, 55, 70, 77
 STACK_STATE_BOX, STACK_STATE_WARM, STACK_STATE_F64 = 28, 67, 94
@@ -39,7 +41,7 @@ INS_STATE_BOX, INS_STATE_WARM, INS_STATE_TASK, INS_STATE_F64 = 42, 81, 108, 110
 EXPORTS = ["d3il_create", "d3il_destroy", "d3il_start", "d3il_reset", "d3il_step", "d3il_get_buffers", "d3il_get_state",
            "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
            "d3il_rccl_available", "d3il_comm_unique_id", "d3il_comm_init", "d3il_comm_count", "d3il_comm_destroy", "d3il_reduce_metrics", "d3il_set_timing",
-           "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_set_option", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
+           "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
 
 
 class D3ilError(RuntimeError):
@@ -100,6 +102,7 @@ def load():
         L.d3il_last_step_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.d3il_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.d3il_debug_scratch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.d3il_set_link_guard.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
         if L.d3il_blob_sizeof() != C.sizeof(ModelBlob):
             raise D3ilError("model blob layout mismatch between include/d3il_model_blob.h and d3il_amd/model/blob.py")
         _LIB = L
@@ -109,3 +112,24 @@ def load():
 def check(rc: int):
     if rc != 0:
         raise D3ilError("libd3il_rollout error %d: %s" % (rc, load().d3il_last_error().decode()))
+
+
+_CAPSULES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "model", "blobs", "panda_link_capsules.json")
+
+
+def link_capsules(body_names, path: str | None = None):
+    """The committed bounding capsules of the rod robot's collision hulls (model/mjcf_compile.py link_capsules) as the f64 [n][9] array
+    d3il_set_link_guard takes - body id looked up by name in ``body_names`` (the blob's body list), statics flag, p0, p1, r - and the default margin."""
+    import json
+    import numpy as np
+    with open(path or _CAPSULES) as f:
+        js = json.load(f)
+    rows = [[body_names.index(c["body"]), c["statics"]] + list(c["p0"]) + list(c["p1"]) + [c["r"]] for c in js["capsules"]]
+    return np.ascontiguousarray(rows, dtype=np.float64), float(js["margin"])
+
+
+def set_link_guard(h, capsules, margin: float, counter_ptr=None):
+    """d3il_set_link_guard: capsules = host f64 [n][9] (or None / empty: off), counter_ptr = device int64 address or None."""
+    import numpy as np
+    caps = np.zeros((0, 9)) if capsules is None else np.ascontiguousarray(capsules, dtype=np.float64).reshape(-1, 9)
+    check(load().d3il_set_link_guard(h, caps.ctypes.data_as(C.c_void_p) if len(caps) else None, len(caps), float(margin), counter_ptr))

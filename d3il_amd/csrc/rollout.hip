@@ -22,6 +22,7 @@ namespace d3il {
 constexpr int WAVE = 64;
 }
 #include "gen_kernels.h"
+#include "link_guard.h"
 #include "stack_kernels.h"
 #include "policy_f16x3.h"
 
@@ -919,6 +920,7 @@ using namespace d3il;
 static_assert(D3IL_STACK_STATE_BOX == SK_STATE_BOX && D3IL_STACK_STATE_WARM == SK_STATE_WARM && D3IL_STACK_STATE_F64 == SK_STATE_F64, "d3il_rollout.h: Stacking state layout");
 static_assert(D3IL_SFLAG_WARM_VALID == SKF_WARM_VALID && D3IL_SFLAG_HAND_NEAR == SKF_HAND_NEAR && D3IL_PFLAG_CON_OVERFLOW == SKF_CON_OVERFLOW && D3IL_PFLAG_OFF_TABLE == SKF_OFF_TABLE,
               "d3il_rollout.h: Stacking flag bits");
+static_assert(D3IL_PFLAG_LINK_NEAR == LG_FLAG && D3IL_PFLAG_LINK_NEAR == D3IL_SFLAG_HAND_NEAR, "d3il_rollout.h: the link-near bit of the generic engine is the hand-near bit of the cooperative one");
 static_assert(D3IL_SFLAG_MODE_MASK == (SKF_NMODE_MASK | (0x3Fu << SKF_IND_SHIFT)), "d3il_rollout.h: Stacking order code");
 static_assert(D3IL_ALIGN_STATE_BOX == AL_STATE_BOX && D3IL_ALIGN_STATE_WARM == AL_STATE_WARM && D3IL_ALIGN_STATE_TARGET == AL_STATE_TARGET && D3IL_ALIGN_STATE_F64 == AL_STATE_F64, "d3il_rollout.h: Aligning state layout");
 static_assert(D3IL_INS_STATE_BOX == 42 && D3IL_INS_STATE_WARM == 42 + 13 * 3 && D3IL_INS_STATE_TASK == 42 + 13 * 3 + 6 * 3 + NDOF && D3IL_INS_STATE_F64 == gen_state_rows(3), "d3il_rollout.h: Inserting state layout");
@@ -973,6 +975,9 @@ struct d3il_handle_s {
   // fused tail of the Avoiding rollout step (k_avoiding_tail): the next step's action is already in `actions` when these match the next call
   bool prep_valid; uint32_t prep_t; uint64_t prep_seed, prep_off; double* prep_actions; bool fuse_tail; double* d_des_before; hipStream_t prep_stream;
   bool info_is_view;       // buf.info_f64 points into buf.state (Pushing on the generic engine: its two task rows) - not freed on its own
+  // link-near guard of the generic engine (link_guard.h, d3il_set_link_guard): lg.n = 0 = off
+  d3il_model_blob model;   // the blob the handle was made from (the body tree places the guard's capsules)
+  LinkGuardConsts lg; LinkGuardConsts* d_lg; int64_t* lg_flagged;   // lg_flagged: caller-owned device counter, may be null
 };
 
 // The Stacking kernels read their model from one __constant__ object per device (scalar loads, no pointer across call boundaries).  Stacking handles on one
@@ -1016,7 +1021,7 @@ static void free_handle(d3il_handle_s* h) {
     if (h->task_id == D3IL_TASK_STACKING && g_active_stack[dev].refs > 0) g_active_stack[dev].refs--;
   }
   void* ptrs[] = {h->dc, h->d_init_qpos, h->buf.obs, h->buf.done, h->buf.success, h->buf.mode, h->buf.state, h->buf.flags, h->buf.step_count, h->buf.policy_des,
-                  h->info_is_view ? nullptr : (void*)h->buf.info_f64, h->d_scratch, h->d_ctx, h->d_mask, h->d_des_before};
+                  h->info_is_view ? nullptr : (void*)h->buf.info_f64, h->d_scratch, h->d_ctx, h->d_mask, h->d_des_before, h->d_lg};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->ring_created) for (int i = 0; i < 128; i++) { (void)hipEventDestroy(h->ring0[i]); (void)hipEventDestroy(h->ring1[i]); }
   rg_drop_for_free(h);
@@ -1041,6 +1046,7 @@ int d3il_create(int task_id, int n_envs, int device_id, const void* model_blob, 
   d3il_handle_s* h = new d3il_handle_s();
   std::memset(&h->buf, 0, sizeof h->buf);
   h->task_id = -1; h->device = device_id;      // task_id is set once the model reference is taken (free_handle)
+  h->model = m; h->d_lg = nullptr; h->lg_flagged = nullptr; h->lg.n = 0;
   h->dc = nullptr; h->d_init_qpos = nullptr; h->d_scratch = nullptr; h->d_ctx = nullptr; h->d_mask = nullptr; h->ev_created = false; h->ring_created = false;
   h->tally_ctx = nullptr; h->tally_nctx = 0; h->tally_table = nullptr; h->tol_mode = 0; h->ctx_dim = 0; h->stack_reset_coop = 1; h->kc_id = 0;
   const char* err = "";
@@ -1338,6 +1344,10 @@ int d3il_step(d3il_handle h, const double* actions, void* stream) {
 #undef D3IL_GEN_LAUNCH
     HIPCHK(hipGetLastError());
     if (h->timing) { HIPCHK(hipEventRecord(h->ev1, s)); h->ev_valid = true; h->ring_head++; }
+    if (h->lg.n > 0) {      // the link-near guard: behind the step kernel, before anything that clears the flags (auto-reset, tally); outside the timed launch
+      hipLaunchKernelGGL(k_gen_link_guard, dim3((h->n + LG_ENVS - 1) / LG_ENVS), dim3(GEN_WAVE), 0, s, h->d_lg, b.state, b.flags, (unsigned long long*)h->lg_flagged, h->n, h->stride);
+      HIPCHK(hipGetLastError());
+    }
     return D3IL_OK;
   }
   if (h->task_id == D3IL_TASK_STACKING) {
@@ -1884,6 +1894,23 @@ int d3il_debug_scratch(d3il_handle h, int env, double* out, int count) {
     return D3IL_OK;
   }
   HIPCHK(hipMemcpy2D(out, sizeof(double), h->d_scratch + env, (size_t)h->stride * sizeof(double), sizeof(double), (size_t)count, hipMemcpyDeviceToHost));
+  return D3IL_OK;
+}
+
+int d3il_set_link_guard(d3il_handle h, const double* capsules, int n, double margin, int64_t* flagged_episodes_device) {
+  if (!h) return fail(D3IL_EINVAL, "d3il_set_link_guard: null handle");
+  if (!gen_task(h->task_id)) return fail(D3IL_EUNSUPPORTED, "d3il_set_link_guard: Pushing / Sorting / Inserting only (Stacking and Aligning have their own guard, D3IL_SFLAG_HAND_NEAR; Avoiding has no objects)");
+  LinkGuardConsts lg;
+  const char* err = "";
+  if (build_link_guard(h->model, capsules, n, margin, lg, &err)) return fail(D3IL_EINVAL, std::string("d3il_set_link_guard: ") + err);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());      // no step of this handle reads the capsules while they change; like any option, the change drops captured graphs
+  if (h->rg_ready) rg_drop(h);
+  if (n > 0) {
+    if (!h->d_lg) HIPCHK(hipMalloc(&h->d_lg, sizeof(LinkGuardConsts)));
+    HIPCHK(hipMemcpy(h->d_lg, &lg, sizeof(LinkGuardConsts), hipMemcpyHostToDevice));
+  }
+  h->lg = lg; h->lg_flagged = n > 0 ? flagged_episodes_device : nullptr;
   return D3IL_OK;
 }
 

@@ -23,6 +23,7 @@ import torch
 
 from .. import capi
 from .avoiding import ObstacleAvoidanceVecEnv
+from .link_guard import LinkGuardMixin
 from .pushing import _yaw_quat
 
 _SPACES = np.array([[0.35, -0.2, 0.5, -0.15], [0.55, -0.1, 0.7, -0.05], [0.35, 0.0, 0.5, 0.05]])   # gate_insertion.py:53-63 (x lo, y lo, x hi, y hi)
@@ -50,15 +51,16 @@ def sample_contexts(n: int, seed: int = 0) -> np.ndarray:
     return out.reshape(n, 21)
 
 
-class GateInsertionVecEnv(ObstacleAvoidanceVecEnv):
+class GateInsertionVecEnv(LinkGuardMixin, ObstacleAvoidanceVecEnv):
     task = "inserting"
     action_dim = 7
     obs_dim = 11
     default_max_steps = 2000          # gate_insertion.py:158
 
-    def __init__(self, n_envs, device=0, render=False, n_substeps: int = 35, max_steps_per_episode: int | None = None):
+    def __init__(self, n_envs, device=0, render=False, n_substeps: int = 35, max_steps_per_episode: int | None = None, link_guard: bool = True):
         super().__init__(n_envs, device=device, render=render, n_substeps=n_substeps, max_steps_per_episode=max_steps_per_episode)
         self._contexts = None
+        self._init_link_guard(link_guard)      # unmodelled robot-link contacts are flagged, not simulated (envs/link_guard.py)
         self.box_row, self.warm_row, self.task_row = capi.INS_STATE_BOX, capi.INS_STATE_WARM, capi.INS_STATE_TASK
         self.targets = torch.as_tensor(np.asarray(self.js["task_const"]["target_pos"], dtype=np.float64), device=self.device)
 

@@ -20,6 +20,7 @@ import torch
 
 from .. import capi
 from .avoiding import ObstacleAvoidanceVecEnv
+from .link_guard import LinkGuardMixin
 
 
 def contexts_from_reference(ctx_list) -> np.ndarray:
@@ -53,17 +54,18 @@ def sample_contexts(n: int, seed: int = 0) -> np.ndarray:
     return out
 
 
-class BlockPushVecEnv(ObstacleAvoidanceVecEnv):
+class BlockPushVecEnv(LinkGuardMixin, ObstacleAvoidanceVecEnv):
     task = "pushing"
     action_dim = 7
     obs_dim = 8
     default_max_steps = 400          # pushing.py:175
 
-    def __init__(self, n_envs, device=0, render=False, n_substeps: int = 35, max_steps_per_episode: int | None = None):
+    def __init__(self, n_envs, device=0, render=False, n_substeps: int = 35, max_steps_per_episode: int | None = None, link_guard: bool = True):
         super().__init__(n_envs, device=device, render=render, n_substeps=n_substeps, max_steps_per_episode=max_steps_per_episode)
         self.mean_distance = self.info_f64[0, :self.n_envs]
         self.reward = self.info_f64[1, :self.n_envs]
         self._contexts = None
+        self._init_link_guard(link_guard)      # unmodelled robot-link contacts are flagged, not simulated (envs/link_guard.py)
 
     def reset(self, mask: torch.Tensor | None = None, random: bool = False, context=None):
         """env.reset(random=False, context=...): ``context`` is f64[n_envs, 14] (numpy or tensor; see module docstring).

@@ -23,6 +23,7 @@ import torch
 
 from .. import capi
 from .avoiding import ObstacleAvoidanceVecEnv
+from .link_guard import LinkGuardMixin
 from .pushing import _yaw_quat
 
 _SLOTS = np.array([[0.4, -0.15, 0.5, -0.1], [0.4, -0.05, 0.5, 0.0], [0.4, 0.05, 0.5, 0.1],
@@ -53,14 +54,14 @@ def sample_contexts(n: int, num_boxes: int = 4, seed: int = 0) -> np.ndarray:
     return out.reshape(n, 7 * num_boxes)
 
 
-class SortingVecEnv(ObstacleAvoidanceVecEnv):
+class SortingVecEnv(LinkGuardMixin, ObstacleAvoidanceVecEnv):
     task = "sorting"
     action_dim = 7
     num_boxes = 4
     obs_dim = 2 + 3 * num_boxes
     default_max_steps = 500          # sorting_sim.py:33
 
-    def __init__(self, n_envs, device=0, render=False, n_substeps: int = 35, max_steps_per_episode: int | None = None, num_boxes: int = 4):
+    def __init__(self, n_envs, device=0, render=False, n_substeps: int = 35, max_steps_per_episode: int | None = None, num_boxes: int = 4, link_guard: bool = True):
         if num_boxes not in (2, 4):
             raise NotImplementedError("this build carries the Sorting-2 and Sorting-4 scenes (the engine has one lane per cube, at most four)")
         self.num_boxes = int(num_boxes)
@@ -68,6 +69,7 @@ class SortingVecEnv(ObstacleAvoidanceVecEnv):
         self.task = "sorting" if num_boxes == 4 else "sorting_%d" % num_boxes          # scene blob (d3il_amd/model/blobs)
         super().__init__(n_envs, device=device, render=render, n_substeps=n_substeps, max_steps_per_episode=max_steps_per_episode)
         self._contexts = None
+        self._init_link_guard(link_guard)      # unmodelled robot-link contacts are flagged, not simulated (envs/link_guard.py)
         self.reward = torch.zeros(self.n_envs, dtype=torch.float64, device=self.device)   # get_reward is the constant 0 (sorting.py:509-511)
         self.box_row = 42
         self.warm_row = 42 + 13 * self.num_boxes

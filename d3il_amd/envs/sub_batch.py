@@ -149,6 +149,11 @@ class SubBatchSet:
             b.agent = as_batched(a, b.n)
             b.agent.reset()
 
+    @property
+    def link_near_episodes(self) -> int:
+        """Episodes flagged by the link-near guard, summed over the sub-batches (0 for tasks without the guard)."""
+        return sum(int(getattr(b.env, "link_near_episodes", 0)) for b in self.batches if b.env is not None)
+
     def close(self):
         for b in self.batches:
             if b.env is not None:

@@ -672,5 +672,98 @@ def main():
                                                                              {k: len(v["vert"]) for k, v in blob["meshes"].items()}))
 
 
+LINK_GUARD_BODIES = ["link0", "link1", "link2", "link3", "link4", "link5", "link6", "link7", "hand", "leftfinger", "rightfinger"]
+LINK_GUARD_DISTAL = ("link5", "link6", "link7", "hand", "leftfinger", "rightfinger")      # the capsules that are also tested against the static boxes
+LINK_GUARD_TASKS = ("pushing", "sorting", "sorting_2", "inserting")
+
+
+def fit_capsule(v):
+    """Bounding capsule (p0, p1, r) of a point set: principal axis through the centroid, r = largest distance from that axis, and the
+    shortest segment on it whose r-neighbourhood still holds every point (a point at axial position t and radial distance d needs a
+    segment point within sqrt(r^2 - d^2) of t: intervals on a line, so the segment runs from the smallest upper end to the largest
+    lower end).  Not minimal, but never looser than the sphere about the centroid."""
+    v = np.asarray(v, dtype=np.float64)
+    c = v.mean(0)
+    u = np.linalg.svd(v - c, full_matrices=False)[2][0]
+    t = (v - c) @ u
+    d = np.linalg.norm((v - c) - np.outer(t, u), axis=1)
+    r = float(d.max())
+    w = np.sqrt(np.maximum(r * r - d * d, 0.0))
+    a, b = float((t + w).min()), float((t - w).max())
+    if a > b:
+        a = b = 0.5 * (a + b)
+    return c + a * u, c + b * u, r * (1.0 + 1e-9) + 1e-12      # (the end points sit exactly on the limit: a hair of radius absorbs the rounding)
+
+
+def link_capsules(task="pushing"):
+    """Bounding capsules of the rod robot's collision hulls (panda_rod_invisible.xml: the `...:geom2` mesh geoms of link0 .. link7, hand and
+    both fingers; the finger-tip boxes are folded into their finger's capsule), each in the frame of the BODY that carries it - the geom's
+    pos / quat are applied (the right finger's mesh is turned by quat 0 0 0 1), the tip box goes through its tip body's offset.
+    Returns (capsules, hulls): capsules = [{body, p0, p1, r, statics}], hulls = {body: hull vertices [n, 3] in the body frame}.
+    The body tree and the geoms are those of the committed blob of `task`; only the STL vertices are read from the reference data."""
+    from scipy.spatial import ConvexHull
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "blobs", task + ".json")) as f:
+        js = json.load(f)
+    bodies, geoms = js["bodies"], js["geoms"]
+    caps, hulls = [], {}
+    for short in LINK_GUARD_BODIES:
+        bi = next(i for i, b in enumerate(bodies) if b["name"] == "panda_rb0_" + short)
+        pts = []
+        for g in geoms:
+            if g["body"] == bi and g["type"] == "mesh" and g["contype"] != 0:
+                v = load_stl_vertices(os.path.join(D3IL, "models/mj/robot/assets/%s.stl" % g["mesh"]))
+                pts.append(v @ quat2mat(_normalize(g["quat"])).T + np.asarray(g["pos"]))
+        for ci, cb in enumerate(bodies):      # welded children that carry collision boxes (the finger tips)
+            if cb["parent"] != bi or cb["joints"]:
+                continue
+            for g in geoms:
+                if g["body"] == ci and g["type"] == "box" and g["contype"] != 0:
+                    sx, sy, sz = g["size"][:3]
+                    corners = np.array([[x, y, z] for x in (-sx, sx) for y in (-sy, sy) for z in (-sz, sz)])
+                    corners = corners @ quat2mat(_normalize(g["quat"])).T + np.asarray(g["pos"])
+                    pts.append(corners @ quat2mat(_normalize(cb["quat"])).T + np.asarray(cb["pos"]))
+        assert pts, short
+        v = np.concatenate(pts)
+        hv = v[ConvexHull(v).vertices]
+        p0, p1, r = fit_capsule(hv)
+        assert capsule_excess(hv, p0, p1, r) <= 0.0
+        hulls[short] = hv
+        caps.append(dict(body="panda_rb0_" + short, p0=p0.tolist(), p1=p1.tolist(), r=r, statics=int(short in LINK_GUARD_DISTAL)))
+    return caps, hulls
+
+
+def capsule_excess(v, p0, p1, r):
+    """Largest (distance to the segment p0 p1) - r over the points v: <= 0 when the capsule holds them all."""
+    p0, p1 = np.asarray(p0), np.asarray(p1)
+    d = p1 - p0
+    L2 = float(d @ d)
+    s = np.clip((v - p0) @ d / L2, 0.0, 1.0) if L2 > 0 else np.zeros(len(v))
+    return float(np.linalg.norm(v - (p0 + np.outer(s, d)), axis=1).max() - r)
+
+
+def write_link_capsules():
+    """blobs/panda_link_capsules.json (capsules + the body id of every capsule in each generic-engine blob's body list) and the test fixture
+    tests/golden/panda_link_hulls.npz (the hull vertices the capsules were fitted to; numbers only)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    caps, hulls = link_capsules("pushing")
+    for t in LINK_GUARD_TASKS:
+        with open(os.path.join(here, "blobs", t + ".json")) as f:
+            names = [b["name"] for b in json.load(f)["bodies"]]
+        for c in caps:
+            c.setdefault("body_id", {})[t] = names.index(c["body"])
+    with open(os.path.join(here, "blobs", "panda_link_capsules.json"), "w") as f:
+        json.dump(dict(version=1, margin=0.02, capsules=caps), f, indent=1)
+    root = os.path.dirname(os.path.dirname(here))
+    np.savez_compressed(os.path.join(root, "tests", "golden", "panda_link_hulls.npz"), **hulls)
+    for c in caps:
+        print("%-22s r = %.4f  length = %.4f  hull vertices %d" % (c["body"], c["r"], float(np.linalg.norm(np.subtract(c["p1"], c["p0"]))), len(hulls[c["body"][10:]])))
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    if "--link-capsules" in sys.argv:      # only the link-guard capsules (the blobs are read, not rebuilt)
+        write_link_capsules()
+    else:
+        main()
+        write_link_capsules()

@@ -17,6 +17,7 @@ import os
 import numpy as np
 import torch
 
+from .. import capi
 from ..distributed import reduce_sim_counts, shard_range, world_info
 from ..envs.pushing import BlockPushVecEnv, contexts_from_reference
 from ..envs.sub_batch import SubBatchSet
@@ -48,6 +49,7 @@ class Pushing_Sim(BaseSim):
         self.max_steps_per_episode = max_steps_per_episode
         self.contexts = load_test_contexts() if contexts is None else np.asarray(contexts, dtype=np.float64)
         self.last_rollout = None
+        self.link_near_episodes = 0      # rollouts of the last test_agent flagged by the link-near guard
 
     def _predict(self, agent, obs10: torch.Tensor) -> torch.Tensor:
         return agent.predict_batch(obs10).to(device=obs10.device, dtype=torch.float64).reshape(obs10.shape[0], 2)
@@ -88,12 +90,17 @@ class Pushing_Sim(BaseSim):
         if world > 1:
             import torch.distributed as dist
             dist.all_reduce(dist_sum)
+        # rollouts in which the link-near guard fired (an unmodelled robot-link contact was within reach: envs/link_guard.py); the Sims do not reset, so the
+        # sticky bit of every rollout is still in its flag word.  Diagnostics only: the metrics do not use it.
+        near = ((flags.to(torch.int64) & capi.PFLAG_LINK_NEAR) != 0).sum().reshape(1)
+        reduce_sim_counts(near, env)
+        self.link_near_episodes = int(near.item())
         c = counts.cpu().numpy()
         success_rate, entropy, mode_probs = pushing_metrics(c[:-1].reshape(self.n_contexts, 4), int(c[-1]), total, self.n_trajectories_per_context)
         self.last_rollout = dict(mode=mode, success=success, mean_distance=mean_distance, counts=c, shard=(lo, hi),
                                  success_rate=success_rate, entropy=entropy, mode_probs=mode_probs,
                                  mean_distance_all=float(dist_sum.item()) / total, flags=flags)
-        log.info("Successrate %s entropy %s mean distance %s", success_rate, entropy, float(dist_sum.item()) / total)
+        log.info("Successrate %s entropy %s mean distance %s link-near rollouts %d", success_rate, entropy, float(dist_sum.item()) / total, self.link_near_episodes)
         if batches is not None:
             batches.close()
         # the reference returns the full [n_contexts, n_trajectories] tables (pushing_sim.py:178): every rank fills its slice of a

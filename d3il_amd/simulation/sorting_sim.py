@@ -21,6 +21,7 @@ import logging
 import numpy as np
 import torch
 
+from .. import capi
 from ..distributed import reduce_sim_counts, shard_range, world_info
 from ..envs.sorting import SortingVecEnv, contexts_from_reference, sample_contexts
 from ..envs.sub_batch import SubBatchSet
@@ -67,6 +68,7 @@ class Sorting_Sim(BaseSim):
         self.n_mode = len(self.mode_keys)
         self.mode_encoding = torch.tensor([self.modes[k] for k in self.mode_keys])
         self.last_rollout = None
+        self.link_near_episodes = 0      # rollouts of the last test_agent flagged by the link-near guard
 
     def _predict(self, agent, obs_in: torch.Tensor) -> torch.Tensor:
         return agent.predict_batch(obs_in).to(device=obs_in.device, dtype=torch.float64).reshape(obs_in.shape[0], 2)
@@ -106,11 +108,16 @@ class Sorting_Sim(BaseSim):
         mode_hist = torch.bincount(mode.clamp(0, 255), minlength=256)       # all rollouts, by final mode code (diagnostics)
         reduce_sim_counts(counts, env)          # the integer tables: the library's RCCL all-reduce under nccl (distributed.py)
         reduce_sim_counts(mode_hist, env)
+        # rollouts in which the link-near guard fired (an unmodelled robot-link contact was within reach: envs/link_guard.py); the Sims do not reset, so the
+        # sticky bit of every rollout is still in its flag word.  Diagnostics only: the metrics do not use it.
+        near = ((flags.to(torch.int64) & capi.PFLAG_LINK_NEAR) != 0).sum().reshape(1)
+        reduce_sim_counts(near, env)
+        self.link_near_episodes = int(near.item())
         c = counts.cpu().numpy()
         success_rate, entropy, kl, score = sorting_metrics(c[:-1].reshape(self.n_contexts, self.n_mode), int(c[-1]), total, self.n_trajectories_per_context,
                                                            self.mode_encoding.numpy())
         self.last_rollout = dict(mode=mode, success=success, counts=c, mode_hist=mode_hist.cpu().numpy(), shard=(lo, hi), flags=flags)
-        log.info("Successrate %s entropy %s KL %s", success_rate, entropy, kl)
+        log.info("Successrate %s entropy %s KL %s link-near rollouts %d", success_rate, entropy, kl, self.link_near_episodes)
         if batches is not None:
             batches.close()
         # the quantities the reference logs (sorting_sim.py:209-212)

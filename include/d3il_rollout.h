@@ -97,6 +97,9 @@ enum {
   D3IL_PFLAG_WARM_VALID = 1 << 6,
   D3IL_PFLAG_CON_OVERFLOW = 1 << 18, /* more contacts than the solver holds (24) in some sub-step */
   D3IL_PFLAG_OFF_TABLE = 1 << 19,    /* a cube left the modelled part of the table */
+  D3IL_PFLAG_LINK_NEAR = 1 << 20,    /* Pushing / Sorting / Inserting with d3il_set_link_guard: a bounding capsule of a robot collision hull this engine does not collide
+                                        (link0 .. link7, hand, fingers) came within the guard margin of a cube or a static box at the end of some env step of the
+                                        episode; the same bit and meaning as D3IL_SFLAG_HAND_NEAR */
   /* Stacking reuses TERMINATED / SUCCESS / SOLVER_FAIL / CON_OVERFLOW (more than 32 contacts) / OFF_TABLE and replaces the low bits: */
   D3IL_SFLAG_MODE_MASK = 0xFF,       /* order code n | c0 << 2 | c1 << 4 | c2 << 6: n boxes have reached the target zone, c_i = colour (0 r, 1 g, 2 b) of the
                                         i-th one (info['mode'] = "rgb"[c0] + ... , stacking.py:395-419); also what buf.mode holds */
@@ -285,6 +288,17 @@ int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offse
  * steps (last_reset mask, episode counters and tally of the finished environments, their reset and re-latch, and the policy's action for the NEXT step -
  * which the next call of an uninterrupted sequence finds in `actions`); same results as the five launches and the copy it replaces. */
 int d3il_set_option(d3il_handle h, const char* name, int value);
+/* Link-near guard of the generic engine (Pushing / Sorting / Inserting; csrc/link_guard.h).  The engine collides only the rod with the scene; the model's other robot
+ * collision hulls (panda_rod_invisible.xml: link0 .. link7, hand, fingers, finger tips) are not evaluated.  With capsules set, every d3il_step ends with one more small
+ * kernel on the caller's stream that places the capsules by forward kinematics (qpos rows 0 .. 8) and raises D3IL_PFLAG_LINK_NEAR in the flag word of every environment
+ * in which a capsule is closer than `margin` to a cube or - capsules with the second word set - to a static box.  The bit is sticky for the episode and cleared by
+ * d3il_reset / d3il_auto_reset like the other per-episode bits; the physics is not touched.  The test samples env-step boundaries: a persisting approach cannot be missed,
+ * one shorter than an env step can.  The distance used is a lower bound of the true capsule <-> box distance, at most 1.25e-4 m below it.
+ * capsules: HOST f64 [n][9] = body id in the blob's body list (an arm link or a body welded to one, a finger or its tip, link0), 1 = also against the static boxes,
+ * p0[3], p1[3] in that body's frame, r.  n = 0 switches the guard off (the default).  flagged_episodes_device (may be NULL): device i64, += 1 whenever an environment's
+ * bit goes 0 -> 1, i.e. the number of flagged episodes.  D3IL_EUNSUPPORTED for Avoiding / Stacking / Aligning handles; D3IL_EINVAL for a body outside the chain, r <= 0,
+ * margin < 0, n > 16, a segment longer than 1 m.  Synchronises the device; drops captured graphs like any option. */
+int d3il_set_link_guard(d3il_handle h, const double* capsules, int n, double margin, int64_t* flagged_episodes_device);
 /* Diagnostics builds only (-DD3IL_DEVICE_STATS): per-path lane/wave counters of the step kernel. */
 int d3il_debug_stats(uint64_t* out32, int reset);
 int d3il_debug_wave_stats(uint64_t* out_nwaves_x10, int nwaves, int reset);
