@@ -113,8 +113,9 @@ def build_stats_variant(verbose: bool = False, counts: bool = False, per_wave: b
 
 
 def build_variant(name: str, defines, verbose: bool = False) -> str:
-    """Comparison / diagnostics builds of the Stacking kernel, loaded with D3IL_LIB_PATH=<file>:
-    poison: every LDS word starts as a NaN and dead areas are poisoned again every sub-step (-DD3IL_SK_POISON);
+    """Comparison / diagnostics builds, loaded with D3IL_LIB_PATH=<file>:
+    poison: the read-before-write guard of ALL kernel families (-DD3IL_POISON, implies -DD3IL_SK_POISON; csrc/rigid_common.h): every LDS word of a workgroup and
+            the generic engine's record area start as NaN, what is not carried across sub-steps is poisoned again every sub-step;
     raw: without the convergence fences (SK_CONVERGE, stack_step.h) - shows the position-dependence defect of DESIGN sections 17.3 / 18.2 (-DD3IL_SK_PRELOAD_RAW);
     nopreload: the table-reading support function (-DD3IL_SK_NO_PRELOAD)."""
     out = os.path.join(PKG, "libd3il_rollout_%s.so" % name)
@@ -126,9 +127,11 @@ def build_variant(name: str, defines, verbose: bool = False) -> str:
 
 
 def build_poison(force: bool = False, verbose: bool = False) -> str:
-    """The NaN-poison build of the cooperative engine (libd3il_rollout_poison.so), rebuilt when a source is newer: tests/test_gpu_poison_build.py runs the
-    Stacking / Aligning parity files on it - a phase that reads an LDS word its launch has not written shows up as a NaN on EVERY box instead of as a result
-    that depends on what the LDS held before (round 6: the slide axes of the rod-robot variants)."""
+    """The NaN-poison build (libd3il_rollout_poison.so; ONE library for the cooperative engine, the generic engine with the link-near guard, and the Avoiding split
+    kernel), rebuilt when a source is newer: tests/test_gpu_poison_build.py runs the parity files of all six tasks on it, checks that the guard is live and
+    compares it bit for bit with the product library - a phase that reads a word its launch has not written shows up on EVERY machine instead of as a result
+    that depends on what the memory held before (round 6: the slide axes of the rod-robot variants).  It cannot see register spills
+    (private scratch); a NaN swallowed by a clamp is caught by the bit-for-bit comparison, not by looking for NaN."""
     out = os.path.join(PKG, "libd3il_rollout_poison.so")
     if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in DEPS):
         check_compiler(verbose)
@@ -141,7 +144,7 @@ VARIANTS = {"gtstatic": ["D3IL_GT_STATIC"],
             "gtinline": ["D3IL_GT_INLINE"],      # the tree solver inlined into the step kernel (no callee-saved register traffic)
             "nsub1": ["D3IL_GEN_NSUB=1"],      # the generic engine with one lane per cube and one physics wave (A/B of the sub-lanes)
             "loneenv": ["D3IL_LONE_PER_ENV=1"],      # lone-cube / tree solver chosen per environment instead of per wave (A/B)
-            "poison": ["D3IL_SK_POISON"], "raw": ["D3IL_SK_PRELOAD_RAW"], "nopreload": ["D3IL_SK_NO_PRELOAD"], "poisonraw": ["D3IL_SK_POISON", "D3IL_SK_PRELOAD_RAW"]}
+            "poison": ["D3IL_POISON"], "raw": ["D3IL_SK_PRELOAD_RAW"], "nopreload": ["D3IL_SK_NO_PRELOAD"], "poisonraw": ["D3IL_POISON", "D3IL_SK_PRELOAD_RAW"]}
 
 if __name__ == "__main__":
     import sys

@@ -73,6 +73,17 @@ __device__ __forceinline__ void gen_unpark_arm(const PushScratch sc, EnvState& s
   st.flags = (unsigned)GLS(GL_ARMST + 28); st.step = (int)GLS(GL_ARMST + 29);
 }
 
+#if defined(D3IL_POISON)
+// Guard build (rigid_common.h, D3IL_POISON): NaN fills of a stretch of LDS and of one environment's record area (HBM), dealt out over `nthreads` lanes.
+// What is filled when: the list of carried words next to the GL_* layout in gen_step.h.
+__device__ __forceinline__ void gen_poison_lds(double* p, int count, int idx, int nthreads) {
+  for (int q = idx; q < count; q += nthreads) ((unsigned long long*)p)[q] = D3IL_POISON_BITS;
+}
+__device__ __forceinline__ void gen_poison_records(const PushScratch sc, int idx, int nthreads) {
+  for (int q = idx; q < GG_SIZE; q += nthreads) *(__attribute__((address_space(1))) unsigned long long*)&GRS(q) = D3IL_POISON_BITS;
+}
+#endif
+
 // The physics role of the step kernel (one wave; GEN_NSUB of them per workgroup).  Built into the kernel by default.  -DD3IL_GT_INLINE makes it a function of
 // its own - called ONCE per env step, with the tree solver built INTO it: the solver's callee-saved register block (84 KB of scratch stores per wave and call,
 // profiles/r05/README.md) is then saved once per step instead of once per sub-step, and the role gets a register allocation of its own.
@@ -114,12 +125,22 @@ D3IL_GEN_ROLE_ATTR void gen_physics_role(double* __restrict__ state, unsigned* _
 #pragma clang loop unroll(disable)
   for (int s = 0; s < n_substeps; s++) {
     GEN_BARRIER_TIMED(role);
+#if defined(D3IL_POISON)
+    // nothing of the environment's block but the parked arm (GL_ARMST) is meant to outlive a sub-step, and no contact record is: the eight lanes of the
+    // environment's group poison both before phase 1 (all of them sit in this wave: a wave-level fence orders the fills before the phases' stores)
+    gen_poison_lds(tbl + col * GL_SIZE, GL_ARMST, l * GEN_NSUB + sub, GEN_MAXNB * GEN_NSUB);
+    if (e < n) gen_poison_records(sc, l * GEN_NSUB + sub, GEN_MAXNB * GEN_NSUB);
+    gen_sync();
+#endif
     PUSH_TIC;
     if (arm_lane) {
       const int b = s & 1;
       double qd[NARM], qdd[NARM], tau[NARM], ff[NFING];
 #pragma unroll
       for (int k = 0; k < NARM; k++) { qd[k] = xch[b][k][col]; qdd[k] = xch[b][NARM + k][col]; }
+#if defined(D3IL_POISON)
+      for (int k = 0; k < 2 * NARM; k++) ((unsigned long long*)&xch[b][k][col])[0] = D3IL_POISON_BITS;      // taken: the controller wave writes this buffer again after the next barrier
+#endif
       EnvState st;
       gen_unpark_arm(sc, st);
       push_control(c, st, qd, qdd, 0.04, false, tau, ff);
@@ -211,6 +232,10 @@ __global__ __launch_bounds__((1 + GEN_NSUB) * WAVE) void k_sorting_step(double* 
   const int role = threadIdx.x / WAVE;
   const PandaConsts& c = kAvoidingConsts;                // the arm is the Avoiding arm (same robot XML / gin / URDF)
   const GenConsts& gc = g_gen_consts;
+#if defined(D3IL_POISON)
+  gen_poison_lds(smem, GEN_LDS_STEP / 8, threadIdx.x, (1 + GEN_NSUB) * WAVE);      // the t blocks of all environments and both set-point buffers
+  __syncthreads();
+#endif
   if (role == 0) {
     const int e = blockIdx.x * GEN_LANES + lane;
     const bool live = lane < GEN_LANES && e < n;         // the other lanes only take part in the barriers
@@ -270,6 +295,10 @@ __global__ __launch_bounds__(WAVE) void k_sorting_reset(const double* __restrict
   PushScratch sc{(push_lds_double*)(smem + lane * GL_SIZE), (push_glb_double*)(scratch + (size_t)blockIdx.x * GG_BLOCK * GEN_LANES + 2 * lane), GEN_LANES, (push_glb_double*)(state + (size_t)42 * stride + e), stride};
   float o[GEN_SORT_OBS];
   st.flags = 0; st.step = 0;
+#if defined(D3IL_POISON)
+  gen_poison_lds(smem + lane * GL_SIZE, GL_SIZE, 0, 1);      // the lane's own block and records (one lane runs the whole environment here: no barrier)
+  gen_poison_records(sc, 0, 1);
+#endif
   gen_env_reset(kAvoidingConsts, gc, st, sc, iq, contexts + (size_t)e * 7 * gc.nb, o);
   gen_store_arm(state, flags, steps, stride, e, st, true);
   const int od = 2 + 3 * gc.nb;

@@ -117,6 +117,20 @@ constexpr int GL_PAIR = GL_TR + 6;                  // cube pair (c, d), c < d: 
 constexpr int GL_ARMST = GL_PAIR + 6;               // the arm's state between the phases of the step kernel (q[9] v[9] bias[7] tcp[3] flags step: gen_kernels.h gen_park_arm) - NOT held in registers across the phases
 constexpr int GL_SIZE = GL_ARMST + 30;
 static_assert(GL_SIZE % 2 == 1, "odd block size: the environments' blocks start on different LDS bank pairs");
+// What is CARRIED from one sub-step to the next, and what is not (the guard build -DD3IL_POISON fills everything that is not with NaN at the top of every
+// sub-step, gen_kernels.h; the host build is checked the same way by tests/test_gen_host_poison.py):
+//   carried, t area : GL_ARMST only (device: the arm's q, v, bias, tcp, flags, step, parked by the arm lane between the phases; the host build keeps the
+//                     arm in its EnvState and never touches the words).
+//   carried, other  : the cubes and the solver's warm start (GWARM) in the state buffer (w area) - gen_env_reset writes zeros there and the solvers choose
+//                     between them and GL_A0 by PF_WARM_VALID; the other set-point buffer xch[(s + 1) & 1] (the controller wave writes sub-step s + 1 into it
+//                     while the physics waves work on s; a buffer is dead once its reader has taken it).
+//   NOT carried     : GL_H .. GL_ROD (Hessian, vectors, rotations, positions, mass matrix, limit rows, arm rows of the rod contacts, rod pose): phases 1 - 3b
+//                     write them before phases 4 - 5 read them;  GL_INFO[0..4], [8], [9..12]: written by phases 1, 2 / 3, 3r, 3b of the same sub-step;
+//                     GL_INFO[5..7] (flags of lanes 1 .. 3): written AFTER the sub-step loop and read by the arm lane behind one fence;  GL_RED: written and
+//                     summed inside one line-search iteration;  GL_TR: gen_arm_reduce sets [0] = 0 before anyone reads it, [1..5] are read only where [0] == 2
+//                     was set in this sub-step;  GL_PAIR: slot (c, d) is read only where cube c's info word of this sub-step names d as a partner;
+//                     the whole g area (contact records): a record beyond its segment's count of this sub-step is never read, and of a record within the count
+//                     only the fields its writer stores (gen_put: 0 .. 15, 20, 21; the solvers' set-up loops: 16 .. 19; gen_phase3 / 3b: 22 .. 27 of rod contacts).
 // g area (HBM): contact records, GEN_SEG per cube
 constexpr int GG_CON = 0;
 constexpr int GREC = 28;   // pos[3] frame[9] dist kind a b | aref[3] Dn fric sign | jar[3] jp[3]   (sign: of the segment's cube in the row, +1 = it is geom 2)

@@ -238,6 +238,11 @@ __global__ __launch_bounds__(GEN_WAVE) void k_gen_link_guard(const LinkGuardCons
   const GenConsts& gc = g_gen_consts;
   const LinkGuardConsts& lg = *lgp;                      // (the arm is the Avoiding arm, as in the step kernel: kAvoidingConsts)
   const double* sp = state + (live ? e : 0);
+#if defined(D3IL_POISON)
+  // guard build (rigid_common.h): a capsule or cube slot that lg_test reads and lg_place skipped (fewer cubes than GEN_MAXNB) is a NaN
+  for (int q = lane; q < LG_ENVS * LG_WORK; q += GEN_WAVE) ((unsigned long long*)&work[0][0])[q] = D3IL_POISON_BITS;
+  __syncthreads();
+#endif
   if (live) {
     double q[NDOF];
 #pragma unroll

@@ -7,6 +7,17 @@
 #pragma once
 #include "panda_step.h"
 
+// -DD3IL_POISON: the read-before-write guard build of ALL kernel families (libd3il_rollout_poison.so, tests/test_gpu_poison_build.py): every LDS word of a
+// workgroup and every word of the generic engine's HBM record area starts as a NaN, and what the design does not carry from one sub-step to the next is
+// poisoned again every sub-step (cooperative engine: stack_kernels.h, D3IL_SK_POISON; generic engine and link-near guard: gen_kernels.h, link_guard.h;
+// Avoiding split kernel: rollout.hip).  Every line of it sits under the define: the product build does not change.
+#if defined(D3IL_POISON)
+#if !defined(D3IL_SK_POISON)
+#define D3IL_SK_POISON 1
+#endif
+#define D3IL_POISON_BITS 0x7ff8dead00000000ull
+#endif
+
 #if defined(D3IL_DEVICE_STATS) && defined(__HIP_DEVICE_COMPILE__)
 // -DD3IL_STATS_PER_WAVE (tools/gpu_sort_phases.py --per-wave): the rows of the timer table are WAVES (4 blockIdx + wave) instead of workgroups, and row 4 blockIdx + 3
 // holds, per wave of the generic engine's step kernel, the ticks it waited at the workgroup barrier of a sub-step (gen_kernels.h)

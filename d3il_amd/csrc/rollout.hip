@@ -165,6 +165,18 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
   if (!live) e = n - 1;                         // keep every lane in the barriers; dead lanes recompute env n-1 and store nothing
   const PandaConsts& c = kAvoidingConsts;
   (void)cp;
+#if defined(D3IL_POISON)
+  // guard build (rigid_common.h): the set-point buffers, the carried sines / cosines and the serving wave's exchange area with its four control words start as
+  // NaN.  The controller wave reads trg[0][0..13] at sub-step 0 before anyone has written them: trg[0][14] == 0 (set below) makes ik_update discard them.
+  {
+    auto poison = [](void* p, int words, int idx, int nthreads) { for (int q = idx; q < words; q += nthreads) ((unsigned long long*)p)[q] = D3IL_POISON_BITS; };
+    const int nt = (SERVE ? 3 : 2) * WAVE;
+    poison(&xch[0][0][0], 2 * 2 * NARM * WAVE, threadIdx.x, nt);
+    poison(&trg[0][0][0], 2 * (2 * NARM + 1) * WAVE, threadIdx.x, nt);
+    if (SERVE) poison(rx_smem, (int)(AVOID_LDS_SERVE / 8), threadIdx.x, nt);
+    __syncthreads();
+  }
+#endif
 #if defined(D3IL_DEVICE_STATS)
   unsigned long long t0 = wall_clock64(), tw = 0;
 #endif
@@ -257,6 +269,9 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
       double qd[NARM], qdd[NARM];
 #pragma unroll
       for (int k = 0; k < NARM; k++) { qd[k] = xch[b][k][lane]; qdd[k] = xch[b][NARM + k][lane]; }
+#if defined(D3IL_POISON)
+      for (int k = 0; k < 2 * NARM; k++) ((unsigned long long*)&xch[b][k][lane])[0] = D3IL_POISON_BITS;      // taken: the controller wave writes this buffer again after the next barrier
+#endif
       double trig[2 * NARM];
 #pragma unroll
       for (int k = 0; k < 2 * NARM; k++) trig[k] = trg[1][k][lane];
@@ -1126,7 +1141,11 @@ int d3il_create(int task_id, int n_envs, int device_id, const void* model_blob, 
       std::lock_guard<std::mutex> lock(g_model_mutex);
       g_active_gen[device_id].refs++; h->task_id = task_id;      // the constants go to the device with the first launch (GenLaunch)
     }
+#if defined(D3IL_POISON)
+    HIPCHK_H(hipMalloc(&h->d_scratch, S * GG_BLOCK * sizeof(double))); HIPCHK_H(hipMemset(h->d_scratch, 0xFF, S * GG_BLOCK * sizeof(double)));      // guard build: all-ones bytes are a quiet NaN
+#else
     HIPCHK_H(hipMalloc(&h->d_scratch, S * GG_BLOCK * sizeof(double))); HIPCHK_H(hipMemset(h->d_scratch, 0, S * GG_BLOCK * sizeof(double)));
+#endif
     if (gen_pushing) { b.info_f64 = b.state + (size_t)(gen_state_rows(h->gc.nb) - 2) * S; h->info_is_view = true; }      // info['mean_distance'], reward: the task rows of the state buffer (gen_step.h gpush_*)
     HIPCHK_H(hipFuncSetAttribute((const void*)k_sorting_step<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEN_LDS_STEP));
     HIPCHK_H(hipFuncSetAttribute((const void*)k_sorting_step<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEN_LDS_STEP));
@@ -1894,6 +1913,23 @@ int d3il_debug_scratch(d3il_handle h, int env, double* out, int count) {
     return D3IL_OK;
   }
   HIPCHK(hipMemcpy2D(out, sizeof(double), h->d_scratch + env, (size_t)h->stride * sizeof(double), sizeof(double), (size_t)count, hipMemcpyDeviceToHost));
+  return D3IL_OK;
+}
+
+/* diagnostics: the build's identity and the record-area layout (tests/test_gpu_poison_build.py checks with it that the guard build is what it loaded) */
+int d3il_debug_build_flags(int* out8) {
+  if (!out8) return fail(D3IL_EINVAL, "d3il_debug_build_flags: null argument");
+  int f = 0;
+#if defined(D3IL_POISON)
+  f |= D3IL_BUILD_POISON;
+#endif
+#if defined(D3IL_SK_POISON)
+  f |= D3IL_BUILD_SK_POISON;
+#endif
+#if defined(D3IL_DEVICE_STATS)
+  f |= D3IL_BUILD_STATS;
+#endif
+  out8[0] = f; out8[1] = GG_SIZE; out8[2] = GEN_SEG; out8[3] = GREC; out8[4] = GEN_MAXNB; out8[5] = GL_SIZE; out8[6] = GEN_LANES; out8[7] = 0;
   return D3IL_OK;
 }
 

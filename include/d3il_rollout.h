@@ -306,6 +306,12 @@ int d3il_debug_wave_counts(uint64_t* out_nwaves_x8, int nwaves, int reset);     
 /* Diagnostics: copies `count` doubles of one environment's solver scratch column (contact records of its last physics sub-step)
  * to the host; Pushing / Sorting / Stacking only. */
 int d3il_debug_scratch(d3il_handle h, int env, double* out, int count);
+/* Diagnostics: what this library was built as, and the layout of the generic engine's record area that d3il_debug_scratch copies.
+ * out8[0] = D3IL_BUILD_* bits, [1] doubles per environment (GG_SIZE), [2] records per segment (GEN_SEG; one segment per cube slot, then the arm's),
+ * [3] doubles per record (GREC), [4] cube slots (GEN_MAXNB), [5] doubles of an environment's LDS block (GL_SIZE), [6] environments per workgroup, [7] 0. */
+enum { D3IL_BUILD_POISON = 1 /* -DD3IL_POISON: the read-before-write guard build of all kernel families */, D3IL_BUILD_SK_POISON = 2 /* the cooperative engine's guard */,
+       D3IL_BUILD_STATS = 4 /* -DD3IL_DEVICE_STATS */ };
+int d3il_debug_build_flags(int* out8);
 const char* d3il_last_error(void);
 size_t d3il_blob_sizeof(void);
 int d3il_version(void);

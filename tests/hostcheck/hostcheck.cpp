@@ -112,14 +112,32 @@ int hc_gen_workspace(void* h, double* ws8) {
   for (int k = 0; k < 2; k++) { ws8[k] = p->gc.in_lo[k]; ws8[2 + k] = p->gc.in_hi[k]; ws8[4 + k] = p->gc.ws_lo[k]; ws8[6 + k] = p->gc.ws_hi[k]; }
   return p->gc.ns_core;
 }
+// read-before-write detector of the generic engine (like hc_stack_poison): when on, the t area (the device's LDS block) and the record area hold NaN before
+// every reset, env step and single sub-step; the warm start is carried in the state rows, nothing else is meant to be carried
+static int g_gen_poison = 0;
+void hc_gen_poison(int on) { g_gen_poison = on; }
+static void gen_poison_fill(GenHost* p) {
+  if (!g_gen_poison) return;
+  for (int i = 0; i < GL_SIZE; i++) p->h[i] = std::nan("");
+  for (int i = 0; i < GG_SIZE; i++) p->g[i] = std::nan("");
+}
+// what the collision phases of the last sub-step found: out[b] = the info word of cube b (contact count | partner cubes << 5 | rod contact << 9),
+// out[GEN_MAXNB] = rod <-> static box contacts (tasks that evaluate those pairs; else 0)
+void hc_gen_contact_info(void* h, int* out) {
+  GenHost* p = (GenHost*)h;
+  for (int b = 0; b < GEN_MAXNB; b++) out[b] = b < p->gc.nb ? (int)(unsigned)p->h[GL_INFO + b] : 0;
+  out[GEN_MAXNB] = p->gc.rod_static ? (int)(unsigned)p->h[GL_INFO + 8] : 0;
+}
 // s: the environment's state column (arm[42] | cubes | warm start | task words), f: flags, step
 void hc_gen_reset(void* h, const double* init_qpos, const double* ctx, double* s, int* f, float* obs) {
   GenHost* p = (GenHost*)h; EnvState st; std::memset(&st, 0, sizeof st);
+  gen_poison_fill(p);
   PushScratch sc{p->h, p->g, 1, s + 42, 1};
   gen_env_reset(p->c, p->gc, st, sc, init_qpos, ctx, obs); pack(st, s, f);
 }
 void hc_gen_step(void* h, double* s, int* f, const double* action, float* obs, unsigned char* done, int* mode_code, int fast) {
   GenHost* p = (GenHost*)h; EnvState st; unpack(s, f, st);
+  gen_poison_fill(p);
   PushScratch sc{p->h, p->g, 1, s + 42, 1};
   if (fast) gen_env_step<true>(p->c, p->gc, st, sc, action, obs, done, mode_code, p->c.n_substeps, p->c.max_steps);
   else gen_env_step<false>(p->c, p->gc, st, sc, action, obs, done, mode_code, p->c.n_substeps, p->c.max_steps);
@@ -128,8 +146,14 @@ void hc_gen_step(void* h, double* s, int* f, const double* action, float* obs, u
 void hc_gen_island_hist(long* out, int reset) { for (int k = 0; k < 80; k++) { out[k] = g_isl_hist[k]; if (reset) g_isl_hist[k] = 0; } }
 void hc_gen_substep(void* h, double* s, int* f, const double* tau, const double* ffing) {
   GenHost* p = (GenHost*)h; EnvState st; unpack(s, f, st);
+  gen_poison_fill(p);
   PushScratch sc{p->h, p->g, 1, s + 42, 1};
   gen_physics_substep(p->c, p->gc, st, sc, tau, ffing); pack(st, s, f);
+}
+// the control law of a sub-step on its own (joint PD towards q_des / qd_des + finger PD, as gen_control_and_physics applies it): torques for hc_gen_substep
+void hc_gen_control(void* h, const double* s, const int* f, const double* q_des, const double* qd_des, double* tau, double* ffing) {
+  GenHost* p = (GenHost*)h; EnvState st; unpack(s, f, st);
+  push_control(p->c, st, q_des, qd_des, 0.04, false, tau, ffing);
 }
 // ---------------------------------------------------------------- Stacking (stack_step.h)
 struct StackHost { PandaConsts c; StackConsts kc; double t[ST_SIZE]; double g[SG_SIZE]; };

@@ -119,9 +119,22 @@ class GenHostCheck:
         tau, ff = np.ascontiguousarray(tau, float), np.ascontiguousarray(ff, float)
         self.L.hc_gen_substep(self.h, _p(self.s), _p(self.f), _p(tau), _p(ff))
 
+    def control(self, q_des, qd_des):
+        """Torques of the joint PD + finger PD for the present state (what a sub-step of the env step applies), for substep()."""
+        q_des, qd_des = np.ascontiguousarray(q_des, float), np.ascontiguousarray(qd_des, float)
+        tau, ff = np.zeros(7), np.zeros(2)
+        self.L.hc_gen_control(self.h, _p(self.s), _p(self.f), _p(q_des), _p(qd_des), _p(tau), _p(ff))
+        return tau, ff
+
     def box(self, b):
         o = 42 + 13 * b
         return self.s[o:o + 3], self.s[o + 3:o + 7], self.s[o + 7:o + 13]
+
+    def contact_info(self):
+        """The last sub-step's collision result: per cube (contacts, partner-cube mask, rod contact), and the number of rod <-> static box contacts."""
+        w = np.zeros(5, dtype=np.int32)
+        self.L.hc_gen_contact_info(self.h, _p(w))
+        return [(int(x) & 31, (int(x) >> 5) & 15, (int(x) >> 9) & 1) for x in w[: self.nb]], int(w[4])
 
 
 class PushHostCheck(GenHostCheck):

@@ -96,7 +96,8 @@ def test_python_binding_constants_agree_with_the_header():
              "STACK_STATE_BOX": "D3IL_STACK_STATE_BOX", "STACK_STATE_WARM": "D3IL_STACK_STATE_WARM", "STACK_STATE_F64": "D3IL_STACK_STATE_F64",
              "SFLAG_MODE_MASK": "D3IL_SFLAG_MODE_MASK", "SFLAG_WARM_VALID": "D3IL_SFLAG_WARM_VALID", "SFLAG_HAND_NEAR": "D3IL_SFLAG_HAND_NEAR",
              "TASK_AVOIDING": "D3IL_TASK_AVOIDING", "TASK_PUSHING": "D3IL_TASK_PUSHING", "TASK_SORTING": "D3IL_TASK_SORTING",
-             "TASK_STACKING": "D3IL_TASK_STACKING", "TALLY_ROW": "D3IL_TALLY_ROW", "TALLY_ALL": "D3IL_TALLY_ALL", "ERCCL": "D3IL_ERCCL"}
+             "TASK_STACKING": "D3IL_TASK_STACKING", "TALLY_ROW": "D3IL_TALLY_ROW", "TALLY_ALL": "D3IL_TALLY_ALL", "ERCCL": "D3IL_ERCCL",
+             "BUILD_POISON": "D3IL_BUILD_POISON", "BUILD_SK_POISON": "D3IL_BUILD_SK_POISON", "BUILD_STATS": "D3IL_BUILD_STATS"}
     for py, c in pairs.items():
         assert c in h, c
         assert getattr(capi, py) == h[c], (py, getattr(capi, py), h[c])
