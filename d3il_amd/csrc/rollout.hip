@@ -72,6 +72,89 @@ __device__ __forceinline__ void store_outputs(const EnvState& st, int e, const f
   done[e] = dn; success[e] = (st.flags & F_SUCCESS) ? 1 : 0; mode[e] = (unsigned short)(st.flags & F_MODE_MASK);
 }
 
+// env.reset() of the Avoiding task has no per-environment input (no context; init_qpos is set once per handle by d3il_start): every reset of every
+// environment writes the same state rows, flags, step counter and observation.  The handle keeps that image - k_avoiding_reset run once on a one-wave
+// column set of its own when d3il_start fixes init_qpos, so the bits are by construction the ones d3il_reset produces - and whoever resets a finished lane
+// (k_avoiding_auto_reset, k_avoiding_tail, the epilogue of k_avoiding_step_split) copies column 0 of it instead of running forward dynamics again.
+struct AvoidResetImage {
+  const double* state;        // [D3IL_STATE_F64][WAVE]
+  const unsigned* flags;      // [WAVE]
+  const int* steps;           // [WAVE]
+  const float* obs;           // [2 * WAVE]
+};
+// What the random-policy harness does for ONE environment between two step launches (avoiding_sim.py:51-66), given what its step returned: the finished mask
+// (buf.last_reset), the episode counters and the per-context tally of a finished lane, its reset from the cached image with the outputs of a reset
+// (done = 0) and the re-latch of the harness pose, then the policy's NEXT action (k_policy_action with step counter t_next; a reset lane draws from its
+// re-latched pose).  k_avoiding_tail reads the block from its kernel arguments, the split step kernel from device memory (AvoidEpilogue* + t_next: two
+// scalars more in its argument list, nothing new alive across the sub-step loop).
+struct AvoidEpilogue {
+  AvoidResetImage img;
+  double* state; unsigned* flags; int* steps; float* obs; unsigned char* done; unsigned char* success; unsigned short* mode;      // the handle's buffers
+  double* des; long long* episode_counts; unsigned char* mask; const int* ctx_id; long long* table;
+  double* actions; double* des_before;
+  unsigned long long seed, env_offset;
+  int n_ctx, n, stride, pad_;
+};
+typedef const __attribute__((address_space(4))) AvoidEpilogue CEpilogue4;
+__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
+template <class IM>
+__device__ __forceinline__ void store_reset_image(const IM& im, double* __restrict__ state, unsigned* __restrict__ flags, int* __restrict__ steps, float* __restrict__ obs,
+                                                  unsigned char* __restrict__ done, unsigned char* __restrict__ success, unsigned short* __restrict__ mode, int stride, int e) {
+  const double* src = im.state;
+  double* s = state + e;
+#pragma unroll
+  for (int i = 0; i < D3IL_STATE_F64; i++) s[i * (size_t)stride] = src[i * WAVE];
+  const unsigned fl = im.flags[0];
+  flags[e] = fl; steps[e] = im.steps[0];
+  obs[2 * e] = im.obs[0]; obs[2 * e + 1] = im.obs[1];
+  done[e] = 0; success[e] = (fl & F_SUCCESS) ? 1 : 0; mode[e] = (unsigned short)(fl & F_MODE_MASK);
+}
+template <class EP>
+__device__ __forceinline__ void avoiding_tail_lane(const EP& a, unsigned t_next, int e) {
+  if (e >= a.n) return;
+  // (no __restrict__ here: in the split step kernel these are the buffers its own done / success / mode parameters point to, written before the trailing barrier)
+  unsigned char* done = a.done; unsigned char* success = a.success; unsigned short* mode = a.mode;
+  const int stride = a.stride;
+  const bool fin = done[e] != 0, ok = success[e] != 0;
+  const int code = (int)(short)mode[e];
+  a.mask[e] = fin ? 1 : 0;
+  double* des = a.des;
+  if (fin) {
+    long long* episode_counts = a.episode_counts;
+    atomicAdd((unsigned long long*)&episode_counts[0], 1ull);
+    if (ok) atomicAdd((unsigned long long*)&episode_counts[1], 1ull);
+    long long* table = a.table;
+    if (table) {
+      const int* ctx_id = a.ctx_id;
+      int c = ctx_id ? ctx_id[e] : 0;
+      if (c >= 0 && c < a.n_ctx) {
+        long long* row = table + (size_t)c * D3IL_TALLY_ROW;
+        atomicAdd((unsigned long long*)&row[0], 1ull);
+        if (ok) {
+          atomicAdd((unsigned long long*)&row[1], 1ull);
+          if (code >= 0 && code < D3IL_TALLY_ROW - 2) atomicAdd((unsigned long long*)&row[2 + code], 1ull);
+        }
+      }
+    }
+    store_reset_image(a.img, a.state, a.flags, a.steps, a.obs, done, success, mode, stride, e);
+    const double* tcp = a.img.state + D3IL_STATE_TCP * WAVE;
+#pragma unroll
+    for (int k = 0; k < 3; k++) des[k * (size_t)stride + e] = tcp[k * WAVE];
+  }
+  unsigned long long ge = a.env_offset + (unsigned long long)e;
+  const unsigned long long seed = a.seed;
+  unsigned r[4];
+  philox4x32_10((unsigned)seed, (unsigned)(seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t_next, 0u, r);
+  double u0 = r[0] * (1.0 / 4294967296.0), u1 = r[1] * (1.0 / 4294967296.0);
+  double* des_before = a.des_before;
+  const double dx = des[e], dy = des[(size_t)stride + e];
+  des_before[e] = dx; des_before[(size_t)stride + e] = dy;      // the pose this draw starts from: put back if the sequence is interrupted
+  double x = dx + (0.02 * u0 - 0.01), y = dy + (0.02 * u1 - 0.01), z = des[2 * (size_t)stride + e];
+  des[e] = x; des[(size_t)stride + e] = y;
+  double* act = a.actions + (size_t)e * 7;
+  act[0] = x; act[1] = y; act[2] = z; act[3] = 0; act[4] = 1; act[5] = 0; act[6] = 0;
+}
+
 // env.step() for the Avoiding task: controller + physics fused over all sub-steps, state stays in registers.
 template <bool FAST, bool BAKED>
 __global__ __launch_bounds__(WAVE) void k_avoiding_step(const PandaConsts* __restrict__ cp, double* __restrict__ state,
@@ -153,10 +236,12 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
                                                                   unsigned* __restrict__ flags, int* __restrict__ steps,
                                                                   const double* __restrict__ actions, float* __restrict__ obs,
                                                                   unsigned char* __restrict__ done, unsigned char* __restrict__ success,
-                                                                  unsigned short* __restrict__ mode, int n, int stride, int n_substeps, int max_steps) {
+                                                                  unsigned short* __restrict__ mode, int n, int stride, int n_substeps, int max_steps,
+                                                                  const AvoidEpilogue* __restrict__ ep, unsigned t_next) {
   __shared__ double xch[2][2 * NARM][WAVE];
   __shared__ double trg[2][2 * NARM + 1][WAVE];     // sin / cos of ikq (controller) and of the arm joints (physics) carried across the sub-steps: parked in LDS between them
   extern __shared__ double rx_smem[];             // SERVE: the rare-path exchange area
+  __shared__ unsigned long long ep_arg[3];        // the epilogue's two arguments and the workgroup index wait here for the end of the launch (written and read by the physics wave): nothing new is alive across the sub-step loop
   const int lane = threadIdx.x & (WAVE - 1);
   const int role = threadIdx.x / WAVE;          // wave-uniform: 0 controller, 1 physics, 2 (SERVE) the rare constraint paths
   RareXch rx; rx.buf = rx_smem; rx.ctl = (int*)(rx_smem + RX_ROWS * WAVE); rx.lane = lane; rx.seq = 0;
@@ -224,6 +309,7 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
 #pragma unroll
       for (int i = 0; i < NARM; i++) { so[(D3IL_STATE_IK_Q + i) * (size_t)stride] = ikq[i]; so[(D3IL_STATE_IK_QD + i) * (size_t)stride] = ikqd[i]; }
     }
+    __syncthreads();      // the trailing barrier (see the physics wave)
   } else if (SERVE && role == 2) {
     double warm[6];
     warm[5] = 0.0;
@@ -247,7 +333,11 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
 #if defined(D3IL_DEVICE_STATS)
     if (lane == 0 && blockIdx.x < 4096) g_dev_wave[blockIdx.x][7] = tw;      // the serving wave's busy ticks (replaces the sub-step counter of this slot: written last)
 #endif
+    __syncthreads();      // the trailing barrier
   } else {
+    // parked for this wave's own epilogue.  Every lane stores the same words, unconditionally: a store by one lane needs a saved exec mask here, where all the
+    // kernel arguments are alive, and that pair costs the two-wave form two more spilled SGPRs
+    ep_arg[0] = (unsigned long long)ep; ep_arg[1] = t_next; ep_arg[2] = blockIdx.x;
     EnvState st;
     load_state(state, flags, steps, stride, e, st);
     float o[2]; unsigned char dn;
@@ -297,6 +387,22 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
       flags[e] = st.flags; steps[e] = st.step;
       store_outputs(st, e, o, dn, obs, done, success, mode);
     }
+    // Epilogue of the random-policy rollout (d3il_random_rollout_step with option fuse_rollout_tail): this wave does for its own lane what k_avoiding_tail
+    // does between two launches, so a rollout step is ONE launch.  A reset lane must end with the cached IK_Q / IK_QD rows, which the controller wave stores
+    // after its own loop: one trailing barrier that every role reaches orders the two.  Dead lanes of a partial last workgroup count nothing and draw
+    // nothing.  The epilogue takes everything from its block - the buffers too,
+    // and this lane's done / success / mode as stored above - so no value of the step proper stays alive for it and the sub-step loop keeps its registers.
+    // The barrier does a second job: this kernel's state / flags / steps / obs / done / success / mode parameters are __restrict__, and the epilogue reaches
+    // the SAME memory through the pointers of its block.  The barrier is what keeps the compiler from moving those accesses across the stores above; do not
+    // remove or move it as if it only ordered IK_Q / IK_QD.
+    __syncthreads();
+    const unsigned ep_lo = __builtin_amdgcn_readfirstlane((unsigned)ep_arg[0]), ep_hi = __builtin_amdgcn_readfirstlane((unsigned)(ep_arg[0] >> 32));
+    const unsigned long long ep_bits = (unsigned long long)ep_lo | ((unsigned long long)ep_hi << 32);
+    const unsigned lane_now = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));      // (the lane index from the wave itself)
+    if (ep_bits != 0ull) {
+      const unsigned wg = __builtin_amdgcn_readfirstlane((unsigned)ep_arg[2]);
+      avoiding_tail_lane(*(CEpilogue4*)ep_bits, __builtin_amdgcn_readfirstlane((unsigned)ep_arg[1]), (int)(wg * WAVE + lane_now));
+    }
   }
 }
 
@@ -322,26 +428,17 @@ __global__ __launch_bounds__(WAVE) void k_avoiding_reset(const PandaConsts* __re
 // Auto-reset of finished environments (the rollout loop's `env.reset()` at avoiding_sim.py:51 for the next trajectory),
 // fused with the harness bookkeeping: episode counters += (finished, successful), desired pose := TCP after the reset
 // (avoiding_sim.py:53-54).  One launch instead of reset + policy_begin + three reductions.
-__global__ __launch_bounds__(WAVE) void k_avoiding_auto_reset(const PandaConsts* __restrict__ cp, const double* __restrict__ init_qpos,
-                                                              double* __restrict__ state, unsigned* __restrict__ flags, int* __restrict__ steps,
+__global__ __launch_bounds__(WAVE) void k_avoiding_auto_reset(AvoidResetImage img, double* __restrict__ state, unsigned* __restrict__ flags, int* __restrict__ steps,
                                                               float* __restrict__ obs, unsigned char* __restrict__ done,
                                                               unsigned char* __restrict__ success, unsigned short* __restrict__ mode,
                                                               double* __restrict__ des, long long* __restrict__ episode_counts, int n, int stride) {
   int e = blockIdx.x * WAVE + threadIdx.x;
   if (e >= n || !done[e]) return;
-  (void)cp;
   atomicAdd((unsigned long long*)&episode_counts[0], 1ull);
   if (success[e]) atomicAdd((unsigned long long*)&episode_counts[1], 1ull);
-  EnvState st;
-  double iq[NARM];
+  store_reset_image(img, state, flags, steps, obs, done, success, mode, stride, e);
 #pragma unroll
-  for (int k = 0; k < NARM; k++) iq[k] = init_qpos[k];
-  float o[2];
-  env_reset(kAvoidingConsts, st, iq, o);
-  store_state(state, flags, steps, stride, e, st);
-  store_outputs(st, e, o, 0, obs, done, success, mode);
-#pragma unroll
-  for (int k = 0; k < 3; k++) des[k * (size_t)stride + e] = st.tcp[k];
+  for (int k = 0; k < 3; k++) des[k * (size_t)stride + e] = img.state[(D3IL_STATE_TCP + k) * WAVE];
 }
 
 // Causal self-attention for the short token sequences of the BESO policy (DiffusionGPT of BASELINE config 5: T = 11 tokens, 6 heads
@@ -827,54 +924,10 @@ __global__ void k_policy_action_dev(double* __restrict__ des, double* __restrict
 __global__ void k_inc_counter(unsigned* __restrict__ t_dev) { if (threadIdx.x == 0 && blockIdx.x == 0) *t_dev += 1u; }
 // Everything the random-policy harness does between two step launches, in ONE launch (d3il_random_rollout_step): the mask of the environments that finished
 // (buf.last_reset), the episode counters and the per-context tally of the finished ones, their reset + re-latch (k_avoiding_auto_reset), and the policy's NEXT
-// action for every environment (k_policy_action with step counter t_next; a reset lane draws from its re-latched pose, as in the separate sequence).  A
-// rollout step is then two launches - step kernel, this kernel - instead of five and a copy.
-__global__ __launch_bounds__(WAVE) void k_avoiding_tail(const double* __restrict__ init_qpos, double* __restrict__ state, unsigned* __restrict__ flags, int* __restrict__ steps,
-                                                        float* __restrict__ obs, unsigned char* __restrict__ done, unsigned char* __restrict__ success,
-                                                        unsigned short* __restrict__ mode, double* __restrict__ des, long long* __restrict__ episode_counts,
-                                                        unsigned char* __restrict__ mask, const int* __restrict__ ctx_id, long long* __restrict__ table, int n_ctx,
-                                                        double* __restrict__ actions, double* __restrict__ des_before, unsigned long long seed, unsigned long long env_offset, unsigned t_next, int n, int stride) {
-  int e = blockIdx.x * WAVE + threadIdx.x;
-  if (e >= n) return;
-  const bool fin = done[e] != 0;
-  mask[e] = fin ? 1 : 0;
-  if (fin) {
-    const bool ok = success[e] != 0;
-    atomicAdd((unsigned long long*)&episode_counts[0], 1ull);
-    if (ok) atomicAdd((unsigned long long*)&episode_counts[1], 1ull);
-    if (table) {
-      int c = ctx_id ? ctx_id[e] : 0;
-      if (c >= 0 && c < n_ctx) {
-        long long* row = table + (size_t)c * D3IL_TALLY_ROW;
-        atomicAdd((unsigned long long*)&row[0], 1ull);
-        const int code = (int)(short)mode[e];
-        if (ok) {
-          atomicAdd((unsigned long long*)&row[1], 1ull);
-          if (code >= 0 && code < D3IL_TALLY_ROW - 2) atomicAdd((unsigned long long*)&row[2 + code], 1ull);
-        }
-      }
-    }
-    EnvState st;
-    double iq[NARM];
-#pragma unroll
-    for (int k = 0; k < NARM; k++) iq[k] = init_qpos[k];
-    float o[2];
-    env_reset(kAvoidingConsts, st, iq, o);
-    store_state(state, flags, steps, stride, e, st);
-    store_outputs(st, e, o, 0, obs, done, success, mode);
-#pragma unroll
-    for (int k = 0; k < 3; k++) des[k * (size_t)stride + e] = st.tcp[k];
-  }
-  unsigned long long ge = env_offset + (unsigned long long)e;
-  unsigned r[4];
-  philox4x32_10((unsigned)seed, (unsigned)(seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t_next, 0u, r);
-  double u0 = r[0] * (1.0 / 4294967296.0), u1 = r[1] * (1.0 / 4294967296.0);
-  des_before[e] = des[e]; des_before[(size_t)stride + e] = des[(size_t)stride + e];      // the pose this draw starts from: put back if the sequence is interrupted
-  double x = des[e] + (0.02 * u0 - 0.01), y = des[(size_t)stride + e] + (0.02 * u1 - 0.01), z = des[2 * (size_t)stride + e];
-  des[e] = x; des[(size_t)stride + e] = y;
-  double* a = actions + (size_t)e * 7;
-  a[0] = x; a[1] = y; a[2] = z; a[3] = 0; a[4] = 1; a[5] = 0; a[6] = 0;
-}
+// action for every environment (k_policy_action with step counter t_next; a reset lane draws from its re-latched pose, as in the separate sequence).
+// This kernel runs behind the one-wave step kernel only (split_waves = 0, lanes_per_wave < 64): a rollout step is there two launches - step kernel, this
+// kernel - instead of five and a copy.  The split step kernels run the same per-lane function (avoiding_tail_lane) as their epilogue: one launch.
+__global__ __launch_bounds__(WAVE) void k_avoiding_tail(AvoidEpilogue a, unsigned t_next) { avoiding_tail_lane(a, t_next, (int)(blockIdx.x * WAVE + threadIdx.x)); }
 __global__ void k_restore_des(double* __restrict__ des, const double* __restrict__ des_before, int n, int stride) {
   int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
@@ -987,7 +1040,10 @@ struct d3il_handle_s {
   hipGraph_t rg_graph[RG_SLOTS]; hipGraphExec_t rg_exec[RG_SLOTS];
   unsigned* rg_t_dev; uint32_t rg_next_t; long rg_launched, rg_drained;
   uint64_t rg_seed, rg_off; double* rg_actions; int64_t* rg_counts; hipStream_t rg_stream;
-  // fused tail of the Avoiding rollout step (k_avoiding_tail): the next step's action is already in `actions` when these match the next call
+  // Avoiding: the post-reset image of one environment (AvoidResetImage; filled by d3il_start) and the device copy of the epilogue's argument block
+  // (epilogue_stream: the stream whose launches read it)
+  void* d_reset_img; AvoidResetImage reset_img; AvoidEpilogue* d_epilogue; AvoidEpilogue epilogue_host; bool epilogue_valid; hipStream_t epilogue_stream;
+  // rollout tail of the Avoiding step (epilogue of the split step kernel, or k_avoiding_tail): the next step's action is already in `actions` when these match the next call
   bool prep_valid; uint32_t prep_t; uint64_t prep_seed, prep_off; double* prep_actions; bool fuse_tail; double* d_des_before; hipStream_t prep_stream;
   bool info_is_view;       // buf.info_f64 points into buf.state (Pushing on the generic engine: its two task rows) - not freed on its own
   // link-near guard of the generic engine (link_guard.h, d3il_set_link_guard): lg.n = 0 = off
@@ -1036,7 +1092,7 @@ static void free_handle(d3il_handle_s* h) {
     if (h->task_id == D3IL_TASK_STACKING && g_active_stack[dev].refs > 0) g_active_stack[dev].refs--;
   }
   void* ptrs[] = {h->dc, h->d_init_qpos, h->buf.obs, h->buf.done, h->buf.success, h->buf.mode, h->buf.state, h->buf.flags, h->buf.step_count, h->buf.policy_des,
-                  h->info_is_view ? nullptr : (void*)h->buf.info_f64, h->d_scratch, h->d_ctx, h->d_mask, h->d_des_before, h->d_lg};
+                  h->info_is_view ? nullptr : (void*)h->buf.info_f64, h->d_scratch, h->d_ctx, h->d_mask, h->d_des_before, h->d_lg, h->d_reset_img, h->d_epilogue};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->ring_created) for (int i = 0; i < 128; i++) { (void)hipEventDestroy(h->ring0[i]); (void)hipEventDestroy(h->ring1[i]); }
   rg_drop_for_free(h);
@@ -1119,6 +1175,10 @@ int d3il_create(int task_id, int n_envs, int device_id, const void* model_blob, 
       (void)hipGetLastError();
       h->serve_avail = false; h->serve_max_wg = 0;
     }
+    // one-wave column set for the cached reset image: state rows | flags | steps | obs | done | success | mode
+    const size_t img_bytes = (size_t)WAVE * (D3IL_STATE_F64 * sizeof(double) + sizeof(unsigned) + sizeof(int) + 2 * sizeof(float) + 2 + sizeof(unsigned short));
+    HIPCHK_H(hipMalloc(&h->d_reset_img, img_bytes)); HIPCHK_H(hipMemset(h->d_reset_img, 0, img_bytes));
+    HIPCHK_H(hipMalloc(&h->d_epilogue, sizeof(AvoidEpilogue)));
   }
   HIPCHK_H(hipMemcpy(h->dc, &h->hc, sizeof(PandaConsts), hipMemcpyHostToDevice));
   HIPCHK_H(hipMalloc(&h->d_init_qpos, 7 * sizeof(double)));
@@ -1195,6 +1255,20 @@ int d3il_start(d3il_handle h, const double* init_qpos7) {
   for (int k = 0; k < 7; k++) if (!(init_qpos7[k] == init_qpos7[k])) return fail(D3IL_EINVAL, "d3il_start: init_qpos contains NaN");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemcpy(h->d_init_qpos, init_qpos7, 7 * sizeof(double), hipMemcpyHostToDevice));
+  if (h->task_id == D3IL_TASK_AVOIDING) {
+    // the cached reset image follows init_qpos: k_avoiding_reset itself, on one environment of the handle's one-wave column set (the bits d3il_reset gives)
+    double* st = (double*)h->d_reset_img;
+    unsigned* fl = (unsigned*)(st + (size_t)D3IL_STATE_F64 * WAVE);
+    int* sc = (int*)(fl + WAVE);
+    float* ob = (float*)(sc + WAVE);
+    unsigned char* dn = (unsigned char*)(ob + 2 * WAVE);
+    unsigned short* md = (unsigned short*)(dn + 2 * WAVE);
+    HIPCHK(hipDeviceSynchronize());      // nothing in flight reads the image while it changes
+    hipLaunchKernelGGL(k_avoiding_reset, dim3(1), dim3(WAVE), 0, (hipStream_t)nullptr, h->dc, h->d_init_qpos, (const unsigned char*)nullptr, st, fl, sc, ob, dn, dn + WAVE, md, 1, WAVE);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    h->reset_img.state = st; h->reset_img.flags = fl; h->reset_img.steps = sc; h->reset_img.obs = ob;
+  }
   h->started = true;
   return D3IL_OK;
 }
@@ -1262,7 +1336,7 @@ static int sync_solver_tol(d3il_handle_s* h, hipStream_t s) {
   return D3IL_OK;
 }
 
-// The fused rollout tail (k_avoiding_tail) has already drawn the NEXT step's action and advanced the harness pose by it.  Any other call that reads or writes
+// The fused rollout tail (the epilogue of the split step kernels, or k_avoiding_tail) has already drawn the NEXT step's action and advanced the harness pose by it.  Any other call that reads or writes
 // the pose / the actions ends that sequence: the pose goes back to where the draw started (on the stream of the sequence, ordered before whatever follows on
 // that stream; a caller that switches streams between calls synchronises them itself, as everywhere in this interface).
 static int drop_prepared_action(d3il_handle_s* h) {
@@ -1341,7 +1415,11 @@ static int timing_begin(d3il_handle h, hipStream_t s) {
   HIPCHK(hipEventRecord(h->ev0, s));
   return D3IL_OK;
 }
-int d3il_step(d3il_handle h, const double* actions, void* stream) {
+// ep / t_next: the rollout epilogue of the Avoiding split kernels (AvoidEpilogue in device memory; null: none).  The caller has checked split_step_kernel(h).
+static bool split_step_kernel(const d3il_handle_s* h) { return h->task_id == D3IL_TASK_AVOIDING && h->fast && h->lanes == WAVE && h->split != 0; }
+static int step_launch(d3il_handle h, const double* actions, void* stream, const AvoidEpilogue* ep, unsigned t_next);
+int d3il_step(d3il_handle h, const double* actions, void* stream) { return step_launch(h, actions, stream, nullptr, 0u); }
+static int step_launch(d3il_handle h, const double* actions, void* stream, const AvoidEpilogue* ep, unsigned t_next) {
   if (!h || !actions) return fail(D3IL_EINVAL, "d3il_step: null argument");
   if (int rc_ = drop_prepared_action(h)) return rc_;
   if (!h->started) return fail(D3IL_ESTATE, "d3il_step: d3il_start() has not been called");
@@ -1401,14 +1479,15 @@ int d3il_step(d3il_handle h, const double* actions, void* stream) {
   if (h->timing && !h->rg_capturing) { if (int rc_ = timing_begin(h, s)) return rc_; }
   // the two-wave kernel wins at every batch size measured (4096 ... 262144 envs: +64 % ... +20 %): at small N the second
   // wave uses an idle SIMD, at saturation its 256-VGPR roles run two waves per SIMD and hide FP64 latency
-  bool split = h->fast && h->lanes == WAVE && h->split != 0;
+  const bool split = split_step_kernel(h);
+  if (ep && !split) return fail(D3IL_ESTATE, "d3il_step: the rollout epilogue needs the split step kernel");
   // the third wave (rare constraint paths) while a CU hosts one workgroup anyway; at saturation the two-wave form keeps two workgroups per CU
   if (split && nwg <= h->serve_max_wg)
     hipLaunchKernelGGL((k_avoiding_step_split<true, true>), dim3(nwg), dim3(3 * WAVE), AVOID_LDS_SERVE, s, h->dc, b.state, b.flags, b.step_count, actions, b.obs, b.done,
-                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps);
+                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, ep, t_next);
   else if (split)
     hipLaunchKernelGGL((k_avoiding_step_split<true, false>), dim3(nwg), dim3(2 * WAVE), 0, s, h->dc, b.state, b.flags, b.step_count, actions, b.obs, b.done,
-                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps);
+                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, ep, t_next);
   else if (h->fast)
     hipLaunchKernelGGL((k_avoiding_step<true, true>), dim3(nwg), dim3(WAVE), lds, s, h->dc, b.state, b.flags, b.step_count, actions, b.obs, b.done,
                        b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, h->lanes);
@@ -1617,7 +1696,7 @@ int d3il_auto_reset(d3il_handle h, int64_t* episode_counts_device, void* stream)
     HIPCHK(hipGetLastError());
   }
   if (avoiding) {
-    hipLaunchKernelGGL(k_avoiding_auto_reset, dim3(h->stride / WAVE), dim3(WAVE), 0, s, h->dc, h->d_init_qpos, b.state, b.flags, b.step_count,
+    hipLaunchKernelGGL(k_avoiding_auto_reset, dim3(h->stride / WAVE), dim3(WAVE), 0, s, h->reset_img, b.state, b.flags, b.step_count,
                        b.obs, b.done, b.success, b.mode, b.policy_des, (long long*)episode_counts_device, h->n, h->stride);
     HIPCHK(hipGetLastError());
     return D3IL_OK;
@@ -1826,18 +1905,34 @@ int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, 
     return D3IL_OK;
   }
   if (h && h->fuse_tail && h->task_id == D3IL_TASK_AVOIDING && actions && episode_counts_device && h->started) {
-    // two launches per step: the step kernel and k_avoiding_tail (mask, tally, auto-reset, the NEXT step's action); the first call of a sequence (or one
-    // whose arguments / step counter do not continue the previous call) starts with the separate policy kernel
+    // ONE launch per step: the split step kernel with its rollout epilogue (mask, tally, reset from the cached image, the NEXT step's action); the one-wave
+    // step kernel is followed by k_avoiding_tail instead.  The first call of a sequence (or one whose arguments / step counter do not continue the previous
+    // call) starts with the separate policy kernel
     const bool cont = h->prep_valid && h->prep_t == t && h->prep_seed == seed && h->prep_off == env_offset && h->prep_actions == actions && h->prep_stream == (hipStream_t)stream;
     if (!h->d_des_before) { HIPCHK(hipSetDevice(h->device)); HIPCHK(hipMalloc(&h->d_des_before, (size_t)h->stride * 2 * sizeof(double))); }
     if (cont) h->prep_valid = 0;          // consumed: the calls below must not put the pose back
     else { if (int rc = d3il_policy_action(h, seed, env_offset, t, actions, stream)) return rc; }      // (d3il_policy_action drops a stale prepared action first)
-    if (int rc = d3il_step(h, actions, stream)) return rc;
     d3il_buffers& b = h->buf;
-    hipLaunchKernelGGL(k_avoiding_tail, dim3(h->stride / WAVE), dim3(WAVE), 0, (hipStream_t)stream, h->d_init_qpos, b.state, b.flags, b.step_count, b.obs, b.done, b.success, b.mode,
-                       b.policy_des, (long long*)episode_counts_device, h->d_mask, h->tally_ctx, (long long*)h->tally_table, h->tally_nctx, actions, h->d_des_before,
-                       (unsigned long long)seed, (unsigned long long)env_offset, t + 1u, h->n, h->stride);
-    HIPCHK(hipGetLastError());
+    AvoidEpilogue a{};
+    a.img = h->reset_img; a.state = b.state; a.flags = b.flags; a.steps = b.step_count; a.obs = b.obs; a.done = b.done; a.success = b.success; a.mode = b.mode;
+    a.n = h->n; a.stride = h->stride; a.des = b.policy_des; a.episode_counts = (long long*)episode_counts_device; a.mask = h->d_mask; a.ctx_id = h->tally_ctx;
+    a.table = (long long*)h->tally_table; a.actions = actions; a.des_before = h->d_des_before; a.seed = seed; a.env_offset = env_offset; a.n_ctx = h->tally_nctx;
+    if (split_step_kernel(h)) {
+      // the device copy of the block follows the arguments: rewritten (on this stream, before the launch that reads it) only when one of them changed.
+      // A launch that still reads the old block is ordered before the copy on its own stream only: when the stream changed too, wait for the device first
+      if (!h->epilogue_valid || std::memcmp(&h->epilogue_host, &a, sizeof a) != 0) {
+        HIPCHK(hipSetDevice(h->device));
+        if (h->epilogue_valid && h->epilogue_stream != (hipStream_t)stream) HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpyAsync(h->d_epilogue, &a, sizeof a, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // `a` is on the stack
+        h->epilogue_host = a; h->epilogue_valid = true; h->epilogue_stream = (hipStream_t)stream;
+      }
+      if (int rc = step_launch(h, actions, stream, h->d_epilogue, t + 1u)) return rc;
+    } else {
+      if (int rc = d3il_step(h, actions, stream)) return rc;
+      hipLaunchKernelGGL(k_avoiding_tail, dim3(h->stride / WAVE), dim3(WAVE), 0, (hipStream_t)stream, a, t + 1u);
+      HIPCHK(hipGetLastError());
+    }
     h->prep_valid = true; h->prep_t = t + 1u; h->prep_seed = seed; h->prep_off = env_offset; h->prep_actions = actions; h->prep_stream = (hipStream_t)stream;
     return D3IL_OK;
   }

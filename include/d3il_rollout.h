@@ -268,7 +268,17 @@ int d3il_last_step_ms(d3il_handle h, float* ms);
  * for a launch it has just enqueued).  Drains the ring and returns out4 = {sum of the launch durations in ms, min, max, number of launches} since d3il_set_timing(h, 1). */
 int d3il_timing_stats(d3il_handle h, double* out4);
 /* One host call for one iteration of the rollout loops (fewer trips through the binding when a GPU's environments are stepped as several sub-batches):
- * d3il_step_auto_reset = d3il_step + d3il_auto_reset; d3il_random_rollout_step = d3il_policy_action + d3il_step + d3il_auto_reset (BASELINE config 2). */
+ * d3il_step_auto_reset = d3il_step + d3il_auto_reset; d3il_random_rollout_step = d3il_policy_action + d3il_step + d3il_auto_reset (BASELINE config 2).
+ * d3il_random_rollout_step with option "fuse_rollout_tail" (Avoiding): a call that continues the previous one (same seed, env_offset, actions, stream, t = previous
+ * t + 1, nothing else called on the handle in between) is ONE kernel launch - the split step kernel, whose physics wave does for its own environment, after
+ * the step, what the harness does between two steps: last_reset mask, episode counters and tally, reset of a finished environment from the handle's cached
+ * post-reset image (d3il_start computes it once per init_qpos with the reset kernel itself), re-latch of the harness pose, and the policy's action for step t + 1,
+ * which it leaves in `actions`.  The first call of a sequence launches the policy kernel first.  Any other call that reads or writes the harness pose or the actions
+ * (d3il_reset, d3il_step, d3il_set_state, d3il_policy_begin / _action, d3il_auto_reset, an option) ends the sequence: the pose is put back to where the prepared
+ * draw started.  With the one-wave step kernel (split_waves = 0, lanes_per_wave < 64) the same work runs as a second launch (k_avoiding_tail).
+ * Cost of a change: the kernel reads seed, env_offset, `actions` and `episode_counts_device` from a small per-handle device block.  A call in which one of
+ * them differs from the previous call rewrites the block and waits for the stream (for the whole device when the stream changed as well) before it launches:
+ * once per sequence in a rollout loop, but a host synchronisation per step for a caller that alternates seed or buffers from step to step. */
 int d3il_step_auto_reset(d3il_handle h, const double* actions, int64_t* episode_counts_device, void* stream);
 int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream);
 /* Option "graph_rollout": captures the graphs the next d3il_random_rollout_step calls with these arguments will launch, without launching anything (outside a timed region). */
@@ -284,9 +294,10 @@ int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offse
  * (the legacy default stream cannot be captured); any later option / timing / tally change drops the graphs, the next call re-captures.  With timing enabled every
  * eighth step runs uncaptured with the event pair around its step launch (event nodes inside a graph give no timestamps with this runtime): d3il_timing_stats
  * then covers a uniform 1-in-8 sample of the launches;
- * "fuse_rollout_tail" (default 0): Avoiding - d3il_random_rollout_step as TWO launches: the step kernel and one kernel that does everything between two
- * steps (last_reset mask, episode counters and tally of the finished environments, their reset and re-latch, and the policy's action for the NEXT step -
- * which the next call of an uninterrupted sequence finds in `actions`); same results as the five launches and the copy it replaces. */
+ * "fuse_rollout_tail" (default 0): Avoiding - d3il_random_rollout_step as ONE launch: the split step kernel does everything between two steps as its epilogue
+ * (last_reset mask, episode counters and tally of the finished environments, their reset and re-latch, and the policy's action for the NEXT step - which the
+ * next call of an uninterrupted sequence finds in `actions`); two launches with the one-wave step kernel; same results as the five launches and the copy it
+ * replaces. */
 int d3il_set_option(d3il_handle h, const char* name, int value);
 /* Link-near guard of the generic engine (Pushing / Sorting / Inserting; csrc/link_guard.h).  The engine collides only the rod with the scene; the model's other robot
  * collision hulls (panda_rod_invisible.xml: link0 .. link7, hand, fingers, finger tips) are not evaluated.  With capsules set, every d3il_step ends with one more small
