@@ -10,6 +10,8 @@
 // core (22-bit significands); `hh` and the cross terms accumulate separately and are combined once per output (acc_hh + 2^-11 acc_x).  Operands carry 22 of the 24
 // bits of an f32, so a 120-term dot product differs from the f32-FMA chain by about as much as two f32 summation orders differ from each other (measured against an
 // f64 reference in tests/test_policies_f16x3.py).  Range: |operand| <= 65504 (saturating) - LayerNorm outputs, GELU outputs and weights are O(1).
+// The saturation is silent in the default instantiations (GUARD = false), and it is expected to swallow a NaN / Inf operand too (the clamp returns its bound; not asserted by a test).  The
+// GUARD = true instantiations (d3il_f16x3_set_guard; "range / NaN guard" below) count the rows it touched and let a non-finite operand through as NaN.
 // The kernels keep the structure of k_mlp_gelu_residual_f32 / k_linear120_f32 (rollout.hip): one wave owns 16 token rows, the transposed product D[feature][row]
 // makes the D registers of the first MLP product the B operand of the second, four waves share the weight stream through a double-buffered LDS stage.
 #pragma once
@@ -34,11 +36,53 @@ __device__ __forceinline__ void hx_split(float x, _Float16& hi, _Float16& lo) {
   hi = (_Float16)x;
   lo = (_Float16)((x - (float)hi) * HX_LO);
 }
+// ---- range / NaN guard (the GUARD = true instantiations of the three kernels; off by default, d3il_f16x3_set_guard).
+// At every split site (the loaded / layer-normalised row; the GELU outputs; the attention outputs):
+//   finite |x| > 65504: saturates exactly as without the guard (the row's output is bit-identical), the row is marked CLIPPED;
+//   NaN / +-Inf: the operand's f16 halves become NaN - the matrix core then makes the row NaN in every output column, as the f32 kernels do, and no other row
+//                (lane (g, j) holds data of row j only, in the B operands and in the D tiles) -, the row is marked NON-FINITE.
+// counts[0] += live rows of the launch marked clipped, counts[1] += marked non-finite (each row at most once per counter and launch, whatever the number of
+// operands and sites; it may be in both), counts[2] += 1 per launch; counts[3] is not touched.  Padding lanes (rows >= M re-reading row M - 1, tokens >= T, dead
+// waves) never count.
+// Per value the guard keeps a running maximum and minimum of ONE integer key of the value: key = (bits << 1) + 2^24 (modulo 2^32) drops the sign, maps the finite
+// values monotonically in |x| to 2^24 .. 2^32 - 2 and wraps NaN / Inf (exponent field all ones) to 0 .. 2^24 - 2: max key > key(65504) <=> some finite |x| > 65504,
+// min key < 2^24 <=> some non-finite x.  v_lshl_add_u32 and a share of a v_max3_u32 / v_min3_u32: two vector instructions per value, tested once per site.
+// The device pass is compiled with -ffinite-math-only: a floating-point isnan / isfinite folds to false, a bit test of a float that was just COMPUTED is recognised
+// as a class test and folds too (panda_step.h action_is_bad), and an FP select of a NaN constant may be dropped.  Hence the bits pass through an empty asm (opaque
+// to the optimiser, no instruction) and the NaN halves are put in with integer selects on the packed registers.
+constexpr unsigned HXG_BIAS = 0x01000000u, HXG_CLIP = (0x477FE000u << 1) + HXG_BIAS;      // key(+-0) = the smallest finite key; key(65504.f)
+typedef unsigned hx_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void hx_track(float x, unsigned& khi, unsigned& klo) {
+  unsigned b = __float_as_uint(x);
+  asm("" : "+v"(b));
+  const unsigned key = (b << 1) + HXG_BIAS;
+  khi = max(khi, key); klo = min(klo, key);
+}
+// all eight halves NaN (0x7E00) if `bad`
+__device__ __forceinline__ hx_h8 hx_poison(hx_h8 v, bool bad) {
+  hx_u4 u = __builtin_bit_cast(hx_u4, v);
+#pragma unroll
+  for (int e = 0; e < 4; e++) u[e] = bad ? 0x7E007E00u : u[e];
+  return __builtin_bit_cast(hx_h8, u);
+}
+// End of a guarded launch: a row's mark is the OR over its four g lanes (lanes j, 16 + j, 32 + j, 48 + j of the wave), one pop count and at most one atomic per
+// counter and wave - a clean launch issues only the launch counter's.  Called by whole waves (the ballots).
+__device__ __forceinline__ void hx_guard_count(bool live, unsigned khi, unsigned klo, long long* counts) {
+  unsigned long long bc = __ballot(live && khi > HXG_CLIP), bn = __ballot(live && klo < HXG_BIAS);
+  bc |= bc >> 32; bc |= bc >> 16; bn |= bn >> 32; bn |= bn >> 16;
+  const int nc = __popc((unsigned)bc & 0xffffu), nn = __popc((unsigned)bn & 0xffffu);
+  if ((threadIdx.x & 63) == 0) {
+    if (nc) atomicAdd((unsigned long long*)counts + 0, (unsigned long long)nc);
+    if (nn) atomicAdd((unsigned long long*)counts + 1, (unsigned long long)nn);
+    if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd((unsigned long long*)counts + 2, 1ull);
+  }
+}
 // Row `rr` of src[.][120] in the B-operand order of v_mfma_f32_16x16x32_f16: lane (g, j) holds, for K step s, the elements 32 s + 8 g + e (e = 0 .. 7) of row j
 // (zero beyond 120), optionally layer-normalised first (nn.LayerNorm over the 120 features, biased variance: the four lane groups of a row hold 32 / 32 / 32 / 24 of
-// its elements, the two row sums take two cross-group exchanges), split into the f16 halves.
+// its elements, the two row sums take two cross-group exchanges), split into the f16 halves.  GUARD: the operands (after the LayerNorm) are a split site.
+template <bool GUARD>
 __device__ __forceinline__ void hx_load_row(const float* __restrict__ src, long rr, int g, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
-                                            hx_h8* hh, hx_h8* hl) {
+                                            hx_h8* hh, hx_h8* hl, unsigned& khi, unsigned& klo) {
   float v[32];
 #pragma unroll
   for (int s = 0; s < 4; s++) {
@@ -79,6 +123,13 @@ __device__ __forceinline__ void hx_load_row(const float* __restrict__ src, long 
   for (int s = 0; s < 4; s++)
 #pragma unroll
     for (int e = 0; e < 8; e++) { _Float16 a, b; hx_split(v[8 * s + e], a, b); hh[s][e] = a; hl[s][e] = b; }
+  if constexpr (GUARD) {
+#pragma unroll
+    for (int k = 0; k < 32; k++) hx_track(v[k], khi, klo);
+    const bool bad = klo < HXG_BIAS;
+#pragma unroll
+    for (int s = 0; s < 4; s++) { hh[s] = hx_poison(hh[s], bad); hl[s] = hx_poison(hl[s], bad); }
+  }
 }
 // erf(x) without branches: libm's erff takes one of two paths per lane (|x| < 1: odd polynomial; else 1 - exp(-p(|x|))) and a wave with both kinds of lanes runs both
 // under exec masks, with a jump each - eight evaluations per lane and hidden pair were the longest serial part of the MLP kernel.  The same two minimax forms
@@ -135,12 +186,15 @@ __device__ __forceinline__ void hx_split2(hx_f2 v, hx_h2& hi, hx_h2& lo) {
 // SOFTWARE PIPELINE: stage k issues the first product of pair k, the GELU of pair k - 1 and the second product of pair k - 1.  The three are independent inside a
 // stage, so the matrix pipe works on one pair while the vector pipe computes the other's GELU (as one chain - first product, GELU, second product per pair - a
 // wave's matrix and vector work did not overlap at all: profiles/r06/f16x3_mlp_ablation.log).  The two empty half stages (k = 0: zero W2, k = HX_PAIRS: zero W1)
-// run like every other - no branches inside the loop body.
+// run like every other - no branches inside the loop body.  GUARD: the GELU of "pair -1" in stage 0 is GELU(0 + 0) = 0 and the first product of the last stage
+// is never read, so the two empty half stages produce no marks; a lane that has seen a non-finite operand (the input row or a GELU output) keeps its B operands NaN
+// for the rest of the launch (selects, no branch) - its row is NaN in every column from the first one on.
 constexpr int HX_STAGES = HX_PAIRS + 1;
-template <int NW>      // waves per workgroup: 16 NW rows share one pass over the weights
+template <int NW, bool GUARD = false>      // waves per workgroup: 16 NW rows share one pass over the weights
 __global__ __launch_bounds__(64 * NW, 2) void k_mlp_gelu_residual_f16x3(const float* __restrict__ h, const float* __restrict__ x, const hx_h8* __restrict__ wp,
                                                                           const float* __restrict__ b1, const float* __restrict__ b2, float* __restrict__ out, long M,
-                                                                          const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps) {
+                                                                          const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                                          long long* counts = nullptr) {
   __shared__ hx_h8 sw[2][HX_PAIR_V];
   __shared__ hx_f4 sb1[HX_H / 4 + 8];      // fc1's bias, one zero row of 32 in front (the GELU of "pair -1" in stage 0 reads it)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
@@ -151,7 +205,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_mlp_gelu_residual_f16x3(const fl
   if (tid < 8) sb1[tid] = hx_f4{0.f, 0.f, 0.f, 0.f};
   if (tid < HX_H / 4) sb1[8 + tid] = ((const hx_f4*)b1)[tid];
   hx_h8 hh[4], hl[4];
-  hx_load_row(h, rr, g, ln_w, ln_b, eps, hh, hl);
+  unsigned khi = 0u, klo = ~0u;      // the guard's running key maximum / minimum of this lane (GUARD only)
+  hx_load_row<GUARD>(h, rr, g, ln_w, ln_b, eps, hh, hl, khi, klo);
   hx_f4 acc2h[8], acc2x[8];
 #pragma unroll
   for (int t = 0; t < 8; t++) { acc2h[t] = hx_f4{0.f, 0.f, 0.f, 0.f}; acc2x[t] = hx_f4{0.f, 0.f, 0.f, 0.f}; }
@@ -203,8 +258,10 @@ __global__ __launch_bounds__(64 * NW, 2) void k_mlp_gelu_residual_f16x3(const fl
         hx_h2 a2, b2;
         hx_split2(gv, a2, b2);
         gh[4 * tile + r] = a2[0]; gh[4 * tile + r + 1] = a2[1]; gl[4 * tile + r] = b2[0]; gl[4 * tile + r + 1] = b2[1];
+        if constexpr (GUARD) { hx_track(gv[0], khi, klo); hx_track(gv[1], khi, klo); }
       }
     }
+    if constexpr (GUARD) { const bool bad = klo < HXG_BIAS; gh = hx_poison(gh, bad); gl = hx_poison(gl, bad); }
     // ---- second product of pair k - 1
 #if defined(HX_ABLATE) && (HX_ABLATE & 2)
     acc2h[0][0] += (float)gh[0] + (float)gl[0] + (float)gh[5] + (float)gl[6];
@@ -229,6 +286,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_mlp_gelu_residual_f16x3(const fl
     }
     __syncthreads();
   }
+  if constexpr (GUARD) hx_guard_count(live, khi, klo, counts);
   if (!live) return;
 #pragma unroll
   for (int t = 0; t < 8; t++) {
@@ -241,9 +299,11 @@ __global__ __launch_bounds__(64 * NW, 2) void k_mlp_gelu_residual_f16x3(const fl
 
 // out[M][N] = (LayerNorm)(xin)[M][120] W^T + bias (+ resid).  wp: ceil(N / 16) tiles of 512 vectors (policies.py pack_linear120_weights_f16x3):
 //   vector (s * 2 + p) * 64 + lane of tile t = W_p[16 t + i][32 s + 8 g + e], zero beyond N rows / 120 columns.  Two tiles per LDS stage.
-template <int NW>
+// GUARD: one split site, the input row; counted before the products.
+template <int NW, bool GUARD = false>
 __global__ __launch_bounds__(64 * NW) void k_linear120_f16x3(const float* __restrict__ xin, const hx_h8* __restrict__ wp, const float* __restrict__ bias, const float* __restrict__ resid,
-                                                          float* __restrict__ out, long M, int N, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps) {
+                                                          float* __restrict__ out, long M, int N, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                          long long* counts = nullptr) {
   __shared__ hx_h8 sw[2][1024];
   __shared__ hx_f4 sbias[96];      // N <= 384 (checked by the caller)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
@@ -253,7 +313,9 @@ __global__ __launch_bounds__(64 * NW) void k_linear120_f16x3(const float* __rest
   const long rr = live ? row : (M - 1);
   if (tid < 96) sbias[tid] = 4 * tid < N ? ((const hx_f4*)bias)[tid] : hx_f4{0.f, 0.f, 0.f, 0.f};
   hx_h8 hh[4], hl[4];
-  hx_load_row(xin, rr, g, ln_w, ln_b, eps, hh, hl);
+  unsigned khi = 0u, klo = ~0u;
+  hx_load_row<GUARD>(xin, rr, g, ln_w, ln_b, eps, hh, hl, khi, klo);
+  if constexpr (GUARD) hx_guard_count(live, khi, klo, counts);
   const int ntiles = (N + 15) / 16, nstages = (ntiles + 1) / 2;      // (the packed buffer is padded to an even number of tiles)
   hx_h8 pre[VPT];
 #pragma unroll
@@ -303,9 +365,12 @@ __global__ __launch_bounds__(64 * NW) void k_linear120_f16x3(const float* __rest
 // T <= 16.  The weight stream: two tiles (16 KB) per stage, double buffered.  At 45056 token rows: 59.9 us against 69.5 us for the three kernels it replaces
 // (87.9 us with four waves per workgroup and one lane per (token, head pair); 65.4 us as two workgroups of four waves per CU with a single weight buffer and
 // two barriers per tile - profiles/r06/attn_half/).
-template <int NW, int TR>
+// GUARD: two split sites, the layer-normalised row and the attention output row of token j; a NaN token makes the later tokens of its sequence NaN through the
+// attention itself (its key and value rows), as in k_attention_causal_f32, and they are marked at the second site.
+template <int NW, int TR, bool GUARD = false>
 __global__ __launch_bounds__(64 * NW) void k_attn_half_f16x3(const float* __restrict__ x, const hx_h8* __restrict__ wp, const float* __restrict__ bqkv, const float* __restrict__ bproj,
-                                                             float* __restrict__ out, long B, int T, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps) {
+                                                             float* __restrict__ out, long B, int T, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+                                                             long long* counts = nullptr) {
   constexpr int C = HX_C, H = 6, D = 20, QKV_STAGES = 12, STAGES = 16, RS = 3 * HX_C;
   __shared__ hx_h8 sw[2][1024];
   __shared__ hx_f4 sbias[96 + 32];      // q | k | v bias (90 vectors, zero padded to 96), then the projection's (30, padded to 32)
@@ -317,7 +382,8 @@ __global__ __launch_bounds__(64 * NW) void k_attn_half_f16x3(const float* __rest
   const long row = (seq < B ? seq : B - 1) * T + (j < T ? j : T - 1);
   for (int q = tid; q < 128; q += NT) sbias[q] = q < 90 ? ((const hx_f4*)bqkv)[q] : (q >= 96 && q < 126 ? ((const hx_f4*)bproj)[q - 96] : hx_f4{0.f, 0.f, 0.f, 0.f});
   hx_h8 hh[4], hl[4];
-  hx_load_row(x, row, g, ln_w, ln_b, eps, hh, hl);
+  unsigned khi = 0u, klo = ~0u;
+  hx_load_row<GUARD>(x, row, g, ln_w, ln_b, eps, hh, hl, khi, klo);
   hx_h8 pre[VPT];
 #pragma unroll
   for (int q = 0; q < VPT; q++) sw[0][tid + NT * q] = wp[tid + NT * q];
@@ -376,7 +442,14 @@ __global__ __launch_bounds__(64 * NW) void k_attn_half_f16x3(const float* __rest
         for (int e = 0; e < 8; e++) {
           const float v = k0 < C ? my[jr][k0 + e] : 0.f;
           _Float16 a, b; hx_split(v, a, b); hh[s][e] = a; hl[s][e] = b;
+          if constexpr (GUARD) hx_track(v, khi, klo);
         }
+      }
+      if constexpr (GUARD) {
+        const bool bad = klo < HXG_BIAS;
+#pragma unroll
+        for (int s = 0; s < 4; s++) { hh[s] = hx_poison(hh[s], bad); hl[s] = hx_poison(hl[s], bad); }
+        hx_guard_count(live, khi, klo, counts);
       }
     }
 #pragma unroll

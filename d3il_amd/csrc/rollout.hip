@@ -1629,6 +1629,12 @@ int d3il_mlp_ln_gelu_residual_f32(const float* h, const float* ln_weight, const 
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
+// Range / NaN guard of the split-f16 kernels (csrc/policy_f16x3.h): the caller's device i64[4], read when one of the three entry points below launches.
+static long long* g_hx_guard_counts = nullptr;
+int d3il_f16x3_set_guard(long long* counts_device) {
+  g_hx_guard_counts = counts_device;
+  return D3IL_OK;
+}
 int d3il_mlp_ln_gelu_residual_f16x3(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* x, const void* w_packed, const float* b1, const float* b2,
                                     float* out, long rows, int C, int H, void* stream) {
   if ((ln_weight == nullptr) != (ln_bias == nullptr)) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: LayerNorm weight and bias come together");
@@ -1637,8 +1643,11 @@ int d3il_mlp_ln_gelu_residual_f16x3(const float* h, const float* ln_weight, cons
   if (rows < 0) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: negative row count");
   if (((uintptr_t)h | (uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)b2 | (uintptr_t)out) % 16 != 0) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: pointers must be 16-byte aligned");
   if (rows == 0) return D3IL_OK;
-  hipLaunchKernelGGL(k_mlp_gelu_residual_f16x3<HX_MLP_NW>, dim3((unsigned)((rows + 16 * HX_MLP_NW - 1) / (16 * HX_MLP_NW))), dim3(64 * HX_MLP_NW), 0, (hipStream_t)stream, h, x, (const hx_h8*)w_packed, b1, b2, out, rows,
-                     ln_weight, ln_bias, ln_eps);
+  const dim3 grid((unsigned)((rows + 16 * HX_MLP_NW - 1) / (16 * HX_MLP_NW))), block(64 * HX_MLP_NW);
+  if (long long* counts = g_hx_guard_counts)
+    hipLaunchKernelGGL((k_mlp_gelu_residual_f16x3<HX_MLP_NW, true>), grid, block, 0, (hipStream_t)stream, h, x, (const hx_h8*)w_packed, b1, b2, out, rows, ln_weight, ln_bias, ln_eps, counts);
+  else
+    hipLaunchKernelGGL((k_mlp_gelu_residual_f16x3<HX_MLP_NW, false>), grid, block, 0, (hipStream_t)stream, h, x, (const hx_h8*)w_packed, b1, b2, out, rows, ln_weight, ln_bias, ln_eps, (long long*)nullptr);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
@@ -1649,8 +1658,11 @@ int d3il_linear120_f16x3(const float* xin, const float* ln_weight, const float* 
   if (rows < 0 || N < 4 || N % 4 != 0 || N > 384) return fail(D3IL_EINVAL, "d3il_linear120_f16x3: needs rows >= 0 and N a multiple of 4 in 4 .. 384");
   if (((uintptr_t)xin | (uintptr_t)w_packed | (uintptr_t)bias | (uintptr_t)resid | (uintptr_t)out) % 16 != 0) return fail(D3IL_EINVAL, "d3il_linear120_f16x3: pointers must be 16-byte aligned");
   if (rows == 0) return D3IL_OK;
-  hipLaunchKernelGGL(k_linear120_f16x3<HX_LIN_NW>, dim3((unsigned)((rows + 16 * HX_LIN_NW - 1) / (16 * HX_LIN_NW))), dim3(64 * HX_LIN_NW), 0, (hipStream_t)stream, xin, (const hx_h8*)w_packed, bias, resid, out, rows, N,
-                     ln_weight, ln_bias, ln_eps);
+  const dim3 grid((unsigned)((rows + 16 * HX_LIN_NW - 1) / (16 * HX_LIN_NW))), block(64 * HX_LIN_NW);
+  if (long long* counts = g_hx_guard_counts)
+    hipLaunchKernelGGL((k_linear120_f16x3<HX_LIN_NW, true>), grid, block, 0, (hipStream_t)stream, xin, (const hx_h8*)w_packed, bias, resid, out, rows, N, ln_weight, ln_bias, ln_eps, counts);
+  else
+    hipLaunchKernelGGL((k_linear120_f16x3<HX_LIN_NW, false>), grid, block, 0, (hipStream_t)stream, xin, (const hx_h8*)w_packed, bias, resid, out, rows, N, ln_weight, ln_bias, ln_eps, (long long*)nullptr);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
@@ -1662,10 +1674,15 @@ int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln
   if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)b_qkv | (uintptr_t)b_proj | (uintptr_t)out | (uintptr_t)ln_weight | (uintptr_t)ln_bias) % 16 != 0) return fail(D3IL_EINVAL, "d3il_attn_half_f16x3: pointers must be 16-byte aligned");
   if (x == out) return fail(D3IL_EINVAL, "d3il_attn_half_f16x3: out must not alias x (the residual is read after other rows have been written)");
   if (n_seq == 0) return D3IL_OK;
-  if (T <= 11)
-    hipLaunchKernelGGL((k_attn_half_f16x3<8, 11>), dim3((unsigned)((n_seq + 7) / 8)), dim3(512), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps);
+  long long* const counts = g_hx_guard_counts;
+  if (T <= 11 && counts)
+    hipLaunchKernelGGL((k_attn_half_f16x3<8, 11, true>), dim3((unsigned)((n_seq + 7) / 8)), dim3(512), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
+  else if (T <= 11)
+    hipLaunchKernelGGL((k_attn_half_f16x3<8, 11, false>), dim3((unsigned)((n_seq + 7) / 8)), dim3(512), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
+  else if (counts)
+    hipLaunchKernelGGL((k_attn_half_f16x3<4, 16, true>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
   else
-    hipLaunchKernelGGL((k_attn_half_f16x3<4, 16>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps);
+    hipLaunchKernelGGL((k_attn_half_f16x3<4, 16, false>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -282,6 +282,86 @@ def pack_linear120_weights_f16x3(weight: torch.Tensor, out: torch.Tensor | None 
     return res
 
 
+def weights_out_of_range(w: torch.Tensor) -> torch.Tensor:
+    """Number of entries of ``w`` that split_f16 cannot carry: NaN, +-Inf or |w| > 65504 (they saturate silently) - a 0-d int64 tensor on ``w``'s device, no
+    synchronisation."""
+    w = w.detach().to(torch.float32)
+    return (~torch.isfinite(w) | (w.abs() > 65504.0)).sum()
+
+
+# ------------------------------------------------------------------------------------------------ range / NaN guard of the split-f16 kernels
+_RANGE_GUARD = None          # the guard whose counters the library currently writes (d3il_f16x3_set_guard), or None
+_GUARD_EPOCH = 0             # bumped by every enable / disable: a graph captured under another epoch launches the wrong instantiation and is captured again
+_ENV_GUARD_TRIED = False
+
+
+class RangeGuard:
+    """Owner of the device int64[4] the guarded split-f16 kernels count into (include/d3il_rollout.h d3il_f16x3_set_guard): rows with an operand beyond +-65504
+    (``clipped``; they saturate as without the guard), rows with a NaN / Inf operand (``nonfinite``; they come out NaN instead of finite) and ``launches``.
+    One guard is active per process (the module keeps it alive while the library holds its address); ``with RangeGuard(dev) as g: ...; g.read()``.  Counts are per launch: a NaN row is counted again by every kernel it passes."""
+
+    def __init__(self, device="cuda"):
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("RangeGuard counts inside the split-f16 HIP kernels: it needs a HIP device (got %s, device available: %s)" % (dev, torch.cuda.is_available()))
+        self.counts = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.enabled = False
+
+    def enable(self):
+        global _RANGE_GUARD, _GUARD_EPOCH
+        from . import capi
+        if _RANGE_GUARD is not None and _RANGE_GUARD is not self:
+            _RANGE_GUARD.enabled = False
+        capi.check(capi.load().d3il_f16x3_set_guard(self.counts.data_ptr()))
+        _RANGE_GUARD, self.enabled = self, True
+        _GUARD_EPOCH += 1
+        return self
+
+    def disable(self):
+        global _RANGE_GUARD, _GUARD_EPOCH
+        if _RANGE_GUARD is self:
+            from . import capi
+            torch.cuda.synchronize(self.counts.device)      # launches in flight still write the counters
+            capi.check(capi.load().d3il_f16x3_set_guard(None))
+            _RANGE_GUARD = None
+            _GUARD_EPOCH += 1
+        self.enabled = False
+
+    def reset(self):
+        self.counts.zero_()
+
+    def read(self) -> dict:
+        torch.cuda.synchronize(self.counts.device)      # every stream of the device: sub-batches launch the policy kernels on streams of their own
+        c = self.counts.tolist()
+        return {"clipped": c[0], "nonfinite": c[1], "launches": c[2]}
+
+    def __enter__(self):
+        return self.enable()
+
+    def __exit__(self, *exc):
+        self.disable()
+        return False
+
+
+def range_guard():
+    """The process's active RangeGuard, or None."""
+    return _RANGE_GUARD
+
+
+def guard_epoch() -> int:
+    return _GUARD_EPOCH
+
+
+def _env_range_guard(device):
+    """D3IL_POLICY_RANGE_GUARD=1: create and enable a guard at the first f16x3 call of the process (outside a graph capture)."""
+    global _ENV_GUARD_TRIED
+    if _ENV_GUARD_TRIED or torch.cuda.is_current_stream_capturing():
+        return
+    _ENV_GUARD_TRIED = True
+    if os.environ.get("D3IL_POLICY_RANGE_GUARD", "0") == "1" and _RANGE_GUARD is None:
+        RangeGuard(device).enable()
+
+
 def policy_gemm_mode() -> str:
     """Which matrix-core path the DiffusionGPT blocks take: "f16x3" (default: split-f16 products, csrc/policy_f16x3.h) or "f32" (D3IL_POLICY_GEMM=f32: the f32-input MFMA
     kernels of rounds 3 - 5)."""
@@ -324,6 +404,7 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
             self._wp_proj = torch.empty(linear120_pack_index(120, dev).numel(), dtype=torch.float32, device=dev)
             self._wp_mlp = torch.empty(mlp_pack_index(120, 480, dev).numel(), dtype=torch.float32, device=dev)
             self._b_qkv = torch.empty(360, dtype=torch.float32, device=dev)
+            self._w_oor = torch.zeros((), dtype=torch.int64, device=dev)
         z = fc1.weight.new_zeros(1)
         with torch.no_grad():
             torch.index_select(torch.cat((a.query.weight.reshape(-1), a.key.weight.reshape(-1), a.value.weight.reshape(-1), z)), 0, linear120_pack_index(360, dev), out=self._wp_qkv)
@@ -339,6 +420,8 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
             if getattr(self, "_hp_attn", None) is None or self._hp_attn.device != dev:
                 self._hp_attn = torch.empty(self._hp_qkv.shape[0] + self._hp_proj.shape[0], 512, 8, dtype=self._hp_qkv.dtype, device=dev)
             torch.cat((self._hp_qkv, self._hp_proj), dim=0, out=self._hp_attn)
+            # entries of the f16x3-packed matrices that the split cannot carry (device scalar, no synchronisation; BESOPolicy.range_report)
+            self._w_oor.copy_(weights_out_of_range(wq) + weights_out_of_range(a.proj.weight) + weights_out_of_range(fc1.weight) + weights_out_of_range(fc2.weight))
         self._pack_key = key
 
     def forward(self, x, keep=None):
@@ -359,6 +442,8 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
             else:
                 assert getattr(self, "_pack_key", None) is not None, "a captured graph replays the packed weight buffers: call ensure_packed() before capturing"
             f16x3 = policy_gemm_mode() == "f16x3"
+            if f16x3 and not _ENV_GUARD_TRIED:
+                _env_range_guard(x.device)
             linear = L.d3il_linear120_f16x3 if f16x3 else L.d3il_linear120_f32
             mlp = L.d3il_mlp_ln_gelu_residual_f16x3 if f16x3 else L.d3il_mlp_ln_gelu_residual_f32
             w_qkv, w_proj, w_mlp = (self._hp_qkv, self._hp_proj, self._hp_mlp) if f16x3 else (self._wp_qkv, self._wp_proj, self._wp_mlp)
@@ -619,7 +704,7 @@ class CapturedPolicy:
 
     def __init__(self, inner):
         self.inner = inner
-        self._g, self._g_in, self._g_out = None, None, None
+        self._g, self._g_in, self._g_out, self._g_epoch = None, None, None, -1
 
     def reset(self):
         if hasattr(self.inner, "reset"):
@@ -642,6 +727,9 @@ class CapturedPolicy:
     def predict_batch(self, obs):
         if not obs.is_cuda:
             return self.inner.predict_batch(obs)
+        if self._g is not None and self._g_epoch != _GUARD_EPOCH and getattr(self.inner, "f16x3_blocks", False):
+            self._g = None      # captured with another setting of the range guard (the graph holds the instantiation and the counter address of its capture);
+                                # policies without split-f16 kernels (BC, DDPM) keep their graph - a new capture would also spend their random draws
         if self._g is None or self._g_in.shape != obs.shape or self._g_in.dtype != obs.dtype:
             dev = obs.device
             self._g_in = obs.clone()
@@ -655,6 +743,7 @@ class CapturedPolicy:
             self._g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g):
                 self._g_out = self.inner.predict_batch(self._g_in)
+            self._g_epoch = _GUARD_EPOCH
         if hasattr(self.inner, "ensure_packed"):
             self.inner.ensure_packed()      # packed weight buffers of a fused policy follow the parameters (in place) - e.g. after the EMA swap of a rollout
         self._g_in.copy_(obs)
@@ -830,7 +919,7 @@ class BESOPolicy:
         # use_graph: capture the sampling loop for full windows ([N, W] sequences, ~1500 small kernels) in a HIP graph and replay it
         # (default noise only: the generator state is part of the capture)
         self.use_graph = bool(use_graph) and noise_fn is None
-        self._graph = None
+        self._graph, self._g_epoch = None, -1      # the captured sampling loop and the range-guard epoch (_GUARD_EPOCH) of its capture
         dev = scaler.x_mean.device
         self.device = dev
         self.n_steps, self.sigma_min, self.sigma_max, self.sigma_data = int(num_sampling_steps), float(sigma_min), float(sigma_max), float(sigma_data)
@@ -849,6 +938,27 @@ class BESOPolicy:
         with torch.no_grad():
             for p, s in zip(self.inner.parameters(), shadow_params):
                 p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
+
+    f16x3_blocks = True      # the DiffusionGPT blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)
+
+    def weights_out_of_range(self) -> int:
+        """Entries of the blocks' f16x3-packed weight matrices that are NaN / Inf or beyond +-65504 (they saturate on the host, policies.split_f16); one
+        synchronising read.  Blocks that have not been packed yet are packed first."""
+        tot = None
+        for blk in self.inner.blocks:
+            if blk._fused_static_ok():
+                blk.ensure_packed()
+                tot = blk._w_oor if tot is None else tot + blk._w_oor
+        return 0 if tot is None else int(tot)
+
+    def range_report(self) -> dict:
+        """The active RangeGuard's counters (clipped / nonfinite / launches) plus ``weights_out_of_range``."""
+        g = range_guard()
+        if g is None:
+            raise RuntimeError("range_report: no RangeGuard is enabled (policies.RangeGuard, D3IL_POLICY_RANGE_GUARD=1 or a Sim's policy_range_guard=True)")
+        rep = g.read()
+        rep["weights_out_of_range"] = self.weights_out_of_range()
+        return rep
 
     def reset(self):
         for h in (self.obs_hist, self.act_hist):
@@ -904,7 +1014,7 @@ class BESOPolicy:
         """``_sample`` for full windows; with ``use_graph`` one HIP-graph replay instead of the eager kernel sequence."""
         if not (self.use_graph and states.is_cuda and states.shape[1] == self.W):
             return self._sample(states, x)
-        if self._graph is None or self._g_st.shape != states.shape:
+        if self._graph is None or self._g_st.shape != states.shape or self._g_epoch != _GUARD_EPOCH:      # (a graph keeps the range-guard setting of its capture)
             self._g_st, self._g_x = states.clone(), x.clone()
             side = torch.cuda.Stream(device=states.device)
             side.wait_stream(torch.cuda.current_stream(states.device))
@@ -915,6 +1025,7 @@ class BESOPolicy:
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
                 self._g_out = self._sample(self._g_st, self._g_x)
+            self._g_epoch = _GUARD_EPOCH
         self._g_st.copy_(states); self._g_x.copy_(x)
         self._graph.replay()
         return self._g_out
@@ -941,6 +1052,8 @@ class BESOPolicy:
         n, act_dim = s.shape[0], self.min_action.shape[0]
         if s.is_cuda and getattr(self, "_sig_dev", None) is None:
             self._sig_dev = torch.tensor(self.sigmas[:-1], dtype=torch.float32, device=s.device)      # (made here, outside a captured sampling loop)
+        if s.is_cuda and not _ENV_GUARD_TRIED and policy_gemm_mode() == "f16x3":
+            _env_range_guard(s.device)
         if s.is_cuda:                          # packed weight copies of the fused blocks: refreshed here, OUTSIDE a captured sampling loop (an EMA swap changes them)
             for blk in self.inner.blocks:
                 if blk._fused_static_ok():

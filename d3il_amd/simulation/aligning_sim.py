@@ -28,8 +28,10 @@ N_MODES = 2
 
 class Aligning_Sim(BaseSim):
     def __init__(self, seed: int, device: str, render: bool, n_cores: int = 1, n_contexts: int = 30, n_trajectories_per_context: int = 1,
-                 if_vision: bool = False, max_steps_per_episode: int = 400, contexts: np.ndarray | None = None, n_sub_batches: int = 1):
+                 if_vision: bool = False, max_steps_per_episode: int = 400, contexts: np.ndarray | None = None, n_sub_batches: int = 1,
+                 policy_range_guard: bool | None = None):
         super().__init__(seed, device, render, n_cores, if_vision)
+        self.policy_range_guard = policy_range_guard      # range / NaN guard of the split-f16 policy kernels (stacking_sim.py): report in last_rollout["policy_range"]
         # the reference's n_cores worker processes (aligning_sim.py:125-160) become sub-batches of the GPU batch on their own streams (envs/sub_batch.py)
         self.n_sub_batches = n_sub_batches
         if if_vision:
@@ -58,7 +60,7 @@ class Aligning_Sim(BaseSim):
         mode = torch.full((n,), -1, dtype=torch.int64, device=dev)
         success = torch.zeros(n, dtype=torch.bool, device=dev)
         mean_distance = torch.zeros(n, dtype=torch.float64, device=dev)
-        batches, env, flags = None, None, torch.zeros(0, dtype=torch.int32, device=dev)
+        batches, env, flags, policy_range = None, None, torch.zeros(0, dtype=torch.int32, device=dev), None
         if n > 0:      # a rank whose shard is empty only takes part in the reductions below
             ctx_np = self.contexts[ctx_of.cpu().numpy()]
 
@@ -71,7 +73,8 @@ class Aligning_Sim(BaseSim):
             batches.fork_agents(agent)
             # the rollout loop of aligning_sim.py:96-108 per sub-batch (simulation/_rollout.py)
             res = xyz_rollout(batches, self.max_steps_per_episode, {"mode": (torch.int64, -1), "success": (torch.bool, False), "mean_distance": (torch.float64, 0.0)},
-                              predict=self._predict)
+                              predict=self._predict, policy_range_guard=self.policy_range_guard)
+            policy_range = res["policy_range"]
             mode, success, mean_distance, flags = res["mode"], res["success"], res["mean_distance"], res["flags"]
             env = batches.batches[0].env
         # integer tables: mode counts of the successful rollouts per context, number of successes; f64 distance sum
@@ -87,7 +90,8 @@ class Aligning_Sim(BaseSim):
         c = counts.cpu().numpy()
         success_rate, entropy, mode_probs = pushing_metrics(c[:-1].reshape(self.n_contexts, N_MODES), int(c[-1]), total, self.n_trajectories_per_context, n_modes=N_MODES)
         self.last_rollout = dict(mode=mode, success=success, mean_distance=mean_distance, counts=c, shard=(lo, hi), success_rate=success_rate, entropy=entropy,
-                                 mode_probs=mode_probs, mean_distance_all=float(dist_sum.item()) / total, flags=flags, score=0.5 * (success_rate + entropy))
+                                 mode_probs=mode_probs, mean_distance_all=float(dist_sum.item()) / total, flags=flags, score=0.5 * (success_rate + entropy),
+                                 policy_range=policy_range)
         log.info("Successrate %s entropy %s mean distance %s", success_rate, entropy, float(dist_sum.item()) / total)
         if batches is not None:
             batches.close()

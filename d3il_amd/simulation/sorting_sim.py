@@ -51,8 +51,9 @@ def load_reference_data(contexts_pkl: str, mode_prob_pkl: str, num_box: int = 4)
 class Sorting_Sim(BaseSim):
     def __init__(self, seed: int, device: str, render: bool, n_cores: int = 1, n_contexts: int = 30, n_trajectories_per_context: int = 1,
                  num_box: int = 4, if_vision: bool = False, max_steps_per_episode: int = 500, contexts: np.ndarray | None = None,
-                 mode_prob: dict | None = None, n_sub_batches: int = 1):
+                 mode_prob: dict | None = None, n_sub_batches: int = 1, policy_range_guard: bool | None = None):
         super().__init__(seed, device, render, n_cores, if_vision)
+        self.policy_range_guard = policy_range_guard      # range / NaN guard of the split-f16 policy kernels (stacking_sim.py): report in last_rollout["policy_range"]
         # the reference's n_cores worker processes (sorting_sim.py:160-189) become sub-batches of the GPU batch on their own streams (envs/sub_batch.py)
         self.n_sub_batches = n_sub_batches
         if num_box not in (2, 4):
@@ -83,7 +84,7 @@ class Sorting_Sim(BaseSim):
         ctx_of = torch.arange(lo, hi, device=dev) // self.n_trajectories_per_context
         mode = torch.zeros(n, dtype=torch.int64, device=dev)
         success = torch.zeros(n, dtype=torch.bool, device=dev)
-        env, batches, flags = None, None, torch.zeros(0, dtype=torch.int32, device=dev)
+        env, batches, flags, policy_range = None, None, torch.zeros(0, dtype=torch.int32, device=dev), None
         if n > 0:      # a rank whose shard is empty (fewer rollouts than ranks) only takes part in the reductions below
             ctx_np = self.test_contexts[ctx_of.cpu().numpy()]
 
@@ -95,7 +96,9 @@ class Sorting_Sim(BaseSim):
             batches = SubBatchSet(n, self.n_sub_batches, dev, make_env)
             batches.fork_agents(agent)
             # the rollout loop of sorting_sim.py:118-133 per sub-batch (simulation/_rollout.py)
-            res = xy_rollout(batches, self.max_steps_per_episode, {"mode": (torch.int64, 0), "success": (torch.bool, False)}, predict=self._predict)
+            res = xy_rollout(batches, self.max_steps_per_episode, {"mode": (torch.int64, 0), "success": (torch.bool, False)}, predict=self._predict,
+                             policy_range_guard=self.policy_range_guard)
+            policy_range = res["policy_range"]
             mode, success, flags = res["mode"], res["success"], res["flags"]
             env = batches.batches[0].env
         # integer table: per context, successful rollouts whose mode code is the k-th key of the prior; number of successes
@@ -116,7 +119,7 @@ class Sorting_Sim(BaseSim):
         c = counts.cpu().numpy()
         success_rate, entropy, kl, score = sorting_metrics(c[:-1].reshape(self.n_contexts, self.n_mode), int(c[-1]), total, self.n_trajectories_per_context,
                                                            self.mode_encoding.numpy())
-        self.last_rollout = dict(mode=mode, success=success, counts=c, mode_hist=mode_hist.cpu().numpy(), shard=(lo, hi), flags=flags)
+        self.last_rollout = dict(mode=mode, success=success, counts=c, mode_hist=mode_hist.cpu().numpy(), shard=(lo, hi), flags=flags, policy_range=policy_range)
         log.info("Successrate %s entropy %s KL %s link-near rollouts %d", success_rate, entropy, kl, self.link_near_episodes)
         if batches is not None:
             batches.close()

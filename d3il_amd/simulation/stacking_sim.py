@@ -71,8 +71,12 @@ def _code_tables(dev):
 
 class Stacking_Sim(BaseSim):
     def __init__(self, seed: int, device: str, render: bool, n_cores: int = 1, n_contexts: int = 30, n_trajectories_per_context: int = 1,
-                 max_steps_per_episode: int = 500, contexts: np.ndarray | None = None, mode_prob: dict | None = None, n_sub_batches: int = 1):
+                 max_steps_per_episode: int = 500, contexts: np.ndarray | None = None, mode_prob: dict | None = None, n_sub_batches: int = 1,
+                 policy_range_guard: bool | None = None):
         super().__init__(seed, device, render, n_cores)
+        # range / NaN guard of the split-f16 policy kernels around the rollout (policies.RangeGuard): True / False, None = follow D3IL_POLICY_RANGE_GUARD;
+        # its report (per rank) is last_rollout["policy_range"]
+        self.policy_range_guard = policy_range_guard
         # the reference's n_cores worker processes (stacking_sim.py:182-216) become sub-batches of the GPU batch on their own streams (envs/sub_batch.py)
         self.n_sub_batches = n_sub_batches
         self.n_contexts, self.n_trajectories_per_context = n_contexts, n_trajectories_per_context
@@ -93,7 +97,7 @@ class Stacking_Sim(BaseSim):
         mode = torch.zeros(n, dtype=torch.int64, device=dev)
         success = torch.zeros(n, dtype=torch.bool, device=dev)
         mean_distance = torch.zeros(n, dtype=torch.float64, device=dev)
-        batches, env, flags = None, None, torch.zeros(0, dtype=torch.int32, device=dev)
+        batches, env, flags, policy_range = None, None, torch.zeros(0, dtype=torch.int32, device=dev), None
         if n > 0:      # a rank whose shard is empty only takes part in the reductions below
             ctx_np = self.test_contexts[ctx_of.cpu().numpy()]
 
@@ -105,7 +109,9 @@ class Stacking_Sim(BaseSim):
             batches = SubBatchSet(n, self.n_sub_batches, dev, make_env)
             batches.fork_agents(agent)
             # the rollout loop of stacking_sim.py:88-109 per sub-batch (simulation/_rollout.py)
-            res = joint_rollout(batches, self.max_steps_per_episode, {"mode": (torch.int64, 0), "success": (torch.bool, False), "mean_distance": (torch.float64, 0.0)})
+            res = joint_rollout(batches, self.max_steps_per_episode, {"mode": (torch.int64, 0), "success": (torch.bool, False), "mean_distance": (torch.float64, 0.0)},
+                                policy_range_guard=self.policy_range_guard)
+            policy_range = res["policy_range"]
             mode, success, mean_distance, flags = res["mode"], res["success"], res["mean_distance"], res["flags"]
             env = batches.batches[0].env
         # integer tables (stacking_sim.py:118-136, 143-151): per context, rollouts by the index of their 1- / 2- / 3-letter colour order
@@ -129,7 +135,8 @@ class Stacking_Sim(BaseSim):
         nc = self.n_contexts
         res = stacking_metrics(c[:3 * nc].reshape(nc, 3), c[3 * nc:9 * nc].reshape(nc, 6), c[9 * nc:15 * nc].reshape(nc, 6), int(c[-3]), int(c[-2]), int(c[-1]),
                                total, self.n_trajectories_per_context, self.mode_encoding_1, self.mode_encoding_2, self.mode_encoding_3)
-        self.last_rollout = dict(mode=mode, success=success, success_1=s1, success_2=s2, mean_distance=mean_distance, counts=c, shard=(lo, hi), flags=flags, metrics=res)
+        self.last_rollout = dict(mode=mode, success=success, success_1=s1, success_2=s2, mean_distance=mean_distance, counts=c, shard=(lo, hi), flags=flags, metrics=res,
+                                 policy_range=policy_range)
         log.info("Successrate %s (1 box %s, 2 boxes %s)", res["successes"], res["successes_1_box"], res["successes_2_boxes"])
         if batches is not None:
             batches.close()

@@ -198,7 +198,8 @@ int d3il_linear120_f32(const float* xin, const float* ln_weight, const float* ln
 /* The same two products on the f16 matrix cores with SPLIT operands (csrc/policy_f16x3.h): every f32 operand x = xh + 2^-11 xl as two f16 numbers (22 of the 24
  * significant bits), w x = wh xh + 2^-11 (wh xl + wl xh) in f32 accumulators - three v_mfma_f32_16x16x32_f16 per f32 product instead of sixteen f32-MFMA issue slots.
  * Agreement with an f64 reference is that of an f32 FMA chain (tests/test_policies_f16x3.py); operands saturate at +-65504.  w_packed: f16 halves in the kernels' tile
- * order (d3il_amd/policies.py pack_mlp_weights_f16x3: 16 stages of 2048 x 16 bytes; pack_linear120_weights_f16x3: an even number of tiles of 512 x 16 bytes). */
+ * order (d3il_amd/policies.py pack_mlp_weights_f16x3: 16 stages of 2048 x 16 bytes; pack_linear120_weights_f16x3: an even number of tiles of 512 x 16 bytes).
+ * The saturation is silent, and it is expected to turn a NaN / Inf operand into a finite number too (the clamp returns its bound), unless the range / NaN guard below is on. */
 int d3il_mlp_ln_gelu_residual_f16x3(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* x, const void* w_packed, const float* b1, const float* b2,
                                     float* out, long rows, int C, int H, void* stream);
 int d3il_linear120_f16x3(const float* xin, const float* ln_weight, const float* ln_bias, float ln_eps, const void* w_packed, const float* bias, const float* resid, float* out,
@@ -209,6 +210,21 @@ int d3il_linear120_f16x3(const float* xin, const float* ln_weight, const float* 
  * (policies.pack_linear120_weights_f16x3 of both, concatenated).  out must not alias x. */
 int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* w_packed, const float* b_qkv, const float* b_proj, float* out,
                          long n_seq, int T, int n_head, int C, void* stream);
+/* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
+ * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
+ * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
+ * d3il_mlp_ln_gelu_residual_f16x3 and d3il_attn_half_f16x3, which then launch the guarded instantiation of their kernel.  The call itself touches no device.
+ * Split sites: the input row after its LayerNorm (all three), the row's 480 GELU outputs (MLP), the row's 120 attention outputs (attention half).  At a site
+ *   a finite operand with |x| > 65504 saturates exactly as without the guard - the row's output is bit-identical - and the row is marked clipped;
+ *   a NaN / +-Inf operand goes to the matrix core as NaN: the row is NaN in every output column (as from the f32 entry points), no other row changes, and the row
+ *   is marked non-finite.
+ * Every launch adds to counts[D3IL_HXG_CLIPPED] / [D3IL_HXG_NONFINITE] the number of its rows (rows < `rows`; tokens < T of sequences < n_seq) with that mark - a row
+ * at most once per counter and launch, possibly in both - and 1 to counts[D3IL_HXG_LAUNCHES]; counts[3] is reserved and not touched.  The same row is counted again by
+ * every later launch it passes through non-finite (a NaN token travels down the blocks), so the counters tell WHETHER and roughly where, not how many operands.
+ * A captured graph keeps the pointer (and the instantiation) it was captured with: capture again after changing the guard.  The packed WEIGHTS are split on the
+ * host (policies.split_f16, saturating too); policies.BESOPolicy.range_report counts their out-of-range entries. */
+enum { D3IL_HXG_CLIPPED = 0, D3IL_HXG_NONFINITE = 1, D3IL_HXG_LAUNCHES = 2, D3IL_HXG_N = 4 };
+int d3il_f16x3_set_guard(long long* counts_device);
 
 /* The whole sampling chain of the reference's DDPM policy in one launch (agents/models/diffusion/gc_diffusion.py:101-216: epsilon prediction, clipped x0, posterior
  * mean, n_timesteps ancestral steps, final clamp; the denoiser = DiffusionMLPNetwork, diffusion_models.py:20-118 over ResidualMLPNetwork, common/mlp.py:114-182: Linear,
