@@ -25,6 +25,7 @@ constexpr int WAVE = 64;
 #include "link_guard.h"
 #include "stack_kernels.h"
 #include "policy_f16x3.h"
+#include "policy_bet.h"
 
 namespace d3il {
 
@@ -1683,6 +1684,26 @@ int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln
     hipLaunchKernelGGL((k_attn_half_f16x3<4, 16, true>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
   else
     hipLaunchKernelGGL((k_attn_half_f16x3<4, 16, false>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_bet_head_f32(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_head, const float* centers, const float* lo, const float* hi,
+                      const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* u_in, float* actions, int32_t* bins,
+                      float* u_out, float* probs, long rows, int C, int V, int A, void* stream) {
+  if (!h || !ln_weight || !ln_bias || !w_head || !centers || !lo || !hi || !scale || !shift || !t_device || !actions || !bins) return fail(D3IL_EINVAL, "d3il_bet_head_f32: null argument");
+  if (V != BET_V || C < 4 || C > BET_CMAX || C % 4 != 0 || A < 1 || A > BET_AMAX)
+    return fail(D3IL_EUNSUPPORTED, "d3il_bet_head_f32: built for 64 bins, n_embd <= 128 (a multiple of 4) and 1 .. 8 action components");
+  if (rows < 0) return fail(D3IL_EINVAL, "d3il_bet_head_f32: negative row count");
+  if (((uintptr_t)h | (uintptr_t)w_head) % 16 != 0) return fail(D3IL_EINVAL, "d3il_bet_head_f32: h and w_head must be 16-byte aligned");
+  if (rows == 0) return D3IL_OK;
+  BetHeadArgs a{h, ln_weight, ln_bias, w_head, centers, lo, hi, scale, shift, t_device, u_in, actions, bins, u_out, probs, (unsigned long long)seed, (unsigned long long)env_offset,
+                rows, ln_eps, C, A};
+  // eight rows per wave where the batch allows it (a wave loads its 64 x C logit weights once), at most one workgroup per CU
+  long blocks = (rows + 8 * BET_NW - 1) / (8 * BET_NW);
+  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks))), block(64 * BET_NW);
+  if (C <= 72) hipLaunchKernelGGL(k_bet_head<72>, grid, block, 0, (hipStream_t)stream, a);
+  else if (C <= 120) hipLaunchKernelGGL(k_bet_head<120>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_bet_head<128>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -147,6 +147,8 @@ class SubBatchSet:
             if hasattr(a, "set_rollout_range"):
                 a.set_rollout_range(b.offset, b.n)
             b.agent = as_batched(a, b.n)
+            if b.agent is not a and hasattr(b.agent, "set_rollout_range"):      # an adapter built from a reference agent (policies.BeTPolicy.from_reference)
+                b.agent.set_rollout_range(b.offset, b.n)
             b.agent.reset()
 
     @property

@@ -557,6 +557,19 @@ class _History:
         if self.lockstep >= 0:
             self.lockstep = min(self.lockstep + 1, self.w)
 
+    def append_(self, x):
+        """append() written INTO the buffers (no new tensors: a captured graph that holds their addresses keeps working on the live history)."""
+        self.buf[:, :-1] = self.buf[:, 1:].clone()
+        self.buf[:, -1] = x
+        self.len.add_(1).clamp_(max=self.w)
+        if self.lockstep >= 0:
+            self.lockstep = min(self.lockstep + 1, self.w)
+
+    def reset_(self, mask):
+        """reset(mask) in place."""
+        self.len.masked_fill_(mask.to(self.len.device).bool().reshape(-1), 0)
+        self.lockstep = -1
+
     def groups(self):
         """[(L, lane index tensor or None for all lanes)] - one entry when the lanes are in lock step."""
         if self.lockstep >= 0:
@@ -733,6 +746,9 @@ class CapturedPolicy:
         if self._g is None or self._g_in.shape != obs.shape or self._g_in.dtype != obs.dtype:
             dev = obs.device
             self._g_in = obs.clone()
+            # a policy with per-episode state on the device (BeTPolicy: history window, step word) hands it over here and gets it back after the capture: the two
+            # warm-up calls must not count as steps.  From the snapshot on it runs a fixed-shape chain that updates that state in place.
+            snap = self.inner.capture_snapshot(self._g_in) if hasattr(self.inner, "capture_snapshot") else None
             cur = torch.cuda.current_stream(dev)
             side = torch.cuda.Stream(dev)      # warm-up outside the capture: library workspaces and lazy initialisation must not happen inside it
             side.wait_stream(cur)
@@ -744,6 +760,8 @@ class CapturedPolicy:
             with torch.cuda.graph(self._g):
                 self._g_out = self.inner.predict_batch(self._g_in)
             self._g_epoch = _GUARD_EPOCH
+            if snap is not None:
+                self.inner.capture_restore(snap)
         if hasattr(self.inner, "ensure_packed"):
             self.inner.ensure_packed()      # packed weight buffers of a fused policy follow the parameters (in place) - e.g. after the EMA swap of a rollout
         self._g_in.copy_(obs)
@@ -1079,3 +1097,285 @@ class BESOPolicy:
             self.act_hist.len = (self.obs_hist.len - 1).clamp_min(0).clamp_max(self.W - 1)
             self.act_hist.lockstep = -1 if self.obs_hist.lockstep < 0 else min(max(self.obs_hist.lockstep - 1, 0), self.W - 1)
         return self.scaler.inverse_scale_output(x0_all)
+
+
+# ------------------------------------------------------------------------------------------------ Behaviour Transformer
+BET_TAG = 0x42655448          # fourth Philox counter word of the sampling head (csrc/policy_bet.h BET_TAG; the random-policy harness uses 0)
+
+
+def philox4x32_10(k0, k1, c0, c1, c2, c3):
+    """Philox4x32-10 on numpy arrays / ints (broadcast): the four output words as uint32 arrays - the host form of csrc/rollout.hip philox4x32_10."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    u = lambda v: np.asarray(v, dtype=np.uint64) & m32
+    k0, k1, c0, c1, c2, c3 = np.broadcast_arrays(u(k0), u(k1), u(c0), u(c1), u(c2), u(c3))
+    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + W0) & m32, (k1 + W1) & m32
+    return tuple(x.astype(np.uint32) for x in (c0, c1, c2, c3))
+
+
+def bet_uniforms(seed: int, env_offset: int, n: int, t: int):
+    """The head kernel's uniforms of rows 0 .. n-1 at step word t, on the host: 24 bits of Philox4x32-10(key = seed, counter = (env_offset + row, t, BET_TAG)),
+    float32 in [0, 1 - 2^-24]."""
+    import numpy as np
+    ge = np.uint64(env_offset) + np.arange(n, dtype=np.uint64)
+    r0 = philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, BET_TAG)[0]
+    return ((r0 >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+
+
+class MinGPTTrunk(nn.Module):
+    """The GPT of the reference's BeT (agents/models/bet/libraries/mingpt/model.py:128-250; continuous input, eval mode) with the reference's parameter names -
+    ``tok_emb``, ``pos_emb``, ``blocks.N.(ln1 | attn.key / query / value / proj | ln2 | mlp.0 / mlp.2)``, ``ln_f``, ``head`` (no bias, V (1 + A) outputs) - so
+    ``load_state_dict`` of a reference state dict works.  The blocks are ``_Block``: 120-wide trunks on the device take the matrix-core kernels of the DiffusionGPT,
+    every other width runs the same blocks through torch, batched.  ``hidden`` stops BEFORE ``ln_f``: the final LayerNorm and the head belong to the sampling tail."""
+
+    def __init__(self, input_dim, n_embd, n_layer, n_head, block_size, vocab_size=64, action_dim=0):
+        super().__init__()
+        self.tok_emb = nn.Linear(input_dim, n_embd)
+        self.pos_emb = nn.Parameter(torch.zeros(1, block_size, n_embd))
+        self.blocks = nn.Sequential(*[_Block(n_embd, n_head, block_size) for _ in range(n_layer)])
+        self.ln_f = nn.LayerNorm(n_embd)
+        self.head = nn.Linear(n_embd, vocab_size * (1 + action_dim), bias=False)
+        self.block_size, self.n_embd, self.vocab_size, self.action_dim = block_size, n_embd, vocab_size, action_dim
+
+    def hidden(self, x, keep=None):
+        """x [N, T, input_dim] -> the last block's output [N, T, C], or [N, len(keep), C] for the token positions ``keep`` (attention sees every token; the last
+        block's projection and MLP run on the kept rows only)."""
+        t = x.shape[1]
+        assert t <= self.block_size, "Cannot forward, model block size is exhausted."
+        h = (self.tok_emb(x) + self.pos_emb[:, :t, :]).contiguous()
+        for blk in self.blocks[:-1]:
+            h = blk(h)
+        return self.blocks[-1](h, keep=keep)
+
+    def forward(self, x):
+        """The reference's GPT.forward without targets: [N, T, V (1 + A)]."""
+        return self.head(self.ln_f(self.hidden(x)))
+
+
+class BeTPolicy:
+    """BeT_Agent.predict (agents/bet_agent.py:328-384) on a batch: scaled observation window (deque maxlen W; the window GROWS at episode start - sequence length
+    1, 2, .. W with pos_emb[:L]), the minGPT trunk, and at every lane's last token the sampling tail - ln_f, the bias-free head of V (1 + A) outputs, softmax over the
+    first V, ONE categorical draw, the offsets of the drawn bin in the layout "(V A)" (latent_generators/mingpt.py:155-186), bin_centers[bin] + offset (k_means.py:111-138),
+    clamp to the data bounds IN SCALED SPACE, inverse scaling.
+
+    The draw is the inverse CDF of the un-normalised softmax, bin = min(#{v : c_v <= u S}, V - 1) with c the inclusive prefix sums of p = exp(logit - max) and S = c_{V-1},
+    on ONE uniform u per lane and step: 24 bits of Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word, BET_TAG) - independent of batch order,
+    sub-batches and rank count, unlike torch.multinomial's device generator - or ``uniform_fn(n) -> [n]`` when given (golden replay, tests).  The step word lives on
+    the device and is advanced by a device-side add after every call, so a captured graph (CapturedPolicy) draws fresh numbers at every replay.
+
+    Deliberately dropped: the reference draws bins for the L - 1 EARLIER positions of the window too (generate_latents samples every row of [batch seq]) and throws
+    them away (bet_agent.py:364); that consumes its generator and nothing else.
+
+    On a HIP device the tail is one kernel (csrc/policy_bet.h through d3il_bet_head_f32; V = 64, C <= 128, A <= 8); on the CPU, for other shapes and with
+    D3IL_POLICY_BET_HEAD=0 the same arithmetic as torch ops (``_tail_torch``).  Lanes with different history lengths (after ``begin_episodes(mask)``) run in one
+    right-padded batch and each lane reads the trunk at its own last valid position - causal attention never looks at the padding behind it."""
+
+    def __init__(self, trunk: MinGPTTrunk, bin_centers, scaler: Scaler, min_action, max_action, window_size: int, seed: int = 0, uniform_fn=None):
+        self.trunk, self.scaler, self.W = trunk.eval(), scaler, int(window_size)
+        dev = scaler.x_mean.device
+        self.device = dev
+        f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
+        self.centers = f(bin_centers)
+        self.V, self.A = int(self.centers.shape[0]), int(self.centers.shape[1])
+        assert trunk.head.weight.shape[0] == self.V * (1 + self.A), "the head has V (1 + A) outputs"
+        self.min_action, self.max_action = f(min_action), f(max_action)
+        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self.seed, self.env_offset, self.uniform_fn = int(seed), 0, uniform_fn
+        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self.hist = None
+        self._static = False          # fixed-shape chain with device-only state (set by capture_snapshot)
+        self.record = False           # also keep the head's probabilities (last_probs) / the torch tail's logits (last_logits)
+        self.last_bins = self.last_u = self.last_probs = self.last_logits = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, uniform_fn=None, device=None):
+        """From a live reference ``BeT_Agent`` (duck-typed): ``agent.model.model.model.state_dict()`` (the GPT), ``agent.action_ae.bin_centers``, ``agent.scaler``
+        (x_mean / x_std / y_mean / y_std), ``agent.min_action`` / ``max_action``, ``agent.window_size``."""
+        mingpt = agent.model.model
+        sd = mingpt.model.state_dict()
+        dev = torch.device(device) if device is not None else sd["tok_emb.weight"].device
+        n_embd, input_dim = sd["tok_emb.weight"].shape
+        n_layer = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        centers = torch.as_tensor(agent.action_ae.bin_centers)
+        V, A = centers.shape
+        n_head = int(getattr(mingpt, "n_head", 0) or mingpt.model.blocks[0].attn.n_head)
+        trunk = MinGPTTrunk(input_dim, n_embd, n_layer, n_head, sd["pos_emb"].shape[1], V, A)
+        trunk.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+        trunk = trunk.to(dev)
+        for p in trunk.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, getattr(sc, "y_bounds", None), device=dev)
+        return cls(trunk, centers, scaler, agent.min_action, agent.max_action, int(agent.window_size), seed=seed, uniform_fn=uniform_fn)
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Does ``agent`` look like the reference's BeT_Agent (what from_reference reads)?"""
+        try:
+            return (hasattr(agent.model.model.model, "state_dict") and hasattr(agent.action_ae, "bin_centers") and hasattr(agent, "scaler")
+                    and hasattr(agent, "min_action") and hasattr(agent, "max_action") and hasattr(agent, "window_size"))
+        except AttributeError:
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet
+    @property
+    def f16x3_blocks(self) -> bool:
+        """The trunk runs the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
+        return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.trunk.blocks)
+
+    def reset(self):
+        if self.hist is not None:
+            self.hist.reset()
+
+    def begin_episodes(self, mask):
+        if self.hist is not None:
+            self.hist.reset_(mask)
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+        if self.hist is not None and self.hist.buf.shape[0] != count:
+            self.hist = None
+
+    def fork(self):
+        """A clone for another sub-batch: trunk, head, centres and scaler shared; history, step word and capture mode its own."""
+        import copy
+        c = copy.copy(self)
+        c.hist, c._static = None, False
+        c._t = self._t.clone()
+        c.last_bins = c.last_u = c.last_probs = c.last_logits = None
+        return c
+
+    def ensure_packed(self):
+        for blk in self.trunk.blocks:
+            if blk._fused_static_ok():
+                blk.ensure_packed()
+
+    def load_reference_state_dict(self, sd):
+        """``GPT.state_dict()`` of the reference (bet_agent.py: agent.model.model.model)."""
+        self.trunk.load_state_dict(sd)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Before the warm-up calls of a capture: switch to the fixed-shape chain (right-padded windows, lengths on the device, in-place history) and return the
+        per-episode state, which capture_restore puts back - warm-up and capture do not count as steps."""
+        self._static = True
+        if self.hist is None or self.hist.buf.shape[0] != obs.shape[0]:
+            self.hist = _History(obs.shape[0], self.W, obs.shape[1], self.device)
+        return (self.hist.buf.clone(), self.hist.len.clone(), self.hist.lockstep, self._t.clone())
+
+    def capture_restore(self, snap):
+        buf, ln, lock, t = snap
+        self.hist.buf.copy_(buf); self.hist.len.copy_(ln); self._t.copy_(t)
+        self.hist.lockstep = lock
+
+    # ---- the sampling tail
+    def head_kernel_ok(self, h) -> bool:
+        C = h.shape[-1]
+        return (h.is_cuda and h.dtype == torch.float32 and self.V == 64 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 8 and self.trunk.head.weight.dtype == torch.float32
+                and os.environ.get("D3IL_POLICY_BET_HEAD", "1") == "1")
+
+    def _uniforms(self, n, dev):
+        if self.uniform_fn is not None:
+            return torch.as_tensor(self.uniform_fn(n), dtype=torch.float32).to(dev).reshape(n).contiguous()
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("BeTPolicy: the torch tail draws its Philox numbers on the host and cannot be captured; the head kernel draws on the device")
+        return torch.as_tensor(bet_uniforms(self.seed, self.env_offset, n, int(self._t.item()) & 0xFFFFFFFF)).to(dev)
+
+    def _tail_torch(self, h):
+        """Steps 1 - 7 of csrc/policy_bet.h as torch ops, in the kernel's order of operations where the order is defined (S is the last prefix sum)."""
+        n, V, A = h.shape[0], self.V, self.A
+        w = self.trunk.head.weight
+        x = self.trunk.ln_f(h)
+        logits = F.linear(x, w[:V])
+        p = torch.exp(logits - logits.max(dim=1, keepdim=True).values)
+        c = torch.cumsum(p, dim=1)
+        S = c[:, -1:]
+        u = self._uniforms(n, h.device)
+        bins = (c <= u.unsqueeze(1) * S).sum(dim=1).clamp_max(V - 1)
+        rows = V + bins.unsqueeze(1) * A + torch.arange(A, device=h.device)
+        off = (w[rows] * x.unsqueeze(1)).sum(dim=2)
+        y = torch.clamp(self.centers[bins] + off, self.min_action, self.max_action) * self.out_scale + self.out_shift
+        bad = ~torch.isfinite(h).all(dim=1)
+        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        self.last_bins, self.last_u = torch.where(bad, torch.full_like(bins, -1), bins).to(torch.int32), u
+        if self.record:
+            self.last_logits, self.last_probs = logits, p / S
+        return y
+
+    def _tail_kernel(self, h):
+        from . import capi
+        n, C = h.shape
+        h = h.contiguous()
+        dev = h.device
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        bins = torch.empty(n, dtype=torch.int32, device=dev)
+        u_out = torch.empty(n, dtype=torch.float32, device=dev)
+        probs = torch.empty(n, self.V, dtype=torch.float32, device=dev) if self.record else None
+        u_in = self._uniforms(n, dev) if self.uniform_fn is not None else None
+        ln, w = self.trunk.ln_f, self.trunk.head.weight
+        assert w.is_contiguous() and self._t.device == dev
+        capi.check(capi.load().d3il_bet_head_f32(h.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w.data_ptr(), self.centers.data_ptr(),
+                                                 self.min_action.data_ptr(), self.max_action.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(),
+                                                 self.seed, self.env_offset, self._t.data_ptr(), None if u_in is None else u_in.data_ptr(), y.data_ptr(), bins.data_ptr(),
+                                                 u_out.data_ptr(), None if probs is None else probs.data_ptr(), n, C, self.V, self.A, torch.cuda.current_stream(dev).cuda_stream))
+        self.last_bins, self.last_u, self.last_probs, self.last_logits = bins, u_out, probs, None
+        return y
+
+    def tail(self, h):
+        """h [N, C] (the trunk's output at every lane's last token, before ln_f) -> actions [N, A]; advances the step word."""
+        y = self._tail_kernel(h) if self.head_kernel_ok(h) else self._tail_torch(h)
+        self._t.add_(1)
+        return y
+
+    def _last_hidden(self):
+        W, hist = self.W, self.hist
+        L = -1 if self._static else hist.lockstep      # (as BESOPolicy: no host look at the lengths once lanes have restarted)
+        if L >= 0:                              # all lanes have the same history length: the reference's shapes, only the last token leaves the last block
+            if getattr(self, "_keep", None) is None or self._keep.device != hist.buf.device:
+                self._keep = torch.arange(W, device=hist.buf.device)
+            return self.trunk.hidden(hist.buf[:, W - L:], keep=self._keep[L - 1:L])[:, 0]
+        n = hist.buf.shape[0]
+        j = torch.arange(W, device=hist.buf.device)
+        ln = hist.len
+        src = ((W - ln).unsqueeze(1) + j).clamp_max(W - 1)
+        st = torch.gather(hist.buf, 1, src.unsqueeze(2).expand(-1, -1, hist.buf.shape[2])) * (j < ln.unsqueeze(1)).unsqueeze(2)
+        out = self.trunk.hidden(st)
+        return out.gather(1, (ln - 1).view(n, 1, 1).expand(-1, 1, out.shape[2])).squeeze(1)
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32))
+        if s.is_cuda and not _ENV_GUARD_TRIED and self.f16x3_blocks:
+            _env_range_guard(s.device)
+        if s.is_cuda and not torch.cuda.is_current_stream_capturing():
+            self.ensure_packed()
+        if self.hist is None or self.hist.buf.shape[0] != s.shape[0]:
+            self.hist = _History(s.shape[0], self.W, s.shape[1], self.device)
+        self.hist.append_(s)
+        return self.tail(self._last_hidden().contiguous())
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, n_embd: int = 120, n_layer: int = 6, n_head: int = 6, window_size: int = 5,
+               action_scale: float = 0.002, uniform_fn=None, policy_seed: int = 0):
+        """A BeT policy of the reference's Stacking / Sorting-4 shape (n_layer 6, n_head 6, n_embd 120, window 5, 64 bins) with fixed random weights - there are no
+        checkpoints offline (as agents.RandomResidualMLPPolicy): torch's default layer initialisation, logit weights scaled to a standard deviation of ~2 (a
+        distribution that is neither uniform nor one-hot), unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-1.5."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            trunk = MinGPTTrunk(obs_dim, n_embd, n_layer, n_head, window_size, 64, action_dim)
+        with torch.no_grad():
+            trunk.pos_emb.copy_(torch.randn(trunk.pos_emb.shape, generator=g) * 0.1)
+            trunk.head.weight[:64] = torch.randn(64, n_embd, generator=g) * (2.0 / n_embd ** 0.5)
+            trunk.head.weight[64:] = torch.randn(64 * action_dim, n_embd, generator=g) * (0.4 / n_embd ** 0.5)
+        for p in trunk.parameters():
+            p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
+        return cls(trunk.to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, sc.y_bounds[0], sc.y_bounds[1], window_size, seed=policy_seed, uniform_fn=uniform_fn)

@@ -210,6 +210,17 @@ int d3il_linear120_f16x3(const float* xin, const float* ln_weight, const float* 
  * (policies.pack_linear120_weights_f16x3 of both, concatenated).  out must not alias x. */
 int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* w_packed, const float* b_qkv, const float* b_proj, float* out,
                          long n_seq, int T, int n_head, int C, void* stream);
+/* Sampling head of the batched Behaviour-Transformer policy (policies.BeTPolicy; bet_agent.py:359-372, latent_generators/mingpt.py:155-186, k_means.py:111-138) in one
+ * launch, f32 throughout.  Per row: x = LayerNorm(h); logit_v = w_head[v] . x (v < V); p = exp(logit - max), S = sum p, c = inclusive prefix sums; u = u_in[row] or
+ * 24 bits of Philox4x32-10 with key = seed and counter = (env_offset + row, *t_device, a tag word other than the 0 of the random-policy harness), so 0 <= u <= 1 - 2^-24;
+ * bin = min(#{v : c_v <= u S}, V - 1); off_a = w_head[V + bin A + a] . x; actions[row][a] = clamp(centers[bin][a] + off_a, lo_a, hi_a) scale_a + shift_a.
+ * h [rows][C] (the last block's output, before ln_f), w_head [V (1 + A)][C] row-major as in the reference's state dict, centers [V][A], lo / hi / scale / shift [A],
+ * t_device: DEVICE u32 read by the kernel (a captured graph draws fresh numbers when its owner advances the word between replays); u_in, u_out [rows], probs [rows][V]
+ * may be NULL; bins i32 [rows].  A row with a NaN / Inf in h gives bins = -1 and NaN in every action component.  Built for V = 64, C <= 128 (a multiple of 4),
+ * 1 <= A <= 8: D3IL_EUNSUPPORTED otherwise, answered before any launch.  h and w_head 16-byte aligned. */
+int d3il_bet_head_f32(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_head, const float* centers, const float* lo, const float* hi,
+                      const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* u_in, float* actions, int32_t* bins,
+                      float* u_out, float* probs, long rows, int C, int V, int A, void* stream);
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
