@@ -99,6 +99,10 @@ enum : unsigned {
   F_MODE_MASK = 0x1FFu, F_L1 = 1u << 9, F_L2 = 1u << 10, F_L3 = 1u << 11, F_TERMINATED = 1u << 12,
   F_SUCCESS = 1u << 13, F_ROD_CONTACT = 1u << 14, F_IK_VALID = 1u << 15, F_SOLVER_FAIL = 1u << 16,
   F_MULTI_CONTACT = 1u << 17,
+  // Never in memory: set by a split Avoiding step kernel in its physics wave, for the length of one launch, on a lane that is finished and not successful
+  // at step_begin while the SAME library call resets it afterwards.  Such a lane takes no rare constraint path.  Cleared before the
+  // flags are stored.
+  F_RETIRED = 1u << 31,
 };
 
 // number of f64 state fields per environment and their order in the SoA state buffer
@@ -1286,7 +1290,9 @@ D3IL_RARE void make_rod_contact(const C& c, const double* sn, const double* cs, 
 // exchange area to ANOTHER WAVE of the workgroup, which runs rare_serve() below and hands the constraint force back - the hot path then
 // carries none of the solvers' register pressure (192 spilled registers and 68 scratch operations per sub-step
 // in the physics wave's main block with the solvers inlined, none without them).
-struct RareInline { static constexpr bool remote = false; };
+// `retire == true`: a lane whose flags carry F_RETIRED takes neither rare path (only the split Avoiding kernels set the bit).
+struct RareInline { static constexpr bool remote = false, retire = false; };
+struct RareInlineRetire { static constexpr bool remote = false, retire = true; };
 constexpr int RX_M = 0, RX_FS = 45, RX_Q = 54, RX_V = 63, RX_SN = 72, RX_MD = 86, RX_BO = 87, RX_BD = 88, RX_BN = 89, RX_BP = 92, RX_FL = 95 /* fsign[2] fD[2] faref[2] */,
               RX_ARM = 101, RX_L = 102 /* LDL^T factors of M: L[45], 1 / d[9] */, RX_ID = 147, RX_ROWS = 156, RX_FC = 0 /* reply: fc[9], fail */;
 
@@ -1435,9 +1441,11 @@ template <class C, class R = RareInline> D3IL_HD void physics_substep(const C& c
   double fc[NDOF];
 #pragma unroll
   for (int k = 0; k < NDOF; k++) fc[k] = 0;
+  bool rare_need = bo >= 0 || arm_rows;
+  if constexpr (R::retire) rare_need = rare_need && !(st.flags & F_RETIRED);      // nothing a retired lane computes survives its launch: it asks for no solve
   bool delegated = false;
   if constexpr (R::remote) {
-    delegated = bo >= 0 || arm_rows;
+    delegated = rare_need;
     if (delegated) {
 #pragma unroll
       for (int i = 0; i < 45; i++) rare->put(RX_M + i, dyn.M[i]);
@@ -1463,7 +1471,7 @@ template <class C, class R = RareInline> D3IL_HD void physics_substep(const C& c
     }
   }
   if (delegated) {
-  } else if (!R::remote && (bo >= 0 || arm_rows)) {
+  } else if (!R::remote && rare_need) {
     if (!rare_constraints(c0, dyn.M, L, id, fs, st.q, st.v, dyn.sn, dyn.cs, bo, bd, bn, bp, fsign, fD, faref, arm_rows, fc, warm)) st.flags |= F_SOLVER_FAIL;
   } else if (fsign[0] != 0 || fsign[1] != 0) {
     // finger-limit rows only: exact active-set solution on the 2x2 block W = (M^-1)_FF

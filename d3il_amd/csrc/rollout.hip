@@ -202,7 +202,7 @@ __global__ __launch_bounds__(WAVE) void k_avoiding_step(const PandaConsts* __res
 // spilled 192 registers (68 scratch operations per sub-step in its main block) and a single environment in contact - about every second
 // launch at 4096 environments - stretched its workgroup, hence the launch, from 0.40 to 0.9 ms; both go away.
 struct RareXch {
-  static constexpr bool remote = true;
+  static constexpr bool remote = true, retire = true;
   double* buf;     // LDS [RX_ROWS][WAVE]
   int* ctl;        // LDS: [0] sequence number posted by the physics wave (sub-step + 1), [1] acknowledged by the serving wave, [2..3] lane mask
   int lane, seq;
@@ -343,6 +343,11 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
     load_state(state, flags, steps, stride, e, st);
     float o[2]; unsigned char dn;
     step_begin(c, st, o, &dn, max_steps);
+    // A lane that is finished and not successful here is reset later in this library call (the epilogue below; without a block, t_next != 0 says that
+    // d3il_step_auto_reset's reset kernels follow): whoever resets it reads its done / success only - mode counts for a successful lane - and
+    // overwrites everything else.  It rides through the sub-steps without a rare constraint solve (F_RETIRED, panda_step.h); it still reaches every barrier and
+    // every rx.post.  Decided once, from the state just loaded, and carried in the flags word, which is alive anyway.
+    st.flags = ((((unsigned long long)ep | t_next) != 0ull) && dn && !(st.flags & F_SUCCESS)) ? (st.flags | F_RETIRED) : (st.flags & ~F_RETIRED);      // (a bit 31 that d3il_set_state brought in retires nobody)
     double warm[6];
     warm[5] = 0.0;
 #pragma unroll
@@ -367,14 +372,14 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
 #pragma unroll
       for (int k = 0; k < 2 * NARM; k++) trig[k] = trg[1][k][lane];
       if constexpr (SERVE) { rx.seq = s + 1; control_and_physics(c, st, qd, qdd, 0.04, false, warm, trig, &rx); }
-      else control_and_physics(c, st, qd, qdd, 0.04, false, warm, trig);
+      else control_and_physics(c, st, qd, qdd, 0.04, false, warm, trig, (RareInlineRetire*)nullptr);
 #pragma unroll
       for (int k = 0; k < 2 * NARM; k++) trg[1][k][lane] = trig[k];
     }
 #if defined(D3IL_DEVICE_STATS)
     if (lane == 0 && blockIdx.x < 4096) { g_dev_wave[blockIdx.x][9] = wall_clock64() - t0 - tw; }
 #endif
-    st.flags |= F_IK_VALID;                     // set by the controller wave's first ik_update in the fused kernel
+    st.flags = (st.flags & ~F_RETIRED) | F_IK_VALID;      // F_IK_VALID: set by the controller wave's first ik_update in the fused kernel
     if (action_is_bad(actions + (size_t)e * 7)) st.flags |= F_SOLVER_FAIL | F_TERMINATED;
     step_end(c, st);
     if (live) {
@@ -1859,6 +1864,14 @@ int d3il_timing_stats(d3il_handle h, double* out4) {
   return D3IL_OK;
 }
 int d3il_step_auto_reset(d3il_handle h, const double* actions, int64_t* episode_counts_device, void* stream) {
+  // Avoiding, split kernels: the reset kernels of this same call overwrite every finished lane and read only done / success / the mode of a successful one,
+  // so the step kernel is told (t_next = 1 without an epilogue block) to retire the lanes that are finished and not successful at step_begin.  Whatever would
+  // make d3il_auto_reset refuse is checked BEFORE the step is enqueued: a retired lane must not be left in memory unreset.
+  if (h && h->task_id == D3IL_TASK_AVOIDING && split_step_kernel(h)) {
+    if (!episode_counts_device) return fail(D3IL_EINVAL, "d3il_step_auto_reset: the Avoiding task needs episode_counts (device i64[2])");
+    if (int rc = step_launch(h, actions, stream, nullptr, 1u)) return rc;
+    return d3il_auto_reset(h, episode_counts_device, stream);
+  }
   if (int rc = d3il_step(h, actions, stream)) return rc;
   return d3il_auto_reset(h, episode_counts_device, stream);
 }

@@ -305,7 +305,10 @@ int d3il_timing_stats(d3il_handle h, double* out4);
  * draw started.  With the one-wave step kernel (split_waves = 0, lanes_per_wave < 64) the same work runs as a second launch (k_avoiding_tail).
  * Cost of a change: the kernel reads seed, env_offset, `actions` and `episode_counts_device` from a small per-handle device block.  A call in which one of
  * them differs from the previous call rewrites the block and waits for the stream (for the whole device when the stream changed as well) before it launches:
- * once per sequence in a rollout loop, but a host synchronisation per step for a caller that alternates seed or buffers from step to step. */
+ * once per sequence in a rollout loop, but a host synchronisation per step for a caller that alternates seed or buffers from step to step.
+ * Avoiding, split step kernels: in both calls an environment that is finished and not successful when the step begins takes no rare constraint solve (rod
+ * contact, arm joint limits) during the step - the reset inside the same call overwrites all it would compute.  What the caller can read afterwards is bit for
+ * bit what d3il_step followed by d3il_auto_reset leaves. */
 int d3il_step_auto_reset(d3il_handle h, const double* actions, int64_t* episode_counts_device, void* stream);
 int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream);
 /* Option "graph_rollout": captures the graphs the next d3il_random_rollout_step calls with these arguments will launch, without launching anything (outside a timed region). */
