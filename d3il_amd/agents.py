@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import torch
 
+from .policies import FusedResMLPHook
+
 
 class BatchedBCAgent:
     """Wraps a reference ``BC_Agent`` (agents/bc_agent.py): attributes used are ``model``, ``scaler``
@@ -108,7 +110,7 @@ def as_batched(agent, n_envs: int | None = None):
     return RowwiseAgent(agent, n_envs)
 
 
-class RandomResidualMLPPolicy(torch.nn.Module):
+class RandomResidualMLPPolicy(FusedResMLPHook, torch.nn.Module):
     """Stand-in policy of BASELINE config 3: the architecture of the reference's BC policy for Pushing
     (agents/models/common/mlp.py:114-182 as configured by configs/agents/bc_agent.yaml:11-22 and
     configs/pushing_config.yaml: input 10 = desired xy + obs 8, hidden 128, 6 hidden layers = 3 pre-activation residual
@@ -143,26 +145,13 @@ class RandomResidualMLPPolicy(torch.nn.Module):
     def _parts(self):
         return (self.inp, [(b[0], b[1]) for b in self.blocks], self.out)
 
-    def ensure_packed(self):
-        if getattr(self, "_fused", None) is not None and self._fused._fw is not None:
-            self._fused.ensure_packed(self._parts())
-
-    def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the tensors' version counters): the next call repacks the device path's weights."""
-        if getattr(self, "_fused", None) is not None:
-            self._fused.invalidate()
-
     @torch.no_grad()
     def predict_batch(self, obs: torch.Tensor) -> torch.Tensor:
-        if obs.is_cuda and obs.dim() == 2:
-            if getattr(self, "_fused", None) is None:
-                from .policies import FusedResMLP
-                object.__setattr__(self, "_fused", FusedResMLP())
-            x32 = obs.to(torch.float32)
-            parts = self._parts()
-            if self._fused.ok(x32, parts):
-                return self._fused(x32, parts).clamp_(-self.bound, self.bound)      # one launch on the f32 matrix cores (policies.FusedResMLP)
-        x = self.inp(obs.to(torch.float32))
+        x = obs.to(torch.float32)
+        y = self._fused_forward(x)      # one launch on the f32 matrix cores (policies.FusedResMLP), with ensure_packed() / invalidate_packed() from the mixin
+        if y is not None:
+            return y.clamp_(-self.bound, self.bound)
+        x = self.inp(x)
         for l1, l2 in self.blocks:
             x = x + l2(self.act(l1(self.act(x))))
         return self.out(x).clamp_(-self.bound, self.bound)

@@ -53,7 +53,34 @@ class _ResBlock(nn.Module):          # TwoLayerPreActivationResNetLinear, agents
         return x + self.l2(F.mish(self.l1(F.mish(x))))
 
 
-class ResidualMLP(nn.Module):
+class FusedResMLPHook:
+    """Mixin of a module with ``_parts()`` = (lin_in, [(l1, l2), ..], lin_out): the lazily created device path (FusedResMLP, below) and its packed buffers."""
+
+    _fused = None      # a plain attribute (no buffer, no parameter): state_dict() does not see it
+
+    def ensure_packed(self):
+        """Refresh the packed weight buffers of the device path (in place) if a parameter has changed - what a captured graph's owner calls before a replay."""
+        if self._fused is not None and self._fused._fw is not None:
+            self._fused.ensure_packed(self._parts())
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        if self._fused is not None:
+            self._fused.invalidate()
+
+    def _fused_forward(self, x):
+        """The network on x [N, in] (f32) in one launch on the f32 matrix cores, or None where the device path does not apply (D3IL_POLICY_FUSED_RESMLP=0, the
+        CPU, other shapes, a caller that wants gradients): the caller then runs torch's layers."""
+        if x.dim() == 2 and x.is_cuda:
+            if self._fused is None:
+                self._fused = FusedResMLP()
+            parts = self._parts()
+            if self._fused.ok(x, parts):
+                return self._fused(x, parts)
+        return None
+
+
+class ResidualMLP(FusedResMLPHook, nn.Module):
     """ResidualMLPNetwork (agents/models/common/mlp.py:114-182), Mish: Linear, num_hidden_layers / 2 pre-activation residual blocks, Linear."""
 
     def __init__(self, input_dim, hidden_dim, num_hidden_layers, output_dim):
@@ -64,24 +91,11 @@ class ResidualMLP(nn.Module):
     def _parts(self):
         return (self.layers[0], [(b.l1, b.l2) for b in self.layers[1:-1]], self.layers[-1])
 
-    def ensure_packed(self):
-        """Refresh the packed weight buffers of the device path (in place) if a parameter has changed - what a captured graph's owner calls before a replay."""
-        if getattr(self, "_fused", None) is not None and self._fused._fw is not None:
-            self._fused.ensure_packed(self._parts())
-
-    def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
-        if getattr(self, "_fused", None) is not None:
-            self._fused.invalidate()
-
     def forward(self, x):
         x = x.to(torch.float32)
-        if x.dim() == 2 and x.is_cuda:
-            if getattr(self, "_fused", None) is None:
-                object.__setattr__(self, "_fused", FusedResMLP())
-            parts = self._parts()
-            if self._fused.ok(x, parts):
-                return self._fused(x, parts)      # one launch on the f32 matrix cores (D3IL_POLICY_FUSED_RESMLP=0: torch's layers)
+        y = self._fused_forward(x)
+        if y is not None:
+            return y
         for layer in self.layers:
             x = layer(x)
         return x
@@ -160,42 +174,49 @@ def _layer_norm(ln: nn.LayerNorm, x):
 _MLP_PACK_IDX = {}
 
 
+def _cached_index(build):
+    """Memoise an index builder ``build(*sizes, device)`` on (its name, the sizes, the device): the indices are built on the host once and kept on the device."""
+    def get(*args):
+        key = (build.__name__,) + args[:-1] + (str(args[-1]),)
+        if key not in _MLP_PACK_IDX:
+            _MLP_PACK_IDX[key] = build(*args)
+        return _MLP_PACK_IDX[key]
+    get.__name__, get.__doc__ = build.__name__, build.__doc__
+    return get
+
+
+@_cached_index
 def mlp_pack_index(C: int, H: int, device) -> torch.Tensor:
     """Gather index that puts the two weight matrices of a transformer MLP (fc1.weight [H, C], fc2.weight [C, H], flattened and concatenated, plus one
     trailing zero) into the per-chunk order d3il_mlp_gelu_residual_f32 copies to LDS: chunk c (16 hidden units) = 16 blocks of [4 g][16 i][4 e] floats (lane 16 g + i reads its float4 at [block][lane]);
     blocks q < 8: fc1.weight[16 c + i][4 (4 q + e) + g] (the A operand of step s = 4 q + e of the first product, zero for s >= C / 4); blocks 8 + t:
     fc2.weight[16 t + i][16 c + 4 g + e] (the A operand of step e of output tile t of the second product, zero for rows >= C)."""
-    key = (C, H, str(device))
-    if key not in _MLP_PACK_IDX:
-        c = torch.arange(H // 16).view(-1, 1, 1, 1, 1)
-        blk = torch.arange(8).view(1, -1, 1, 1, 1)
-        g = torch.arange(4).view(1, 1, -1, 1, 1)          # lane = 16 g + i: the float4 of a lane sits at [block][lane]
-        i = torch.arange(16).view(1, 1, 1, -1, 1)
-        e = torch.arange(4).view(1, 1, 1, 1, -1)
-        zero = C * H * 2
-        s = 4 * blk + e
-        i1 = torch.where(s < C // 4, (16 * c + i) * C + 4 * s + g, torch.full_like(s + c + i + g, zero))
-        row = 16 * blk + i
-        i2 = torch.where(row < C, C * H + row * H + 16 * c + 4 * g + e, torch.full_like(row + c + g + e, zero))
-        _MLP_PACK_IDX[key] = torch.cat((i1.expand(H // 16, 8, 4, 16, 4), i2.expand(H // 16, 8, 4, 16, 4)), dim=1).reshape(-1).to(device)
-    return _MLP_PACK_IDX[key]
+    c = torch.arange(H // 16).view(-1, 1, 1, 1, 1)
+    blk = torch.arange(8).view(1, -1, 1, 1, 1)
+    g = torch.arange(4).view(1, 1, -1, 1, 1)          # lane = 16 g + i: the float4 of a lane sits at [block][lane]
+    i = torch.arange(16).view(1, 1, 1, -1, 1)
+    e = torch.arange(4).view(1, 1, 1, 1, -1)
+    zero = C * H * 2
+    s = 4 * blk + e
+    i1 = torch.where(s < C // 4, (16 * c + i) * C + 4 * s + g, torch.full_like(s + c + i + g, zero))
+    row = 16 * blk + i
+    i2 = torch.where(row < C, C * H + row * H + 16 * c + 4 * g + e, torch.full_like(row + c + g + e, zero))
+    return torch.cat((i1.expand(H // 16, 8, 4, 16, 4), i2.expand(H // 16, 8, 4, 16, 4)), dim=1).reshape(-1).to(device)
 
 
+@_cached_index
 def linear120_pack_index(N: int, device) -> torch.Tensor:
     """Gather index for d3il_linear120_f32: weight [N, 120] (flattened, plus one trailing zero) -> ceil(N / 16) tiles of 8 blocks of [4 g][16 i][4 e] floats,
     block q of tile t: W[16 t + i][4 (4 q + e) + g] (zero beyond N rows / 30 steps)."""
-    key = ("lin", N, str(device))
-    if key not in _MLP_PACK_IDX:
-        nt = (N + 15) // 16
-        t = torch.arange(nt).view(-1, 1, 1, 1, 1)
-        q = torch.arange(8).view(1, -1, 1, 1, 1)
-        g = torch.arange(4).view(1, 1, -1, 1, 1)
-        i = torch.arange(16).view(1, 1, 1, -1, 1)
-        e = torch.arange(4).view(1, 1, 1, 1, -1)
-        s_, row = 4 * q + e, 16 * t + i
-        idx = torch.where((s_ < 30) & (row < N), row * 120 + 4 * s_ + g, torch.full_like(row + s_ + g, N * 120))
-        _MLP_PACK_IDX[key] = idx.reshape(-1).to(device)
-    return _MLP_PACK_IDX[key]
+    nt = (N + 15) // 16
+    t = torch.arange(nt).view(-1, 1, 1, 1, 1)
+    q = torch.arange(8).view(1, -1, 1, 1, 1)
+    g = torch.arange(4).view(1, 1, -1, 1, 1)
+    i = torch.arange(16).view(1, 1, 1, -1, 1)
+    e = torch.arange(4).view(1, 1, 1, 1, -1)
+    s_, row = 4 * q + e, 16 * t + i
+    idx = torch.where((s_ < 30) & (row < N), row * 120 + 4 * s_ + g, torch.full_like(row + s_ + g, N * 120))
+    return idx.reshape(-1).to(device)
 
 
 def pack_linear120_weights(weight: torch.Tensor) -> torch.Tensor:
@@ -217,32 +238,30 @@ def split_f16(w: torch.Tensor):
     return hi, lo
 
 
+@_cached_index
 def mlp_f16x3_pack_index(C: int, H: int, device) -> torch.Tensor:
     """Gather index [H / 32 pairs][2048 vectors][8] into cat(fc1.weight [H, C], fc2.weight [C, H], one zero) for d3il_mlp_ln_gelu_residual_f16x3 - WITHOUT the half
     dimension (the packer interleaves hi / lo): entry (c, v, e) with v < 512: tile = v // 256, s = (v // 64) % 4, lane = v % 64 -> fc1.weight[32 c + 16 tile + i][32 s + 8 g + e];
     v >= 512: t = (v - 512) // 64 -> fc2.weight[16 t + i][32 c + 16 (e >> 2) + 4 g + (e & 3)]; lane = 16 g + i; zero beyond the matrices."""
-    key = ("mlp16", C, H, str(device))
-    if key not in _MLP_PACK_IDX:
-        c = torch.arange(H // 32).view(-1, 1, 1, 1, 1, 1)
-        tile = torch.arange(2).view(1, -1, 1, 1, 1, 1)
-        s_ = torch.arange(4).view(1, 1, -1, 1, 1, 1)
-        g = torch.arange(4).view(1, 1, 1, -1, 1, 1)
-        i = torch.arange(16).view(1, 1, 1, 1, -1, 1)
-        e = torch.arange(8).view(1, 1, 1, 1, 1, -1)
-        zero = 2 * C * H
-        k = 32 * s_ + 8 * g + e
-        i1 = torch.where(k < C, (32 * c + 16 * tile + i) * C + k, torch.full_like(k + c + tile + i, zero))            # [P, 2, 4, 4, 16, 8]
-        t = torch.arange(8).view(1, -1, 1, 1, 1)
-        c2, g2, i2_, e2 = c.view(-1, 1, 1, 1, 1), g.view(1, 1, -1, 1, 1), i.view(1, 1, 1, -1, 1), e.view(1, 1, 1, 1, -1)
-        row = 16 * t + i2_
-        hid = 32 * c2 + 16 * (e2 >> 2) + 4 * g2 + (e2 & 3)
-        i2 = torch.where(row < C, C * H + row * H + hid, torch.full_like(row + hid, zero))                              # [P, 8, 4, 16, 8]
-        P = H // 32
-        _MLP_PACK_IDX[key] = (i1.reshape(P, 512, 8).to(device), i2.reshape(P, 512, 8).to(device))
-    return _MLP_PACK_IDX[key]
+    c = torch.arange(H // 32).view(-1, 1, 1, 1, 1, 1)
+    tile = torch.arange(2).view(1, -1, 1, 1, 1, 1)
+    s_ = torch.arange(4).view(1, 1, -1, 1, 1, 1)
+    g = torch.arange(4).view(1, 1, 1, -1, 1, 1)
+    i = torch.arange(16).view(1, 1, 1, 1, -1, 1)
+    e = torch.arange(8).view(1, 1, 1, 1, 1, -1)
+    zero = 2 * C * H
+    k = 32 * s_ + 8 * g + e
+    i1 = torch.where(k < C, (32 * c + 16 * tile + i) * C + k, torch.full_like(k + c + tile + i, zero))            # [P, 2, 4, 4, 16, 8]
+    t = torch.arange(8).view(1, -1, 1, 1, 1)
+    c2, g2, i2_, e2 = c.view(-1, 1, 1, 1, 1), g.view(1, 1, -1, 1, 1), i.view(1, 1, 1, -1, 1), e.view(1, 1, 1, 1, -1)
+    row = 16 * t + i2_
+    hid = 32 * c2 + 16 * (e2 >> 2) + 4 * g2 + (e2 & 3)
+    i2 = torch.where(row < C, C * H + row * H + hid, torch.full_like(row + hid, zero))                              # [P, 8, 4, 16, 8]
+    P = H // 32
+    return (i1.reshape(P, 512, 8).to(device), i2.reshape(P, 512, 8).to(device))
 
 
-def pack_mlp_weights_f16x3(fc1_weight: torch.Tensor, fc2_weight: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+def pack_mlp_weights_f16x3(fc1_weight: torch.Tensor, fc2_weight: torch.Tensor) -> torch.Tensor:
     """f16 [H / 32 + 1 stages][2048][8]: stage k = first-product vectors ((tile * 4 + s) * 2 + p) * 64 + lane of hidden pair k (zero for the last stage), then the
     second-product vectors 1024 + (t * 2 + p) * 64 + lane of pair k - 1 (zero for stage 0); p: 0 hi, 1 lo - the software pipeline of k_mlp_gelu_residual_f16x3."""
     H, C = fc1_weight.shape
@@ -253,33 +272,27 @@ def pack_mlp_weights_f16x3(fc1_weight: torch.Tensor, fc2_weight: torch.Tensor, o
     a = torch.stack((hi[i1].view(P, 8, 64, 8), lo[i1].view(P, 8, 64, 8)), dim=2).reshape(P, 1024, 8)      # [(tile, s)][p][lane]
     b = torch.stack((hi[i2].view(P, 8, 64, 8), lo[i2].view(P, 8, 64, 8)), dim=2).reshape(P, 1024, 8)      # [t][p][lane]
     z = torch.zeros_like(a[:1])
-    res = torch.cat((torch.cat((a, z), dim=0), torch.cat((z, b), dim=0)), dim=1).contiguous()      # [P + 1, 2048, 8]
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res
+    return torch.cat((torch.cat((a, z), dim=0), torch.cat((z, b), dim=0)), dim=1).contiguous()      # [P + 1, 2048, 8]
 
 
-def pack_linear120_weights_f16x3(weight: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+@_cached_index
+def linear120_f16x3_pack_index(N: int, C: int, device) -> torch.Tensor:
+    """Gather index [2 ceil(N / 32) tiles][4 s][64 lanes][8 e] into weight [N, C] (flattened, plus one trailing zero): W[16 t + i][32 s + 8 g + e], lane = 16 g + i."""
+    nt = 2 * ((N + 31) // 32)
+    t = torch.arange(nt).view(-1, 1, 1, 1, 1)
+    s_ = torch.arange(4).view(1, -1, 1, 1, 1)
+    g = torch.arange(4).view(1, 1, -1, 1, 1)
+    i = torch.arange(16).view(1, 1, 1, -1, 1)
+    e = torch.arange(8).view(1, 1, 1, 1, -1)
+    row, k = 16 * t + i, 32 * s_ + 8 * g + e
+    return torch.where((row < N) & (k < C), row * C + k, torch.full_like(row + k, N * C)).reshape(nt, 4, 64, 8).to(device)
+
+
+def pack_linear120_weights_f16x3(weight: torch.Tensor) -> torch.Tensor:
     """f16 [2 ceil(N / 32) tiles][512][8] for d3il_linear120_f16x3: vector (s * 2 + p) * 64 + lane of tile t = W_p[16 t + i][32 s + 8 g + e] (zero beyond N x 120)."""
-    N, C = weight.shape
-    key = ("lin16", N, C, str(weight.device))
-    if key not in _MLP_PACK_IDX:
-        nt = 2 * ((N + 31) // 32)
-        t = torch.arange(nt).view(-1, 1, 1, 1, 1)
-        s_ = torch.arange(4).view(1, -1, 1, 1, 1)
-        g = torch.arange(4).view(1, 1, -1, 1, 1)
-        i = torch.arange(16).view(1, 1, 1, -1, 1)
-        e = torch.arange(8).view(1, 1, 1, 1, -1)
-        row, k = 16 * t + i, 32 * s_ + 8 * g + e
-        _MLP_PACK_IDX[key] = torch.where((row < N) & (k < C), row * C + k, torch.full_like(row + k, N * C)).reshape(nt, 4, 64, 8).to(weight.device)
-    idx = _MLP_PACK_IDX[key]
+    idx = linear120_f16x3_pack_index(*weight.shape, weight.device)
     hi, lo = split_f16(torch.cat((weight.reshape(-1), weight.new_zeros(1))))
-    res = torch.stack((hi[idx], lo[idx]), dim=2).reshape(idx.shape[0], 512, 8).contiguous()
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res
+    return torch.stack((hi[idx], lo[idx]), dim=2).reshape(idx.shape[0], 512, 8).contiguous()
 
 
 def weights_out_of_range(w: torch.Tensor) -> torch.Tensor:
@@ -287,6 +300,49 @@ def weights_out_of_range(w: torch.Tensor) -> torch.Tensor:
     synchronisation."""
     w = w.detach().to(torch.float32)
     return (~torch.isfinite(w) | (w.abs() > 65504.0)).sum()
+
+
+class PackedWeights:
+    """Packed device copies of a module's weights that follow its parameters: ``buf`` is a dict of PERSISTENT buffers, refreshed in place whenever a parameter has
+    changed (tensor version counters: no device synchronisation).  The addresses never change while names, shapes, dtypes and devices stay, so a captured HIP graph
+    keeps reading the current weights as long as ``ensure`` runs before every replay - e.g. after the EMA swap of a rollout.  The parameters and the pack function
+    come with every call (no reference to the module is kept): a deep copy of the module gets its own buffers and packs ITS weights into them."""
+
+    def __init__(self):
+        self.buf, self.key = None, None
+
+    def invalidate(self):
+        """Force a repack at the next ensure().  Needed after writes that bypass the tensors' version counters - ``param.data.copy_(...)`` as the reference's EMA
+        helper does in copy_to / restore (agents/models/.../ema.py); ``use_ema()``, ``load_state_dict`` and in-place ops on the parameters are seen without it."""
+        self.key = None
+
+    def ensure(self, params, pack):
+        """``pack() -> {name: tensor or plain value}`` runs only when the (data_ptr, _version) key of ``params`` has changed."""
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if self.key == key:
+            return
+        with torch.no_grad():
+            new, old = pack(), self.buf
+        layout = lambda d: {k: (v.shape, v.dtype, v.device) if torch.is_tensor(v) else None for k, v in d.items()}
+        if old is not None and layout(old) == layout(new):
+            for k, v in new.items():
+                if torch.is_tensor(v):
+                    old[k].copy_(v)
+                else:
+                    old[k] = v
+        else:
+            # first pack, another layout or another device (the module has moved): new buffers, the cache's OWN (a pack function may hand back a view of a parameter,
+            # e.g. an f32 bias as it is: refreshing that in place would write the parameter and bump the very version counter the key is made of)
+            self.buf = {k: v.clone() if torch.is_tensor(v) else v for k, v in new.items()}
+        self.key = key
+
+    def current(self, params, pack):
+        """The buffers for a launch: refreshed here, except inside a graph capture, where packing kernels must not be recorded - they have to be packed already."""
+        if torch.cuda.is_current_stream_capturing():
+            assert self.key is not None, "a captured graph replays the packed weight buffers: call ensure_packed() before capturing"
+        else:
+            self.ensure(params, pack)
+        return self.buf
 
 
 # ------------------------------------------------------------------------------------------------ range / NaN guard of the split-f16 kernels
@@ -374,6 +430,7 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
         self.ln1, self.ln2 = nn.LayerNorm(n_embd), nn.LayerNorm(n_embd)
         self.attn = _CausalSelfAttention(n_embd, n_heads, block_size)
         self.mlp = nn.Sequential(nn.Linear(n_embd, 4 * n_embd), nn.GELU(), nn.Linear(4 * n_embd, n_embd), nn.Dropout(0.0))
+        self._packed = PackedWeights()      # a plain attribute: state_dict() keeps the reference's names
 
     def _fused_static_ok(self):
         return (self.mlp[0].weight.shape == (480, 120) and self.mlp[0].weight.is_cuda and self.mlp[0].weight.dtype == torch.float32 and 120 // self.attn.n_head <= 32
@@ -387,42 +444,29 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
 
     def invalidate_packed(self):
         """Force a repack at the next ensure_packed() (after ``param.data`` writes, which the version counters do not see)."""
-        self._pack_key = None
+        self._packed.invalidate()
+
+    def _pack_params(self):
+        a = self.attn
+        return (a.query.weight, a.key.weight, a.value.weight, a.query.bias, a.key.bias, a.value.bias, a.proj.weight, self.mlp[0].weight, self.mlp[2].weight)
+
+    def _pack(self):
+        """The block's weights in the tile order of the matrix-core kernels: ``wp_*`` for the f32-input kernels, ``hp_*`` the split-f16 forms of the same three
+        matrices (csrc/policy_f16x3.h)."""
+        a, fc1, fc2 = self.attn, self.mlp[0], self.mlp[2]
+        wq = torch.cat((a.query.weight, a.key.weight, a.value.weight), dim=0)
+        hp_qkv, hp_proj = pack_linear120_weights_f16x3(wq), pack_linear120_weights_f16x3(a.proj.weight)
+        return {"wp_qkv": pack_linear120_weights(wq), "wp_proj": pack_linear120_weights(a.proj.weight), "wp_mlp": pack_mlp_weights(fc1, fc2),
+                "b_qkv": torch.cat((a.query.bias, a.key.bias, a.value.bias), dim=0),
+                "hp_qkv": hp_qkv, "hp_proj": hp_proj, "hp_mlp": pack_mlp_weights_f16x3(fc1.weight, fc2.weight),
+                # (query | key | value) tiles followed by the projection's: the weight stream of the one-kernel attention half (d3il_attn_half_f16x3)
+                "hp_attn": torch.cat((hp_qkv, hp_proj), dim=0),
+                # entries of the f16x3-packed matrices that the split cannot carry (device scalar, no synchronisation; BESOPolicy.range_report)
+                "w_oor": weights_out_of_range(wq) + weights_out_of_range(a.proj.weight) + weights_out_of_range(fc1.weight) + weights_out_of_range(fc2.weight)}
 
     def ensure_packed(self):
-        """Packed copies of the block's weights in the tile order of the matrix-core kernels, in PERSISTENT device buffers refreshed in place whenever a
-        parameter has changed (tensor version counters: no device synchronisation).  The addresses never change, so a captured HIP graph keeps reading the
-        current weights as long as this runs before every replay (BESOPolicy.predict_batch does) - e.g. after the EMA swap of a rollout."""
-        a, fc1, fc2 = self.attn, self.mlp[0], self.mlp[2]
-        params = (a.query.weight, a.key.weight, a.value.weight, a.query.bias, a.key.bias, a.value.bias, a.proj.weight, fc1.weight, fc2.weight)
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if getattr(self, "_pack_key", None) == key:
-            return
-        dev = fc1.weight.device
-        if getattr(self, "_wp_qkv", None) is None or self._wp_qkv.device != dev:
-            self._wp_qkv = torch.empty(linear120_pack_index(360, dev).numel(), dtype=torch.float32, device=dev)
-            self._wp_proj = torch.empty(linear120_pack_index(120, dev).numel(), dtype=torch.float32, device=dev)
-            self._wp_mlp = torch.empty(mlp_pack_index(120, 480, dev).numel(), dtype=torch.float32, device=dev)
-            self._b_qkv = torch.empty(360, dtype=torch.float32, device=dev)
-            self._w_oor = torch.zeros((), dtype=torch.int64, device=dev)
-        z = fc1.weight.new_zeros(1)
-        with torch.no_grad():
-            torch.index_select(torch.cat((a.query.weight.reshape(-1), a.key.weight.reshape(-1), a.value.weight.reshape(-1), z)), 0, linear120_pack_index(360, dev), out=self._wp_qkv)
-            torch.index_select(torch.cat((a.proj.weight.reshape(-1), z)), 0, linear120_pack_index(120, dev), out=self._wp_proj)
-            torch.index_select(torch.cat((fc1.weight.reshape(-1), fc2.weight.reshape(-1), z)), 0, mlp_pack_index(120, 480, dev), out=self._wp_mlp)
-            torch.cat((a.query.bias, a.key.bias, a.value.bias), dim=0, out=self._b_qkv)
-            # the split-f16 forms of the same three matrices (csrc/policy_f16x3.h), refreshed in place like the f32 ones
-            wq = torch.cat((a.query.weight, a.key.weight, a.value.weight), dim=0)
-            self._hp_qkv = pack_linear120_weights_f16x3(wq, getattr(self, "_hp_qkv", None))
-            self._hp_proj = pack_linear120_weights_f16x3(a.proj.weight, getattr(self, "_hp_proj", None))
-            self._hp_mlp = pack_mlp_weights_f16x3(fc1.weight, fc2.weight, getattr(self, "_hp_mlp", None))
-            # (query | key | value) tiles followed by the projection's: the weight stream of the one-kernel attention half (d3il_attn_half_f16x3)
-            if getattr(self, "_hp_attn", None) is None or self._hp_attn.device != dev:
-                self._hp_attn = torch.empty(self._hp_qkv.shape[0] + self._hp_proj.shape[0], 512, 8, dtype=self._hp_qkv.dtype, device=dev)
-            torch.cat((self._hp_qkv, self._hp_proj), dim=0, out=self._hp_attn)
-            # entries of the f16x3-packed matrices that the split cannot carry (device scalar, no synchronisation; BESOPolicy.range_report)
-            self._w_oor.copy_(weights_out_of_range(wq) + weights_out_of_range(a.proj.weight) + weights_out_of_range(fc1.weight) + weights_out_of_range(fc2.weight))
-        self._pack_key = key
+        """Refresh the packed weights (PackedWeights: in place while the module stays on its device) - BESOPolicy.predict_batch does before every replay."""
+        self._packed.ensure(self._pack_params(), self._pack)
 
     def forward(self, x, keep=None):
         """keep: token positions (LongTensor) whose outputs are needed; the block then returns [B, len(keep), C] - attention still sees every token, the output
@@ -437,27 +481,24 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
             B, T, C = x.shape
             M = B * T
             a = self.attn
-            if not torch.cuda.is_current_stream_capturing():
-                self.ensure_packed()
-            else:
-                assert getattr(self, "_pack_key", None) is not None, "a captured graph replays the packed weight buffers: call ensure_packed() before capturing"
+            w = self._packed.current(self._pack_params(), self._pack)
             f16x3 = policy_gemm_mode() == "f16x3"
             if f16x3 and not _ENV_GUARD_TRIED:
                 _env_range_guard(x.device)
             linear = L.d3il_linear120_f16x3 if f16x3 else L.d3il_linear120_f32
             mlp = L.d3il_mlp_ln_gelu_residual_f16x3 if f16x3 else L.d3il_mlp_ln_gelu_residual_f32
-            w_qkv, w_proj, w_mlp = (self._hp_qkv, self._hp_proj, self._hp_mlp) if f16x3 else (self._wp_qkv, self._wp_proj, self._wp_mlp)
-            if f16x3 and T <= 16 and a.n_head == 6 and self._hp_attn.shape[0] == 32 and os.environ.get("D3IL_POLICY_FUSED_ATTN", "1") == "1":
+            w_qkv, w_proj, w_mlp = (w["hp_qkv"], w["hp_proj"], w["hp_mlp"]) if f16x3 else (w["wp_qkv"], w["wp_proj"], w["wp_mlp"])
+            if f16x3 and T <= 16 and a.n_head == 6 and w["hp_attn"].shape[0] == 32 and os.environ.get("D3IL_POLICY_FUSED_ATTN", "1") == "1":
                 # the attention half in ONE launch, one wave per sequence: q | k | v and the attention output never leave the CU (csrc/policy_f16x3.h k_attn_half_f16x3)
                 x1 = torch.empty_like(x)
-                capi.check(L.d3il_attn_half_f16x3(x.data_ptr(), self.ln1.weight.data_ptr(), self.ln1.bias.data_ptr(), float(self.ln1.eps), self._hp_attn.data_ptr(),
-                                                  self._b_qkv.data_ptr(), a.proj.bias.data_ptr(), x1.data_ptr(), B, T, a.n_head, C, st))
+                capi.check(L.d3il_attn_half_f16x3(x.data_ptr(), self.ln1.weight.data_ptr(), self.ln1.bias.data_ptr(), float(self.ln1.eps), w["hp_attn"].data_ptr(),
+                                                  w["b_qkv"].data_ptr(), a.proj.bias.data_ptr(), x1.data_ptr(), B, T, a.n_head, C, st))
                 if keep is not None:
                     x1 = x1.index_select(1, keep)
                     M = x1.shape[0] * x1.shape[1]
             else:
                 qkv = torch.empty(B, T, 3 * C, dtype=torch.float32, device=x.device)
-                capi.check(linear(x.data_ptr(), self.ln1.weight.data_ptr(), self.ln1.bias.data_ptr(), float(self.ln1.eps), w_qkv.data_ptr(), self._b_qkv.data_ptr(), None,
+                capi.check(linear(x.data_ptr(), self.ln1.weight.data_ptr(), self.ln1.bias.data_ptr(), float(self.ln1.eps), w_qkv.data_ptr(), w["b_qkv"].data_ptr(), None,
                                   qkv.data_ptr(), M, 3 * C, st))
                 y = torch.empty_like(x)
                 capi.check(L.d3il_attention_causal_f32(qkv.data_ptr(), y.data_ptr(), B, T, a.n_head, C // a.n_head, st))
@@ -475,6 +516,18 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
         if keep is not None:
             x = x.index_select(1, keep)
         return x + self.mlp(_layer_norm(self.ln2, x))
+
+
+for _name in ("wp_qkv", "wp_proj", "wp_mlp", "b_qkv", "hp_qkv", "hp_proj", "hp_mlp", "hp_attn", "w_oor"):      # the packed tensors under their earlier names, read-only
+    setattr(_Block, "_" + _name, property(lambda self, _name=_name: self._packed.buf[_name]))
+
+
+def ensure_blocks_packed(blocks) -> list:
+    """ensure_packed() of every block that can take the matrix-core kernels (OUTSIDE a captured chain: an EMA swap changes the packed copies); returns those blocks."""
+    fused = [blk for blk in blocks if blk._fused_static_ok()]
+    for blk in fused:
+        blk.ensure_packed()
+    return fused
 
 
 class DiffusionGPT(nn.Module):
@@ -570,6 +623,15 @@ class _History:
         self.len.masked_fill_(mask.to(self.len.device).bool().reshape(-1), 0)
         self.lockstep = -1
 
+    def padded(self):
+        """Lanes with different history lengths in ONE batch: (window [N, W, dim], lengths [N]) with every lane's entries left-aligned, oldest first, and zeros on
+        the right up to the window size.  A causal network whose position embedding counts from the first token never lets a lane's tokens see the padding behind
+        them; the newest entry of lane i sits at position len_i - 1."""
+        W, L = self.w, self.len
+        j = torch.arange(W, device=self.buf.device)
+        src = ((W - L).unsqueeze(1) + j).clamp_max(W - 1)
+        return torch.gather(self.buf, 1, src.unsqueeze(2).expand(-1, -1, self.buf.shape[2])) * (j < L.unsqueeze(1)).unsqueeze(2), L
+
     def groups(self):
         """[(L, lane index tensor or None for all lanes)] - one entry when the lanes are in lock step."""
         if self.lockstep >= 0:
@@ -603,8 +665,9 @@ class BCPolicy:
 
 
 def pack_resmlp_weights(lin_in, blocks, lin_out) -> dict:
-    """Linear, residual blocks [(l1, l2), ..], Linear of a ResidualMLPNetwork in the operand order of k_resmlp_f32 (the order of pack_ddpm_weights for any hidden
-    width that is a multiple of 16): [T_out][t][lane (g, i)][r] = W[16 T_out + i][16 t + 4 g + r]."""
+    """Linear, residual blocks [(l1, l2), ..], Linear of a ResidualMLPNetwork in the operand order of k_resmlp_f32 and k_ddpm_mlp_f32, for any hidden
+    width that is a multiple of 16: [T_out][t][lane (g, i)][r] = W[16 T_out + i][16 t + 4 g + r] for the square layers and the output layer (rows and bias padded
+    to 16 with zeros; k_ddpm_mlp_f32 reads two of them); the input layer, columns padded to 32: [T_out][lane (g, i)][s] = W[16 T_out + i][4 s + g]."""
     dev = lin_in.weight.device
     H = lin_in.out_features
     NT = H // 16
@@ -629,18 +692,16 @@ def pack_resmlp_weights(lin_in, blocks, lin_out) -> dict:
 
 
 class FusedResMLP:
-    """The device path of a ResidualMLPNetwork (csrc/rollout.hip k_resmlp_f32 through d3il_resmlp_f32): packed weights in persistent buffers, refreshed in place
-    when a parameter's version counter has changed (a captured graph keeps reading current weights).  Every call takes ``parts`` = (lin_in, [(l1, l2), ..],
-    lin_out) of the module it serves (no reference to the module is kept: a deep copy of the module gets its own buffers and packs ITS weights)."""
+    """The device path of a ResidualMLPNetwork (csrc/rollout.hip k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
+    ``parts`` = (lin_in, [(l1, l2), ..], lin_out) of the module it serves (no reference to the module is kept)."""
 
     def __init__(self):
-        self._fw, self._key = None, None
+        self._packed = PackedWeights()
+
+    _fw, _key = property(lambda self: self._packed.buf), property(lambda self: self._packed.key)      # read-only views of the cache
 
     def invalidate(self):
-        """Force a repack at the next ensure_packed().  Needed after writes that bypass the tensors' version counters - ``param.data.copy_(...)`` as the
-        reference's EMA helper does in copy_to / restore (agents/models/.../ema.py) - which the (data_ptr, _version) key cannot see; ``use_ema()``,
-        ``load_state_dict`` and in-place ops on the parameters themselves are detected without it."""
-        self._key = None
+        self._packed.invalidate()
 
     def ok(self, x, parts):
         lin_in, blocks, lin_out = parts
@@ -650,61 +711,47 @@ class FusedResMLP:
         return (x.is_cuda and x.dim() == 2 and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and lin_in.in_features <= 28
                 and lin_out.out_features <= 16 and os.environ.get("D3IL_POLICY_FUSED_RESMLP", "1") == "1")
 
-    def ensure_packed(self, parts):
+    @staticmethod
+    def _pack_args(parts):
+        """(the parameters the packed copy follows, the pack function) for PackedWeights."""
         lin_in, blocks, lin_out = parts
-        params = [lin_in.weight, lin_in.bias, lin_out.weight, lin_out.bias] + [p for b in blocks for l in b for p in (l.weight, l.bias)]
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._key == key:
-            return
-        with torch.no_grad():
-            fw = pack_resmlp_weights(lin_in, blocks, lin_out)
-            if self._fw is not None and all(not torch.is_tensor(v) or v.shape == self._fw[k].shape for k, v in fw.items()):
-                for k, v in fw.items():
-                    if torch.is_tensor(v):
-                        self._fw[k].copy_(v)
-            else:
-                self._fw = fw
-        self._key = key
+        return [lin_in.weight, lin_in.bias, lin_out.weight, lin_out.bias] + [p for b in blocks for l in b for p in (l.weight, l.bias)], lambda: pack_resmlp_weights(*parts)
+
+    def ensure_packed(self, parts):
+        self._packed.ensure(*self._pack_args(parts))
 
     def __call__(self, x, parts):
         from . import capi
         lib = capi.load()
         lin_in, blocks, lin_out = parts
-        if not torch.cuda.is_current_stream_capturing():
-            self.ensure_packed(parts)
-        else:
-            assert self._key is not None, "a captured graph replays the packed weight buffers: call ensure_packed() before capturing"
+        w = self._packed.current(*self._pack_args(parts))
         x = x.to(torch.float32).contiguous()
         out = torch.empty(x.shape[0], lin_out.out_features, dtype=torch.float32, device=x.device)
-        w = self._fw
         capi.check(lib.d3il_resmlp_f32(x.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_out"].data_ptr(), w["b_out"].data_ptr(),
                                        out.data_ptr(), x.shape[0], lin_in.in_features, lin_in.out_features, w["n_blocks"], lin_out.out_features, torch.cuda.current_stream(x.device).cuda_stream))
         return out
 
 
-def pack_ddpm_weights(model: "DiffusionMLP") -> dict:
-    """DiffusionMLP (hidden 256, action 2, t_dim 8) in the operand order of k_ddpm_mlp_f32: lane (g, i) = 16 g + i of a wave holds, for output tile T_out and
-    input group t, the four weights W[16 T_out + i][16 t + 4 g + r] (r = 0..3) - the D registers of one layer are the B operands of the next."""
-    L = model.layers.layers
-    lin_in, blocks, lin_out = L[0], list(L[1:-1]), L[-1]
-    dev = lin_in.weight.device
-    ar = lambda k: torch.arange(k, device=dev)
-    To, t, g, i, r = ar(16)[:, None, None, None, None], ar(16)[None, :, None, None, None], ar(4)[None, None, :, None, None], ar(16)[None, None, None, :, None], ar(4)[None, None, None, None, :]
-    pack = lambda W: W[16 * To + i, 16 * t + 4 * g + r].reshape(16, 16, 64, 4)
-    wi = torch.zeros(256, 32, device=dev)
-    wi[:, :lin_in.in_features] = lin_in.weight
-    s8 = ar(8)[None, None, None, :]
-    w_in = wi[16 * ar(16)[:, None, None, None] + ar(16)[None, None, :, None], 4 * s8 + ar(4)[None, :, None, None]].reshape(16, 64, 8)
-    wo = torch.zeros(16, 256, device=dev)
-    wo[:2] = lin_out.weight
-    w_out = wo[i[0], 16 * t[0] + 4 * g[0] + r[0]].reshape(16, 64, 4)
-    if blocks:
-        w_blk = torch.stack([pack(l.weight) for b in blocks for l in (b.l1, b.l2)])
-        b_blk = torch.stack([l.bias for b in blocks for l in (b.l1, b.l2)])
-    else:
-        w_blk, b_blk = torch.zeros(1, 16, 16, 64, 4, device=dev), torch.zeros(1, 256, device=dev)
-    f = lambda x: x.detach().to(torch.float32).contiguous()
-    return {"w_in": f(w_in), "b_in": f(lin_in.bias), "w_blk": f(w_blk), "b_blk": f(b_blk), "w_out": f(w_out), "b_out": f(lin_out.bias), "n_blocks": len(blocks)}
+def capture_graph(fn, device):
+    """``fn()`` - a fixed chain of device kernels on static inputs - as a captured HIP graph: two warm-up calls on a side stream (library handles, workspaces and
+    lazy initialisation must not happen inside the capture), then the capture.  Returns (graph, static output of fn, the range-guard epoch of the capture)."""
+    cur, side = torch.cuda.current_stream(device), torch.cuda.Stream(device)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            fn()
+    cur.wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = fn()
+    return graph, out, _GUARD_EPOCH
+
+
+def graph_is_stale(epoch, policy) -> bool:
+    """A graph holds the kernel instantiation and the counter address of the range-guard setting it was captured under: where split-f16 blocks are involved
+    (``policy.f16x3_blocks``) a graph of another _GUARD_EPOCH is dropped and captured again.  Policies without them (BC, DDPM) keep their graph - a new capture
+    would also spend their random draws."""
+    return epoch != _GUARD_EPOCH and bool(getattr(policy, "f16x3_blocks", False))
 
 
 class CapturedPolicy:
@@ -740,26 +787,14 @@ class CapturedPolicy:
     def predict_batch(self, obs):
         if not obs.is_cuda:
             return self.inner.predict_batch(obs)
-        if self._g is not None and self._g_epoch != _GUARD_EPOCH and getattr(self.inner, "f16x3_blocks", False):
-            self._g = None      # captured with another setting of the range guard (the graph holds the instantiation and the counter address of its capture);
-                                # policies without split-f16 kernels (BC, DDPM) keep their graph - a new capture would also spend their random draws
+        if self._g is not None and graph_is_stale(self._g_epoch, self.inner):
+            self._g = None
         if self._g is None or self._g_in.shape != obs.shape or self._g_in.dtype != obs.dtype:
-            dev = obs.device
             self._g_in = obs.clone()
             # a policy with per-episode state on the device (BeTPolicy: history window, step word) hands it over here and gets it back after the capture: the two
             # warm-up calls must not count as steps.  From the snapshot on it runs a fixed-shape chain that updates that state in place.
             snap = self.inner.capture_snapshot(self._g_in) if hasattr(self.inner, "capture_snapshot") else None
-            cur = torch.cuda.current_stream(dev)
-            side = torch.cuda.Stream(dev)      # warm-up outside the capture: library workspaces and lazy initialisation must not happen inside it
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.inner.predict_batch(self._g_in)
-            cur.wait_stream(side)
-            self._g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g):
-                self._g_out = self.inner.predict_batch(self._g_in)
-            self._g_epoch = _GUARD_EPOCH
+            self._g, self._g_out, self._g_epoch = capture_graph(lambda: self.inner.predict_batch(self._g_in), obs.device)
             if snap is not None:
                 self.inner.capture_restore(snap)
         if hasattr(self.inner, "ensure_packed"):
@@ -800,6 +835,7 @@ class DDPMPolicy:
         self.noise_fn = noise_fn or (lambda shape: torch.randn(shape, device=dev))
         self.hist = None
         self.n_envs = n_envs
+        self._packed = PackedWeights()
 
     # ---- the whole chain in one kernel of the rollout library (csrc/rollout.hip k_ddpm_mlp_f32)
     def fused_ok(self):
@@ -812,51 +848,38 @@ class DDPMPolicy:
     def invalidate_packed(self):
         """Force a repack at the next call.  Needed after writes through ``param.data`` (e.g. the reference EMA helper's copy_to / restore), which do not bump the
         version counters ensure_packed() keys on; use_ema() and load_state_dict are seen without it."""
-        self._pack_key = None
+        self._packed.invalidate()
         self.model.layers.invalidate_packed()
 
-    def ensure_packed(self):
-        """The denoiser's weights in the tile order of the kernel, the time embeddings of the T steps and the schedule table, in persistent device buffers
-        refreshed whenever a parameter has changed (tensor version counters) - e.g. after the EMA swap of a rollout."""
-        params = list(self.model.parameters())
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if getattr(self, "_pack_key", None) == key:
-            return
+    _fw = property(lambda self: self._packed.buf)      # the packed buffers, read-only
+
+    def _pack(self):
+        """The denoiser's weights in the tile order of the kernel, the time embeddings of the T steps, the schedule table and the action bounds."""
         self.model.layers.ensure_packed()      # (the torch chain's inner network, if its device path has been used)
-        L = self.model.layers.layers
-        dev = L[0].weight.device
-        with torch.no_grad():
-            fw = pack_ddpm_weights(self.model)
-            fw["temb"] = self.model.temp_layers(torch.arange(self.T, device=dev)).to(torch.float32).contiguous()
-            sig = (0.5 * self.post_logvar).exp() * torch.cat((torch.zeros(1, device=dev), torch.ones(self.T - 1, device=dev)))
-            fw["sched"] = torch.stack((self.sqrt_recip_ac, self.sqrt_recipm1_ac, self.coef1, self.coef2, sig), dim=1).to(torch.float32).contiguous()
-            fw["bounds"] = torch.cat((self.min_action.reshape(-1), self.max_action.reshape(-1))).to(torch.float32).contiguous()
-            old = getattr(self, "_fw", None)
-            if old is not None and all(torch.is_tensor(v) == torch.is_tensor(old.get(k)) and (not torch.is_tensor(v) or v.shape == old[k].shape) for k, v in fw.items()):
-                for k, v in fw.items():      # in place: the addresses never change, a captured graph keeps reading the current weights
-                    if torch.is_tensor(v):
-                        old[k].copy_(v)
-            else:
-                self._fw = fw
-        self._temb, self._sched, self._bounds = self._fw["temb"], self._fw["sched"], self._fw["bounds"]
-        self._pack_key = key
+        dev = self.model.layers.layers[0].weight.device
+        fw = pack_resmlp_weights(*self.model.layers._parts())
+        fw["temb"] = self.model.temp_layers(torch.arange(self.T, device=dev)).to(torch.float32).contiguous()
+        sig = (0.5 * self.post_logvar).exp() * torch.cat((torch.zeros(1, device=dev), torch.ones(self.T - 1, device=dev)))
+        fw["sched"] = torch.stack((self.sqrt_recip_ac, self.sqrt_recipm1_ac, self.coef1, self.coef2, sig), dim=1).to(torch.float32).contiguous()
+        fw["bounds"] = torch.cat((self.min_action.reshape(-1), self.max_action.reshape(-1))).to(torch.float32).contiguous()
+        return fw
+
+    def ensure_packed(self):
+        """The packed buffers of the fused chain (PackedWeights) follow the parameters - e.g. after the EMA swap of a rollout."""
+        self._packed.ensure(list(self.model.parameters()), self._pack)
 
     def _sample_fused(self, state):
         from . import capi
         lib = capi.load()
         n, sd = state.shape
-        if not torch.cuda.is_current_stream_capturing():
-            self.ensure_packed()
-        else:
-            assert getattr(self, "_pack_key", None) is not None, "a captured graph replays the packed weight buffers: call ensure_packed() before capturing"
+        w = self._packed.current(list(self.model.parameters()), self._pack)
         shape = (n, 2)
         noise = torch.stack([self.noise_fn(shape) for _ in range(self.T + 1)]).to(torch.float32).contiguous() if self._custom_noise else torch.randn((self.T + 1, n, 2), device=self.device)
         out = torch.empty(n, 2, dtype=torch.float32, device=self.device)
-        w = self._fw
         st = torch.cuda.current_stream(self.device).cuda_stream
         state = state.contiguous()
-        capi.check(lib.d3il_ddpm_mlp_f32(state.data_ptr(), noise.data_ptr(), self._temb.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(),
-                                         w["w_out"].data_ptr(), w["b_out"].data_ptr(), self._sched.data_ptr(), self._bounds.data_ptr(), out.data_ptr(), n, sd, self.T, 256, w["n_blocks"], st))
+        capi.check(lib.d3il_ddpm_mlp_f32(state.data_ptr(), noise.data_ptr(), w["temb"].data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(),
+                                         w["w_out"].data_ptr(), w["b_out"].data_ptr(), w["sched"].data_ptr(), w["bounds"].data_ptr(), out.data_ptr(), n, sd, self.T, 256, w["n_blocks"], st))
         return out
 
     def fork(self):
@@ -865,7 +888,7 @@ class DDPMPolicy:
         import copy
         c = copy.copy(self)
         c.hist = copy.deepcopy(self.hist)
-        c._fw, c._pack_key = None, None
+        c._packed = PackedWeights()
         return c
 
     def captured(self):
@@ -962,12 +985,7 @@ class BESOPolicy:
     def weights_out_of_range(self) -> int:
         """Entries of the blocks' f16x3-packed weight matrices that are NaN / Inf or beyond +-65504 (they saturate on the host, policies.split_f16); one
         synchronising read.  Blocks that have not been packed yet are packed first."""
-        tot = None
-        for blk in self.inner.blocks:
-            if blk._fused_static_ok():
-                blk.ensure_packed()
-                tot = blk._w_oor if tot is None else tot + blk._w_oor
-        return 0 if tot is None else int(tot)
+        return int(sum(blk._w_oor for blk in ensure_blocks_packed(self.inner.blocks)))
 
     def range_report(self) -> dict:
         """The active RangeGuard's counters (clipped / nonfinite / launches) plus ``weights_out_of_range``."""
@@ -1032,30 +1050,19 @@ class BESOPolicy:
         """``_sample`` for full windows; with ``use_graph`` one HIP-graph replay instead of the eager kernel sequence."""
         if not (self.use_graph and states.is_cuda and states.shape[1] == self.W):
             return self._sample(states, x)
-        if self._graph is None or self._g_st.shape != states.shape or self._g_epoch != _GUARD_EPOCH:      # (a graph keeps the range-guard setting of its capture)
+        if self._graph is None or self._g_st.shape != states.shape or graph_is_stale(self._g_epoch, self):
             self._g_st, self._g_x = states.clone(), x.clone()
-            side = torch.cuda.Stream(device=states.device)
-            side.wait_stream(torch.cuda.current_stream(states.device))
-            with torch.cuda.stream(side):                      # warm-up outside the capture (library handles, workspaces)
-                for _ in range(2):
-                    self._sample(self._g_st, self._g_x)
-            torch.cuda.current_stream(states.device).wait_stream(side)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._g_out = self._sample(self._g_st, self._g_x)
-            self._g_epoch = _GUARD_EPOCH
+            self._graph, self._g_out, self._g_epoch = capture_graph(lambda: self._sample(self._g_st, self._g_x), states.device)
         self._g_st.copy_(states); self._g_x.copy_(x)
         self._graph.replay()
         return self._g_out
 
     def _padded_inputs(self, noise):
-        """Lanes with different history lengths in ONE batch: the sequences are left-aligned and padded on the right to the window
-        size.  The transformer is causal and its position embedding counts from the first token, so the tokens of a lane never see
-        the padding behind them; the newest action of lane i sits at position len_i - 1."""
-        W, L = self.W, self.obs_hist.len
+        """The padded observation window (_History.padded) and, aligned with it, the action sequence: the previous actions of lane i at positions 0 .. len_i - 2,
+        the noise of its newest action at position len_i - 1."""
+        W = self.W
+        st, L = self.obs_hist.padded()
         j = torch.arange(W, device=self.device)
-        src = ((W - L).unsqueeze(1) + j).clamp_max(W - 1)
-        st = torch.gather(self.obs_hist.buf, 1, src.unsqueeze(2).expand(-1, -1, self.obs_hist.buf.shape[2])) * (j < L.unsqueeze(1)).unsqueeze(2)
         newest = (j == (L - 1).unsqueeze(1)).unsqueeze(2)
         x = newest * noise
         if self.act_hist is not None:
@@ -1072,10 +1079,8 @@ class BESOPolicy:
             self._sig_dev = torch.tensor(self.sigmas[:-1], dtype=torch.float32, device=s.device)      # (made here, outside a captured sampling loop)
         if s.is_cuda and not _ENV_GUARD_TRIED and policy_gemm_mode() == "f16x3":
             _env_range_guard(s.device)
-        if s.is_cuda:                          # packed weight copies of the fused blocks: refreshed here, OUTSIDE a captured sampling loop (an EMA swap changes them)
-            for blk in self.inner.blocks:
-                if blk._fused_static_ok():
-                    blk.ensure_packed()
+        if s.is_cuda:                          # packed weight copies of the fused blocks: refreshed here, OUTSIDE a captured sampling loop
+            ensure_blocks_packed(self.inner.blocks)
         if self.obs_hist is None:
             self.obs_hist = _History(n, self.W, s.shape[1], self.device)
             self.act_hist = _History(n, self.W - 1, act_dim, self.device) if self.W > 1 else None
@@ -1253,9 +1258,7 @@ class BeTPolicy:
         return c
 
     def ensure_packed(self):
-        for blk in self.trunk.blocks:
-            if blk._fused_static_ok():
-                blk.ensure_packed()
+        ensure_blocks_packed(self.trunk.blocks)
 
     def load_reference_state_dict(self, sd):
         """``GPT.state_dict()`` of the reference (bet_agent.py: agent.model.model.model)."""
@@ -1341,13 +1344,9 @@ class BeTPolicy:
             if getattr(self, "_keep", None) is None or self._keep.device != hist.buf.device:
                 self._keep = torch.arange(W, device=hist.buf.device)
             return self.trunk.hidden(hist.buf[:, W - L:], keep=self._keep[L - 1:L])[:, 0]
-        n = hist.buf.shape[0]
-        j = torch.arange(W, device=hist.buf.device)
-        ln = hist.len
-        src = ((W - ln).unsqueeze(1) + j).clamp_max(W - 1)
-        st = torch.gather(hist.buf, 1, src.unsqueeze(2).expand(-1, -1, hist.buf.shape[2])) * (j < ln.unsqueeze(1)).unsqueeze(2)
+        st, ln = hist.padded()
         out = self.trunk.hidden(st)
-        return out.gather(1, (ln - 1).view(n, 1, 1).expand(-1, 1, out.shape[2])).squeeze(1)
+        return out.gather(1, (ln - 1).view(-1, 1, 1).expand(-1, 1, out.shape[2])).squeeze(1)
 
     @torch.no_grad()
     def predict_batch(self, obs):
