@@ -26,6 +26,7 @@ constexpr int WAVE = 64;
 #include "stack_kernels.h"
 #include "policy_f16x3.h"
 #include "policy_bet.h"
+#include "policy_ddpm_gpt.h"
 
 namespace d3il {
 
@@ -1709,6 +1710,29 @@ int d3il_bet_head_f32(const float* h, const float* ln_weight, const float* ln_bi
   if (C <= 72) hipLaunchKernelGGL(k_bet_head<72>, grid, block, 0, (hipStream_t)stream, a);
   else if (C <= 120) hipLaunchKernelGGL(k_bet_head<120>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_bet_head<128>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_ddpm_gpt_step_f32(const float* hk, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_pred, const float* b_pred, const float* w_aemb,
+                           const float* bias_pos, const float* temb, const float* sched, const float* lo, const float* hi, const float* scale, const float* shift,
+                           const int64_t* len, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* noise_in, float* x, float* xbuf, float* actions,
+                           int32_t* bad, float* noise_out, long n_env, int C, int A, int W, int T, int k, void* stream) {
+  if (C < 4 || C > DG_CMAX || C % 4 != 0 || A < 1 || A > DG_AMAX || W < 1 || W > DG_WMAX || T < 1 || T > DG_TMAX)
+    return fail(D3IL_EUNSUPPORTED, "d3il_ddpm_gpt_step_f32: built for n_embd <= 128 (a multiple of 4), 1 .. 8 action components, a window of 1 .. 16 and 1 .. 255 timesteps");
+  if (!ln_weight || !ln_bias || !w_pred || !b_pred || !w_aemb || !bias_pos || !temb || !sched || !lo || !hi || !scale || !shift || !len || !t_device || !x || !xbuf || !actions || !bad)
+    return fail(D3IL_EINVAL, "d3il_ddpm_gpt_step_f32: null argument");
+  if (k < 0 || k > T) return fail(D3IL_EINVAL, "d3il_ddpm_gpt_step_f32: chain index outside 0 .. T");
+  if (k < T && !hk) return fail(D3IL_EINVAL, "d3il_ddpm_gpt_step_f32: a reverse step needs the hidden rows");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_ddpm_gpt_step_f32: negative environment count");
+  if (n_env == 0) return D3IL_OK;
+  DdpmGptArgs a{hk, ln_weight, ln_bias, w_pred, b_pred, w_aemb, bias_pos, temb, sched, lo, hi, scale, shift, (const long long*)len, t_device, noise_in, x, xbuf, actions, bad, noise_out,
+                (unsigned long long)seed, (unsigned long long)env_offset, n_env, ln_eps, C, A, W, T, k};
+  // two environments per wave where the batch allows it (a wave loads its 32 weight registers once), at most 1024 workgroups
+  long blocks = (n_env + 2 * DG_NW - 1) / (2 * DG_NW);
+  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks))), block(64 * DG_NW);
+  if (C == 72) hipLaunchKernelGGL(k_ddpm_gpt_step<72>, grid, block, 0, (hipStream_t)stream, a);
+  else if (C == 120) hipLaunchKernelGGL(k_ddpm_gpt_step<120>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_ddpm_gpt_step<128>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

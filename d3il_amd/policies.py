@@ -813,6 +813,21 @@ def cosine_beta_schedule(timesteps, s=0.008):     # agents/models/diffusion/util
     return torch.tensor(np.clip(1 - (ac[1:] / ac[:-1]), a_min=0, a_max=0.999), dtype=torch.float32)
 
 
+def ddpm_schedule(betas: torch.Tensor) -> dict:
+    """The tables the DDPM samplers derive from the betas (in the betas' dtype, on their device): sqrt(1 / ac), sqrt(1 / ac - 1), the clipped posterior log
+    variance, the two posterior-mean coefficients, and ``sched`` [T, 5] = (sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sig) with sig = exp(logvar / 2) and
+    sig[0] = 0 - what the fused sampler kernels read per step."""
+    alphas = 1.0 - betas
+    ac = torch.cumprod(alphas, dim=0)
+    ac_prev = torch.cat([torch.ones_like(betas[:1]), ac[:-1]])
+    post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
+    s = {"betas": betas, "alphas": alphas, "ac": ac, "ac_prev": ac_prev, "sqrt_recip_ac": torch.sqrt(1.0 / ac), "sqrt_recipm1_ac": torch.sqrt(1.0 / ac - 1), "post_var": post_var,
+         "post_logvar": torch.log(torch.clamp(post_var, min=1e-20)), "coef1": betas * torch.sqrt(ac_prev) / (1.0 - ac), "coef2": (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac)}
+    sig = (0.5 * s["post_logvar"]).exp() * torch.cat((torch.zeros_like(betas[:1]), torch.ones_like(betas[1:])))
+    s["sched"] = torch.stack((s["sqrt_recip_ac"], s["sqrt_recipm1_ac"], s["coef1"], s["coef2"], sig), dim=1).contiguous()
+    return s
+
+
 class DDPMPolicy:
     """DiffusionAgent.predict (ddpm_agent.py:213-274) with the Diffusion sampler (gc_diffusion.py:101-216: epsilon prediction, clipped
     x0, posterior mean / variance, n_timesteps ancestral steps, final clamp) on a batch.  ``noise_fn(shape)`` supplies the Gaussian
@@ -822,14 +837,8 @@ class DDPMPolicy:
         self.model, self.scaler, self.T, self.W = model.eval(), scaler, int(n_timesteps), int(window_size)
         dev = scaler.x_mean.device
         self.device = dev
-        betas = cosine_beta_schedule(self.T).to(dev)
-        alphas = 1.0 - betas
-        ac = torch.cumprod(alphas, dim=0)
-        ac_prev = torch.cat([torch.ones(1, device=dev), ac[:-1]])
-        self.sqrt_recip_ac, self.sqrt_recipm1_ac = torch.sqrt(1.0 / ac), torch.sqrt(1.0 / ac - 1)
-        post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
-        self.post_logvar = torch.log(torch.clamp(post_var, min=1e-20))
-        self.coef1, self.coef2 = betas * torch.sqrt(ac_prev) / (1.0 - ac), (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac)
+        sch = ddpm_schedule(cosine_beta_schedule(self.T).to(dev))
+        self.sqrt_recip_ac, self.sqrt_recipm1_ac, self.post_logvar, self.coef1, self.coef2, self._sched = (sch[k] for k in ("sqrt_recip_ac", "sqrt_recipm1_ac", "post_logvar", "coef1", "coef2", "sched"))
         self.min_action, self.max_action = scaler.y_bounds[0], scaler.y_bounds[1]
         self._custom_noise = noise_fn is not None
         self.noise_fn = noise_fn or (lambda shape: torch.randn(shape, device=dev))
@@ -859,8 +868,7 @@ class DDPMPolicy:
         dev = self.model.layers.layers[0].weight.device
         fw = pack_resmlp_weights(*self.model.layers._parts())
         fw["temb"] = self.model.temp_layers(torch.arange(self.T, device=dev)).to(torch.float32).contiguous()
-        sig = (0.5 * self.post_logvar).exp() * torch.cat((torch.zeros(1, device=dev), torch.ones(self.T - 1, device=dev)))
-        fw["sched"] = torch.stack((self.sqrt_recip_ac, self.sqrt_recipm1_ac, self.coef1, self.coef2, sig), dim=1).to(torch.float32).contiguous()
+        fw["sched"] = self._sched.to(device=dev, dtype=torch.float32).contiguous()
         fw["bounds"] = torch.cat((self.min_action.reshape(-1), self.max_action.reshape(-1))).to(torch.float32).contiguous()
         return fw
 
@@ -1378,3 +1386,352 @@ class BeTPolicy:
             p.requires_grad_(False)
         sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
         return cls(trunk.to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, sc.y_bounds[0], sc.y_bounds[1], window_size, seed=policy_seed, uniform_fn=uniform_fn)
+
+
+# ------------------------------------------------------------------------------------------------ DDPM with the transformer denoiser
+DDPM_GPT_TAG = 0x44470000     # fourth Philox counter word of the step kernel, or-ed with k << 8 | j << 1 | q (csrc/policy_ddpm_gpt.h; never 0, never BET_TAG)
+
+
+def ddpm_gpt_words(seed: int, env_offset: int, n: int, t: int, k: int, W: int):
+    """The Philox words behind ``ddpm_gpt_normals``: uint32 [n, W, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
+    DDPM_GPT_TAG | k << 8 | j << 1 | q))."""
+    import numpy as np
+    assert 1 <= k <= 255 and 1 <= W <= 16, "the counter layout holds k <= 255 and j <= 15; chain index 0 is never drawn"
+    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1, 1)
+    j = np.arange(W, dtype=np.uint64).reshape(1, W, 1)
+    q = np.arange(2, dtype=np.uint64).reshape(1, 1, 2)
+    tag = np.uint64(DDPM_GPT_TAG | (k << 8)) | (j << np.uint64(1)) | q
+    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+
+
+def ddpm_gpt_normals(seed: int, env_offset: int, n: int, t: int, k: int, W: int, A: int):
+    """The step kernel's normals of environments 0 .. n-1 at step word t and chain index k, on the host: float64 [n, W, A].  Exact on the 32-bit words
+    (``ddpm_gpt_words``: two calls q per (row, j)) and f64 from there on: Box-Muller with u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24,
+    (n0, n1) = sqrt(-2 ln u1) (cos, sin)(2 pi u2), (n2, n3) likewise from r2, r3; component a = 4 q + m."""
+    import numpy as np
+    assert 1 <= A <= 8
+    r = ddpm_gpt_words(seed, env_offset, n, t, k, W)
+    out = np.zeros((n, W, 2, 4))
+    for p in range(2):
+        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+        rad = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
+    return out.reshape(n, W, 8)[:, :, :A]
+
+
+class DiffusionGPTDenoiser(nn.Module):
+    """DiffusionTransformerNetwork (agents/models/diffusion/diffusion_models.py:409-667), not goal conditioned, with the reference's parameter names - ``tok_emb``,
+    ``pos_emb``, ``blocks.N...``, ``ln_f``, ``time_emb.1 / .3``, ``action_emb``, ``action_pred`` - so the entries of ``Diffusion.state_dict()`` under ``model.``
+    load with ``load_state_dict``.  It is DiffusionGPT with the time-step MLP (SinusoidalPosEmb(C) -> Linear(C, 2 C) -> Mish -> Linear(2 C, C)) in place of
+    ``sigma_emb``: tokens [time, s_1, a_1, ..., s_t, a_t], the same ``_Block`` (120-wide nets take the matrix-core kernels), the action positions are decoded."""
+
+    def __init__(self, state_dim, action_dim, embed_dim, n_layers, n_heads, obs_seq_len, linear_output=True):
+        super().__init__()
+        block_size = 2 * obs_seq_len + 1
+        self.tok_emb = nn.Linear(state_dim, embed_dim)
+        self.pos_emb = nn.Parameter(torch.zeros(1, obs_seq_len + 1, embed_dim))
+        self.blocks = nn.Sequential(*[_Block(embed_dim, n_heads, block_size) for _ in range(n_layers)])
+        self.ln_f = nn.LayerNorm(embed_dim)
+        self.time_emb = nn.Sequential(_SinusoidalPosEmb(embed_dim), nn.Linear(embed_dim, embed_dim * 2), nn.Mish(), nn.Linear(embed_dim * 2, embed_dim))
+        self.action_emb = nn.Linear(action_dim, embed_dim)
+        self.action_pred = nn.Linear(embed_dim, action_dim) if linear_output else nn.Sequential(nn.Linear(embed_dim, 100), nn.GELU(), nn.Linear(100, action_dim))
+        self.goal_conditioned = False
+        self.state_dim, self.action_dim, self.obs_seq_len, self.embed_dim, self.n_heads, self.linear_output = state_dim, action_dim, obs_seq_len, embed_dim, n_heads, bool(linear_output)
+
+    def hidden(self, xbuf, keep):
+        """The block chain on a token buffer [b, 2 t + 1, C]: the last block's output at the positions ``keep`` (before ln_f)."""
+        x = xbuf
+        for blk in self.blocks[:-1]:
+            x = blk(x)
+        return self.blocks[-1](x, keep=keep)
+
+    def forward(self, actions, time, states, goals=None):
+        """The reference's forward without goals: eps [b, t, A] for actions [b, t, A], time [b] (integers) and states [b, t, state_dim]."""
+        b, t, _ = states.size()
+        emb_t = self.time_emb(time.reshape(b)).unsqueeze(1)
+        pos = self.pos_emb[:, :t, :]
+        state_x, action_x = self.tok_emb(states) + pos, self.action_emb(actions) + pos
+        sa = torch.stack([state_x, action_x], dim=1).permute(0, 2, 1, 3).reshape(b, 2 * t, self.embed_dim)
+        x = torch.cat([emb_t, sa], dim=1).contiguous()
+        keep = torch.arange(2, 2 * t + 1, 2, device=x.device)
+        return self.action_pred(_layer_norm(self.ln_f, self.hidden(x, keep).contiguous()))
+
+
+class DDPMGPTPolicy:
+    """DiffusionAgent.predict with window_size > 1 (agents/ddpm_agent.py:213-274) around Diffusion.sample (gc_diffusion.py:117-216) with the transformer denoiser, on
+    a batch: scaled observation window (deque maxlen W; the window GROWS at episode start), ALL L action positions of the window start from noise (no action history,
+    unlike BESO), T reverse steps - epsilon prediction, x0 clipped to the data bounds in scaled space, posterior mean, posterior noise except at step 0 -, final clamp,
+    the action of the last valid position, inverse scaling.
+
+    Always the fixed-shape form: windows right-padded to W (_History.padded), lengths on the device, in-place history.  Causal attention never lets a valid position see
+    the padding behind it and ``pos_emb[:L]`` of the reference equals the first L rows of the padded form, so a lane with L < W entries gets the reference's numbers;
+    the few extra tokens during the first W - 1 steps of an episode buy ONE code path that can be captured (CapturedPolicy).
+
+    One predict_batch: the state tokens once (torch), one launch of the step kernel in its init mode (csrc/policy_ddpm_gpt.h through d3il_ddpm_gpt_step_f32: first
+    iterate = noise, its action tokens, the time token), then T times the block chain (the last block on the action positions only) and one launch of the step kernel
+    (ln_f, head, clipped x0, posterior mean, noise, the next iterate's tokens; at step 0 the clamped, inverse-scaled action), then a device-side add on the step word.
+
+    The noise is Box-Muller on Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word, DDPM_GPT_TAG | k << 8 | j << 1 | q) - chain index k = T for the
+    first iterate, i for reverse step i; index 0 is never drawn - so results do not depend on batch order, sub-batches or ranks (``ddpm_gpt_normals`` is the host form);
+    or ``noise_in(k, n) -> [n, W, A]`` when given (golden replay, tests).  On the CPU, for unsupported shapes (the Linear-GELU-Linear head among them) and with
+    D3IL_POLICY_DDPM_GPT_STEP=0 the same arithmetic runs as torch ops (``_step_torch``) with the Philox normals computed on the host - that path cannot be captured.
+    A NaN / Inf in a valid hidden row or iterate marks the environment (``last_bad``) and its action comes out NaN (D3IL_FLAG_SOLVER_FAIL in that lane's step)."""
+
+    def __init__(self, model: DiffusionGPTDenoiser, scaler: Scaler, n_timesteps: int, window_size: int, seed: int = 0, noise_in=None):
+        self.model, self.scaler, self.T, self.W = model.eval(), scaler, int(n_timesteps), int(window_size)
+        assert 1 <= self.T <= 255 and 1 <= self.W <= 16, "the Philox counter layout holds T <= 255 and W <= 16"
+        assert self.W <= model.obs_seq_len, "the window cannot exceed the denoiser's obs_seq_len"
+        dev = scaler.x_mean.device
+        self.device = dev
+        self.A = int(model.action_dim)
+        sch = ddpm_schedule(cosine_beta_schedule(self.T).to(dev))
+        self.sqrt_recip_ac, self.sqrt_recipm1_ac, self.post_logvar, self.coef1, self.coef2, self._sched = (sch[k] for k in ("sqrt_recip_ac", "sqrt_recipm1_ac", "post_logvar", "coef1", "coef2", "sched"))
+        f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
+        self.min_action, self.max_action = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self.seed, self.env_offset, self.noise_in = int(seed), 0, noise_in
+        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self.hist = None
+        self._packed = PackedWeights()
+        self.record = False           # also keep what every launch drew (last_noise: {k: [n, W, A]})
+        self.last_bad = self.last_noise = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, noise_in=None, device=None):
+        """From a live reference ``DiffusionAgent`` (duck-typed) whose ``model`` is a ``Diffusion`` around a ``DiffusionTransformerNetwork``: the denoiser's state
+        dict, ``n_timesteps``, ``agent.scaler``, ``agent.window_size``; with ``agent.use_ema`` the EMA shadow parameters (the reference swaps them in for every predict)."""
+        diff = agent.model
+        net = diff.model
+        sd = {k: torch.as_tensor(v) for k, v in net.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["tok_emb.weight"].device
+        C, state_dim = sd["tok_emb.weight"].shape
+        A = sd["action_emb.weight"].shape[1]
+        n_layers = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        n_heads = int(net.blocks[0].attn.n_head)
+        den = DiffusionGPTDenoiser(state_dim, A, C, n_layers, n_heads, sd["pos_emb"].shape[1] - 1, linear_output="action_pred.weight" in sd)
+        den.load_state_dict(sd)
+        den = den.to(dev)
+        for p in den.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        pol = cls(den, scaler, int(diff.n_timesteps), int(agent.window_size), seed=seed, noise_in=noise_in)
+        if getattr(agent, "use_ema", False):
+            pol.use_ema(agent.ema_helper.shadow_params)
+        return pol
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Does ``agent`` look like the reference's DiffusionAgent around a DiffusionTransformerNetwork without goals (what from_reference reads), configured as the
+        sampler restated here (``model.betas`` = the cosine schedule, epsilon prediction, clip_denoised, neither diffusion_x nor diffusion_kde)?  The DDPM-MLP agent
+        (no ``time_emb`` / ``action_emb`` / ``blocks``) and BeT do not."""
+        try:
+            diff = agent.model
+            net = diff.model
+            if not (hasattr(net, "time_emb") and hasattr(net, "action_emb") and hasattr(net, "blocks") and hasattr(net, "state_dict") and net.goal_conditioned is False
+                    and hasattr(agent, "scaler") and int(agent.window_size) >= 1):
+                return False
+            # the sampler this policy restates: cosine schedule, epsilon prediction, clipped x0, no diffusion-x tail, no KDE selection - any other switch of the
+            # reference's configuration keeps the agent on the row-by-row adapter, which runs the reference's own code
+            if getattr(diff, "diffusion_x", False) or getattr(agent, "diffusion_kde", False) or not getattr(diff, "predict_epsilon", True) or not getattr(diff, "clip_denoised", True):
+                return False
+            T = int(diff.n_timesteps)
+            betas = torch.as_tensor(diff.betas).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+            return 1 <= T <= 255 and betas.shape[0] == T and bool(torch.equal(betas, cosine_beta_schedule(T)))
+        except (AttributeError, TypeError, ValueError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet
+    @property
+    def f16x3_blocks(self) -> bool:
+        """The blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
+        return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.model.blocks)
+
+    def reset(self):
+        if self.hist is not None:
+            self.hist.reset()
+
+    def begin_episodes(self, mask):
+        if self.hist is not None:
+            self.hist.reset_(mask)
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+        if self.hist is not None and self.hist.buf.shape[0] != count:
+            self.hist = None
+
+    def fork(self):
+        """A clone for another sub-batch: denoiser, scaler and schedule shared; history, step word and packed tables its own."""
+        import copy
+        c = copy.copy(self)
+        c.hist = None
+        c._t = self._t.clone()
+        c._packed = PackedWeights()
+        c.last_bad = c.last_noise = None
+        return c
+
+    def load_reference_state_dict(self, sd):
+        """``Diffusion.state_dict()`` of the reference: the denoiser sits under ``model.``."""
+        self.model.load_state_dict({k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")})
+
+    def use_ema(self, shadow_params):
+        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order."""
+        with torch.no_grad():
+            for p, s in zip(self.model.parameters(), shadow_params):
+                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
+
+    # ---- packed tables
+    def _pack_params(self):
+        m = self.model
+        return list(m.time_emb.parameters()) + [m.action_emb.bias, m.pos_emb]
+
+    def _pack(self):
+        """temb [T, C] = time_emb(arange(T)); the schedule table [T, 5] (ddpm_schedule: the one DDPMPolicy packs, sig[0] = 0); bias_pos [W, C] = action_emb.bias + pos_emb[:W]."""
+        m, dev = self.model, self.model.pos_emb.device
+        return {"temb": m.time_emb(torch.arange(self.T, device=dev)).to(torch.float32).contiguous(),
+                "sched": self._sched.to(device=dev, dtype=torch.float32).contiguous(),
+                "bias_pos": (m.action_emb.bias + m.pos_emb[0, :self.W]).to(torch.float32).contiguous()}
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        self._packed.invalidate()
+        for blk in self.model.blocks:
+            blk.invalidate_packed()
+
+    def ensure_packed(self):
+        """The packed tables and the blocks' packed weights follow the parameters (outside any capture) - e.g. after the EMA swap of a rollout."""
+        self._packed.ensure(self._pack_params(), self._pack)
+        if self.model.pos_emb.is_cuda:
+            ensure_blocks_packed(self.model.blocks)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Before the warm-up calls of a capture: the per-episode state (history, lengths, step word), which capture_restore puts back - warm-up and capture do not
+        count as steps.  (The chain has one form only: nothing to switch.)"""
+        if self.hist is None or self.hist.buf.shape[0] != obs.shape[0]:
+            self.hist = _History(obs.shape[0], self.W, obs.shape[1], self.device)
+        return (self.hist.buf.clone(), self.hist.len.clone(), self.hist.lockstep, self._t.clone())
+
+    def capture_restore(self, snap):
+        buf, ln, lock, t = snap
+        self.hist.buf.copy_(buf); self.hist.len.copy_(ln); self._t.copy_(t)
+        self.hist.lockstep = lock
+
+    # ---- one step of the chain
+    def step_kernel_ok(self, dev) -> bool:
+        m = self.model
+        C = m.embed_dim
+        return (dev.type == "cuda" and m.linear_output and m.pos_emb.dtype == torch.float32 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 8 and 1 <= self.W <= 16 and 1 <= self.T <= 255
+                and os.environ.get("D3IL_POLICY_DDPM_GPT_STEP", "1") == "1")
+
+    def _noise(self, k, n, dev):
+        """The normals of chain index k as the torch path takes them: ``noise_in(k, n)`` or the host form of the kernel's Philox draw."""
+        if self.noise_in is not None:
+            return torch.as_tensor(self.noise_in(k, n), dtype=torch.float32).to(dev).reshape(n, self.W, self.A).contiguous()
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DDPMGPTPolicy: the torch path draws its Philox normals on the host and cannot be captured; the step kernel draws on the device")
+        return torch.as_tensor(ddpm_gpt_normals(self.seed, self.env_offset, n, int(self._t.item()) & 0xFFFFFFFF, k, self.W, self.A), dtype=torch.float32).to(dev)
+
+    def _step_torch(self, st, k, hk):
+        """Steps 1 - 8 of csrc/policy_ddpm_gpt.h as torch ops, in the kernel's order of operations, on the chain state ``st`` (x, xbuf, bad, lengths, packed tables)."""
+        m, T, W = self.model, self.T, self.W
+        x, xbuf, ln, w = st["x"], st["xbuf"], st["len"], st["w"]
+        n = x.shape[0]
+        valid = (torch.arange(W, device=x.device) < ln.unsqueeze(1)).unsqueeze(2)
+        if k == T:
+            noise = self._noise(k, n, x.device)
+            xp = noise
+            st["bad"].zero_()
+            hit = ~torch.isfinite(xp)
+        else:
+            noise = self._noise(k, n, x.device) if (k > 0 or self.noise_in is not None) else torch.zeros_like(x)
+            eps = m.action_pred(m.ln_f(hk))
+            s = w["sched"][k]
+            x0 = torch.minimum(torch.maximum(s[0] * x - s[1] * eps, self.min_action), self.max_action)
+            mean = s[2] * x0 + s[3] * x
+            xp = mean if k == 0 else mean + s[4] * noise
+            hit = ~torch.isfinite(hk).all(dim=2, keepdim=True) | ~torch.isfinite(eps) | ~torch.isfinite(x) | ~torch.isfinite(xp)
+        st["bad"] |= (hit & valid).any(dim=2).any(dim=1).to(torch.int32)
+        xp = torch.where(valid, xp, torch.zeros_like(xp))
+        if self.record:
+            self.last_noise[k] = noise
+        if k > 0:
+            x.copy_(xp)
+            xbuf[:, 0] = w["temb"][k - 1]
+            xbuf[:, 2::2] = w["bias_pos"] + xp @ m.action_emb.weight.t()
+        else:
+            last = xp.gather(1, (ln - 1).view(n, 1, 1).expand(-1, 1, self.A)).squeeze(1)
+            y = torch.minimum(torch.maximum(last, self.min_action), self.max_action) * self.out_scale + self.out_shift
+            st["actions"].copy_(torch.where(st["bad"].bool().unsqueeze(1), torch.full_like(y, float("nan")), y))
+
+    def _step_kernel(self, st, k, hk):
+        from . import capi
+        m, w, dev = self.model, st["w"], st["x"].device
+        n = st["x"].shape[0]
+        noise_in = self._noise(k, n, dev) if self.noise_in is not None else None
+        noise_out = torch.empty(n, self.W, self.A, dtype=torch.float32, device=dev) if self.record else None
+        ptr = lambda v: None if v is None else v.data_ptr()
+        assert hk is None or hk.is_contiguous()
+        assert m.action_pred.weight.is_contiguous() and m.action_emb.weight.is_contiguous() and self._t.device == dev
+        capi.check(capi.load().d3il_ddpm_gpt_step_f32(ptr(hk), m.ln_f.weight.data_ptr(), m.ln_f.bias.data_ptr(), float(m.ln_f.eps), m.action_pred.weight.data_ptr(),
+                                                      m.action_pred.bias.data_ptr(), m.action_emb.weight.data_ptr(), w["bias_pos"].data_ptr(), w["temb"].data_ptr(), w["sched"].data_ptr(),
+                                                      self.min_action.data_ptr(), self.max_action.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), st["len"].data_ptr(),
+                                                      self.seed, self.env_offset, self._t.data_ptr(), ptr(noise_in), st["x"].data_ptr(), st["xbuf"].data_ptr(), st["actions"].data_ptr(),
+                                                      st["bad"].data_ptr(), ptr(noise_out), n, m.embed_dim, self.A, self.W, self.T, k, torch.cuda.current_stream(dev).cuda_stream))
+        if self.record:
+            self.last_noise[k] = noise_out
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32))
+        m, W, T = self.model, self.W, self.T
+        n, dev = s.shape[0], s.device
+        capturing = s.is_cuda and torch.cuda.is_current_stream_capturing()
+        if s.is_cuda and not _ENV_GUARD_TRIED and self.f16x3_blocks:
+            _env_range_guard(dev)
+        if not capturing:
+            self.ensure_packed()
+        assert self._packed.key is not None, "a captured graph replays the packed tables: call ensure_packed() before capturing"
+        w = self._packed.buf
+        if self.hist is None or self.hist.buf.shape[0] != n:
+            self.hist = _History(n, W, s.shape[1], self.device)
+        self.hist.append_(s)
+        states, ln = self.hist.padded()
+        C = m.embed_dim
+        st = dict(x=torch.empty(n, W, self.A, dtype=torch.float32, device=dev), xbuf=torch.empty(n, 2 * W + 1, C, dtype=torch.float32, device=dev),
+                  actions=torch.empty(n, self.A, dtype=torch.float32, device=dev), bad=torch.empty(n, dtype=torch.int32, device=dev), len=ln.contiguous(), w=w)
+        # 1. the state tokens: the same in every sampling step
+        torch.add(m.tok_emb(states), m.pos_emb[0, :W, :], out=st["xbuf"][:, 1::2])
+        if getattr(self, "_keep", None) is None or self._keep.device != dev:
+            self._keep = torch.arange(2, 2 * W + 1, 2, device=dev)
+        step = self._step_kernel if self.step_kernel_ok(dev) else self._step_torch
+        if self.record:
+            self.last_noise = {}
+        step(st, T, None)                                                    # 2. first iterate = noise, its tokens, the time token of step T - 1
+        for i in reversed(range(T)):                                         # 3. T times: the blocks, then everything up to the next token buffer
+            step(st, i, m.hidden(st["xbuf"], self._keep).contiguous())
+        self._t.add_(1)                                                      # 4. the step word
+        self.last_bad = st["bad"]
+        return st["actions"]
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, embed_dim: int = 120, n_layers: int = 6, n_heads: int = 6, window_size: int = 5,
+               n_timesteps: int = 8, action_scale: float = 0.002, noise_in=None, policy_seed: int = 0, linear_output: bool = True):
+        """A policy of the reference's Stacking / Sorting shape (6 layers, 6 heads, 120 wide, window 5, 8 timesteps) with fixed random weights - there are no
+        checkpoints offline (as BeTPolicy.random): torch's default layer initialisation, position rows of standard deviation 0.1, a head that predicts noise of
+        roughly unit size, unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-1.5."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            den = DiffusionGPTDenoiser(obs_dim, action_dim, embed_dim, n_layers, n_heads, window_size, linear_output=linear_output)
+        with torch.no_grad():
+            den.pos_emb.copy_(torch.randn(den.pos_emb.shape, generator=g) * 0.1)
+            if linear_output:
+                den.action_pred.weight.copy_(torch.randn(den.action_pred.weight.shape, generator=g) * (1.0 / embed_dim ** 0.5))
+        for p in den.parameters():
+            p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
+        return cls(den.to(device), sc, n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)

@@ -221,6 +221,23 @@ int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln
 int d3il_bet_head_f32(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_head, const float* centers, const float* lo, const float* hi,
                       const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* u_in, float* actions, int32_t* bins,
                       float* u_out, float* probs, long rows, int C, int V, int A, void* stream);
+/* Everything between two block chains of the batched DDPM-GPT sampler (policies.DDPMGPTPolicy; ddpm_agent.py:213-274, gc_diffusion.py:117-216 around
+ * diffusion_models.py DiffusionTransformerNetwork) in one launch, f32 throughout.  k = T - 1 .. 0 are the reverse steps, k = T the init mode.  For environment n and
+ * window position j < W: z = LayerNorm(hk[n][j]); eps_a = w_pred[a] . z + b_pred[a]; x0_a = clamp(sched[k][0] x_a - sched[k][1] eps_a, lo_a, hi_a);
+ * mean_a = sched[k][2] x0_a + sched[k][3] x_a; x'_a = mean_a + sched[k][4] noise_a (k = 0: x' = mean_a, nothing is drawn).  k > 0: x[n][j] = x',
+ * xbuf[n][2 + 2 j][c] = sum_a w_aemb[c][a] x'_a + bias_pos[j][c] and xbuf[n][0] = temb[k - 1]; k = 0: actions[n][a] = clamp(x'_a, lo_a, hi_a) scale_a + shift_a at
+ * j = len[n] - 1.  Init mode: x' = noise (hk is not read and may be NULL), bad is cleared.  Positions j >= len[n]: x' = 0, the token is bias_pos[j].
+ * noise_a = noise_in[n][j][a] when given (the [n_env][W][A] slice of THIS chain index), otherwise Box-Muller (u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24,
+ * sqrt(-2 ln u1) (cos, sin)(2 pi u2); r2, r3 likewise) on Philox4x32-10 with key = seed and counter = (env_offset + n, *t_device, 0x44470000 | k << 8 | j << 1 | q),
+ * component a = 4 q + m.  hk [n_env][W][C], w_pred [A][C], w_aemb [C][A] (nn.Linear weights as they are), bias_pos [W][C], temb [T][C], sched [T][5], lo / hi (scaled
+ * space) / scale / shift [A], len i64 [n_env] (clamped to 1 .. W), t_device: DEVICE u32, x [n_env][W][A] (in / out), xbuf [n_env][2 W + 1][C], noise_out
+ * [n_env][W][A] may be NULL.  bad i32 [n_env]: sticky from the init launch on - set by a NaN / Inf in a valid hidden row, normalised row or iterate; at k = 0 such an
+ * environment gets NaN in every action component.  Built for C <= 128 (a multiple of 4), 1 <= A <= 8, 1 <= W <= 16, 1 <= T <= 255: D3IL_EUNSUPPORTED otherwise,
+ * answered before any launch. */
+int d3il_ddpm_gpt_step_f32(const float* hk, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_pred, const float* b_pred, const float* w_aemb,
+                           const float* bias_pos, const float* temb, const float* sched, const float* lo, const float* hi, const float* scale, const float* shift,
+                           const int64_t* len, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* noise_in, float* x, float* xbuf, float* actions,
+                           int32_t* bad, float* noise_out, long n_env, int C, int A, int W, int T, int k, void* stream);
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
