@@ -27,6 +27,7 @@ constexpr int WAVE = 64;
 #include "policy_f16x3.h"
 #include "policy_bet.h"
 #include "policy_ddpm_gpt.h"
+#include "policy_ibc.h"
 
 namespace d3il {
 
@@ -1733,6 +1734,29 @@ int d3il_ddpm_gpt_step_f32(const float* hk, const float* ln_weight, const float*
   if (C == 72) hipLaunchKernelGGL(k_ddpm_gpt_step<72>, grid, block, 0, (hipStream_t)stream, a);
   else if (C == 120) hipLaunchKernelGGL(k_ddpm_gpt_step<120>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_ddpm_gpt_step<128>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_ibc_langevin_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out,
+                          const float* wT_blocks, const float* wT_in_act, const float* coef, float noise_scale, const float* lo, const float* hi, const float* clip,
+                          const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* x0_in, const float* noise_in,
+                          const float* u_in, float* actions, int32_t* picks, float* x_final, float* energies, float* x0_out, float* noise_out, float* u_out, long n_env,
+                          int obs_dim, int A, int hidden, int n_blocks, int S, int K, void* stream) {
+  if ((hidden != 128 && hidden != 256) || A < 1 || A > IBC_AMAX || obs_dim < 0 || obs_dim + A > 28 || S != IBC_S || K < 0 || K > IBC_KMAX || n_blocks < 0 || n_blocks > IBC_MAXB ||
+      n_env > 0x7FFFFFFFL)
+    return fail(D3IL_EUNSUPPORTED, "d3il_ibc_langevin_f32: built for hidden 128 / 256, 0 .. 4 residual blocks, obs_dim + A <= 28, 1 .. 8 action components, 64 samples and 0 .. 63 iterations");
+  if (!state || !w_in || !b_in || !w_blocks || !b_blocks || !w_out || !b_out || !wT_blocks || !wT_in_act || (!coef && K > 0) || !lo || !hi || !clip || !scale || !shift || !t_device || !actions || !picks)
+    return fail(D3IL_EINVAL, "d3il_ibc_langevin_f32: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_ibc_langevin_f32: negative environment count");
+  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_out | (uintptr_t)wT_blocks | (uintptr_t)wT_in_act) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_ibc_langevin_f32: the packed weights and biases must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  IbcArgs a{state, w_in, b_in, w_blocks, b_blocks, w_out, b_out, wT_blocks, wT_in_act, coef, lo, hi, clip, scale, shift, t_device, x0_in, noise_in, u_in, actions, picks, x_final, energies,
+            x0_out, noise_out, u_out, (unsigned long long)seed, (unsigned long long)env_offset, n_env, noise_scale, obs_dim, A, n_blocks, K};
+  // one workgroup per environment: its four row tiles of 16 samples one after the other, then the draw
+  const dim3 grid((unsigned)n_env), block(64 * IBC_NW);
+  if (hidden == 128) hipLaunchKernelGGL(k_ibc_langevin<128>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_ibc_langevin<256>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -1735,3 +1735,352 @@ class DDPMGPTPolicy:
             p.requires_grad_(False)
         sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
         return cls(den.to(device), sc, n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)
+
+
+# ------------------------------------------------------------------------------------------------ Implicit BC: Langevin chain on an energy network
+IBC_TAG = 0x49420000          # fourth Philox counter word of the chain kernel, or-ed with kind << 14 | k << 8 | s << 2 | q (csrc/policy_ibc.h; never 0, BET_TAG or a DDPM_GPT_TAG word)
+IBC_EDGE = 1e-4               # a draw this close to an edge of the normalised CDF is not decided between two arithmetics (tests, golden generator)
+
+
+def ibc_words(seed: int, env_offset: int, n: int, t: int, kind: int, k: int, S: int = 64):
+    """The Philox words of the chain kernel: uint32 [n, S, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
+    IBC_TAG | kind << 14 | k << 8 | s << 2 | q)); kind 0 = start point, 1 = noise of iteration k, 2 = the draw (s = q = 0 is the word that is used)."""
+    import numpy as np
+    assert 0 <= kind <= 2 and 0 <= k <= 63 and 1 <= S <= 64, "the counter layout holds k <= 63 and s <= 63"
+    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1, 1)
+    s = np.arange(S, dtype=np.uint64).reshape(1, S, 1)
+    q = np.arange(2, dtype=np.uint64).reshape(1, 1, 2)
+    tag = np.uint64(IBC_TAG | (kind << 14) | (k << 8)) | (s << np.uint64(2)) | q
+    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+
+
+def ibc_start_uniforms(seed: int, env_offset: int, n: int, t: int, A: int, S: int = 64):
+    """The kernel's start-point uniforms of environments 0 .. n-1 at step word t: float32 [n, S, A] in [0, 1 - 2^-24], component a = 4 q + m takes word m of
+    call q.  The start point is lo + u (hi - lo), every operation rounded to f32."""
+    import numpy as np
+    assert 1 <= A <= 8
+    r = ibc_words(seed, env_offset, n, t, 0, 0, S).reshape(n, S, 8)[:, :, :A]
+    return ((r >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+
+
+def ibc_normals(seed: int, env_offset: int, n: int, t: int, k: int, A: int, S: int = 64):
+    """The kernel's normals of iteration k: float64 [n, S, A].  Exact on the words and f64 from there on, Box-Muller as ``ddpm_gpt_normals``."""
+    import numpy as np
+    assert 1 <= A <= 8
+    r = ibc_words(seed, env_offset, n, t, 1, k, S)
+    out = np.zeros((n, S, 2, 4))
+    for p in range(2):
+        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+        rad = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
+    return out.reshape(n, S, 8)[:, :, :A]
+
+
+def ibc_pick_uniforms(seed: int, env_offset: int, n: int, t: int):
+    """The kernel's uniform of the categorical draw, one per environment: float32 [n]."""
+    import numpy as np
+    r0 = ibc_words(seed, env_offset, n, t, 2, 0, 1)[:, 0, 0, 0]
+    return ((r0 >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+
+
+def ibc_step_sizes(iterations: int, init_infer: float, init: float, final: float, power: float, second_init: float, second: bool = True):
+    """The step sizes of LangevinMCMCSampler.infer as Python floats: the first step is ``sampler_stepsize_init_infer``, steps 1 .. I-1 follow the polynomial
+    schedule that starts from ``sampler_stepsize_init`` (NOT the _infer value; schedulers.py:16-23 with its I - 1 denominator), the second loop of I steps
+    keeps ``second_inference_stepsize_init``."""
+    I = int(iterations)
+    steps = [float(init_infer)] + [(init - final) * ((1.0 - float(i) / float(I - 1)) ** power) + final for i in range(1, I)]
+    return steps[:I] + ([float(second_init)] * I if second else [])
+
+
+def _mish_and_derivative(x):
+    """Mish and its derivative in the form of csrc/policy_ibc.h ibc_mish: n = e^x, p = n (n + 2), t = p / (p + 2); x t and t + x 4 n (n + 1) / (p + 2)^2; x > 20: x, 1."""
+    big = x > 20.0
+    n = torch.exp(torch.where(big, torch.zeros_like(x), x))
+    p = n * (n + 2.0)
+    q = p + 2.0
+    t = p / q
+    return torch.where(big, x, x * t), torch.where(big, torch.ones_like(x), t + x * (4.0 * n * (n + 1.0)) / (q * q))
+
+
+def resmlp_energy_and_grad(model: ResidualMLP, rows, obs_dim: int, grad: bool = True):
+    """E = model(rows)[:, 0] and dE / d rows[:, obs_dim:] of a ResidualMLP with one output, analytically, in the dtype of ``rows`` and the parameters:
+    per block y = x + W2 m(W1 m(x) + b1) + b2 the row gradient is gx = gy + m'(x) . ((m'(u) . (gy W2)) W1); the chain starts from the output row."""
+    lin_in, blocks, lin_out = model._parts()
+    x = F.linear(rows, lin_in.weight, lin_in.bias)
+    kept = []
+    for l1, l2 in blocks:
+        m0, d0 = _mish_and_derivative(x)
+        m1, d1 = _mish_and_derivative(F.linear(m0, l1.weight, l1.bias))
+        x = x + F.linear(m1, l2.weight, l2.bias)
+        kept.append((d0, d1))
+    e = F.linear(x, lin_out.weight, lin_out.bias)[:, 0]
+    if not grad:
+        return e, None
+    g = lin_out.weight[0].expand_as(x)
+    for (l1, l2), (d0, d1) in zip(reversed(blocks), reversed(kept)):
+        g = g + d0 * ((d1 * (g @ l2.weight)) @ l1.weight)
+    return e, g @ lin_in.weight[:, obs_dim:]
+
+
+class IBCPolicy:
+    """IBCAgent.predict without goals (agents/ibc_agent.py:248-286) around LangevinMCMCSampler.infer (samplers/langevin_mcmc.py:129-163, 236-286) on the energy
+    network EBMMLP (ebms.py:21-51: a ResidualMLPNetwork on [state | action] with one output), on a batch: scale the observation, S uniform start points per
+    environment inside the data bounds (scaled space), K Langevin iterations x <- clamp(x - clamp(step / 2 dE/dx + step noise_scale z, +-clip), lo, hi) with
+    clip = delta_action_clip (hi - lo) / 2 - the noise is multiplied by the step, not by its root, as the reference does; the samples are carried in f64 and the
+    network runs in f32, also as the reference does (its f64 bounds array promotes the samples, ResidualMLPNetwork.forward casts to f32) -, one categorical draw from
+    softmax(-E) of the final samples, inverse scaling (no clamp afterwards: the sampler's bounds are the only one).  ``steps`` is the table of
+    ``ibc_step_sizes``.
+
+    On a HIP device the whole call is ONE kernel (csrc/policy_ibc.h through d3il_ibc_langevin_f32: forward pass, analytic backward pass and update for all
+    iterations, the energies and the draw; hidden 128 / 256, at most 4 blocks, obs + A <= 28, S = 64, K <= 63), then a device-side add on the step word.  On the
+    CPU, for other shapes and with D3IL_POLICY_IBC_FUSED=0 the same arithmetic runs as torch ops (``_chain_torch``, the analytic gradient of
+    ``resmlp_energy_and_grad``) on the same Philox stream computed on the host - that path cannot be captured.  Random numbers: Philox4x32-10 keyed by ``seed``
+    with counter (env_offset + lane, step word, IBC_TAG | kind << 14 | k << 8 | s << 2 | q), so results do not depend on batch order, sub-batches or ranks;
+    ``x0_in(n) -> [n, S, A]``, ``noise_in(n) -> [K, n, S, A]`` (standard normals) and ``u_in(n) -> [n]`` replace the draws when given (golden replay, tests).
+    A NaN / Inf in an environment's state row, iterates or final energies gives that environment a NaN action (``last_picks`` = -1)."""
+
+    def __init__(self, model: ResidualMLP, scaler: Scaler, steps, noise_scale: float = 0.5, delta_action_clip: float = 0.1, samples: int = 64, seed: int = 0,
+                 n_envs: int | None = None, bounds=None, x0_in=None, noise_in=None, u_in=None):
+        self.model, self.scaler = model.eval(), scaler
+        dev = scaler.x_mean.device
+        self.device = dev
+        lin_in, _, lin_out = model._parts()
+        assert lin_out.out_features == 1, "the energy network has one output"
+        b = torch.as_tensor(scaler.y_bounds if bounds is None else bounds).detach().to(device="cpu", dtype=torch.float64)
+        self.A = int(b.shape[1])
+        self.obs_dim = int(lin_in.in_features) - self.A
+        self.S, self.K = int(samples), len(steps)
+        assert 1 <= self.A <= 8 and 1 <= self.S <= 64 and 0 <= self.K <= 63, "the Philox counter layout holds A <= 8, S <= 64 and K <= 63"
+        self.steps = [float(v) for v in steps]
+        self.noise_scale, self.delta_action_clip = float(noise_scale), float(delta_action_clip)
+        f = lambda a: a.to(device=dev, dtype=torch.float32).contiguous()
+        self.lo, self.hi, self.clip = f(b[0]), f(b[1]), f(self.delta_action_clip * 0.5 * (b[1] - b[0]))      # (the clip in f64 from the f64 bounds, as the reference)
+        self.coef = f(torch.tensor([[v * 0.5, v] for v in self.steps], dtype=torch.float64).reshape(self.K, 2))
+        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self.seed, self.env_offset, self.n_envs = int(seed), 0, n_envs
+        self.x0_in, self.noise_in, self.u_in = x0_in, noise_in, u_in
+        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self._packed = PackedWeights()
+        self.record = False           # also keep the chain's start points, noise, final samples and energies (last_x0, last_noise, last_x, last_energies)
+        self.last_picks = self.last_u = self.last_x0 = self.last_noise = self.last_x = self.last_energies = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, n_envs: int | None = None, device=None, **banks):
+        """From a live reference ``IBCAgent`` (duck-typed): ``agent.model.mlp.state_dict()``, ``agent.sampler``'s settings and f64 bounds, ``agent.scaler``; with
+        ``agent.use_ema`` the EMA shadow parameters (the reference swaps them in for every predict)."""
+        mlp, smp = agent.model.mlp, agent.sampler
+        sd = {k: torch.as_tensor(v) for k, v in mlp.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["layers.0.weight"].device
+        hidden, in_dim = sd["layers.0.weight"].shape
+        n_blocks = len({k.split(".")[1] for k in sd if ".l1." in k})
+        net = ResidualMLP(in_dim, hidden, 2 * n_blocks, 1)
+        net.load_state_dict(sd)
+        net = net.to(dev)
+        for p in net.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        steps = ibc_step_sizes(smp.inference_iterations, smp.sampler_stepsize_init_infer, smp.sampler_stepsize_init, smp.sampler_stepsize_final, smp.sampler_stepsize_power,
+                               smp.second_inference_stepsize_init, bool(smp.second_infer))
+        pol = cls(net, scaler, steps, noise_scale=smp.noise_scale_infer, delta_action_clip=smp.delta_action_clip, samples=int(smp.inference_samples), seed=seed, n_envs=n_envs,
+                  bounds=smp.bounds, **banks)
+        if getattr(agent, "use_ema", False):
+            pol.use_ema(agent.ema_helper.shadow_params)
+        return pol
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: an IBCAgent without goal conditioning whose sampler is a plain LangevinMCMCSampler (none of its
+        subclasses) on the polynomial schedule and whose model is an EBMMLP around a Mish ResidualMLPNetwork without norm and without spectral norm, with one
+        output, at most 64 samples and 63 iterations?  Everything else stays on the row-by-row adapter, which runs the reference's own code."""
+        try:
+            smp, ebm = agent.sampler, agent.model
+            if type(smp).__name__ != "LangevinMCMCSampler" or not getattr(smp, "_use_polynomial_rate", False) or not hasattr(smp, "infer_schedule"):
+                return False
+            if agent.goal_conditioning is not False or type(ebm).__name__ != "EBMMLP" or not hasattr(agent, "scaler") or smp.bounds is None:
+                return False
+            layers = list(ebm.mlp.layers)
+            lins = [layers[0], layers[-1]] + [l for b in layers[1:-1] for l in (b.l1, b.l2)]
+            if not all(isinstance(l, nn.Linear) and not hasattr(l, "weight_orig") for l in lins) or layers[-1].out_features != 1:
+                return False
+            if not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in layers[1:-1]):
+                return False
+            K = int(smp.inference_iterations) * (2 if smp.second_infer else 1)
+            return int(smp.inference_iterations) >= 2 and K <= 63 and 1 <= int(smp.inference_samples) <= 64 and 1 <= smp.bounds.shape[1] <= 8
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet
+    def reset(self):
+        pass
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+
+    def fork(self):
+        """A clone for another sub-batch: network, scaler and tables shared; step word and packed buffers its own."""
+        import copy
+        c = copy.copy(self)
+        c._t = self._t.clone()
+        c._packed = PackedWeights()
+        c.last_picks = c.last_u = c.last_x0 = c.last_noise = c.last_x = c.last_energies = None
+        return c
+
+    def captured(self):
+        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: one kernel and the add on the step word)."""
+        return CapturedPolicy(self)
+
+    def load_reference_state_dict(self, sd):
+        """``EBMMLP.state_dict()`` of the reference: the network sits under ``mlp.``."""
+        self.model.load_state_dict({k[len("mlp."):]: v for k, v in sd.items() if k.startswith("mlp.")})
+
+    def use_ema(self, shadow_params):
+        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order."""
+        with torch.no_grad():
+            for p, s in zip(self.model.parameters(), shadow_params):
+                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
+
+    # ---- packed tables
+    def _pack_params(self):
+        return list(self.model.parameters())
+
+    def _pack(self):
+        """pack_resmlp_weights of the network; the same packer on the transposed square layers (``wT_blk``) and on the action columns of the input layer as a
+        16-row output tile (``wT_act``: row a = W_in[:, obs + a])."""
+        from types import SimpleNamespace as NS
+        lin_in, blocks, lin_out = self.model._parts()
+        out = pack_resmlp_weights(lin_in, blocks, lin_out)
+        tr = [tuple(NS(weight=l.weight.t(), bias=l.bias) for l in b) for b in blocks]
+        out["wT_blk"] = pack_resmlp_weights(lin_in, tr, lin_out)["w_blk"]
+        act = NS(weight=lin_in.weight[:, self.obs_dim:].t(), bias=torch.zeros(self.A, device=lin_in.weight.device), out_features=self.A)
+        out["wT_act"] = pack_resmlp_weights(lin_in, [], act)["w_out"]
+        return out
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        self._packed.invalidate()
+
+    def ensure_packed(self):
+        if next(self.model.parameters()).is_cuda:
+            self._packed.ensure(self._pack_params(), self._pack)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Warm-up and capture do not count as steps: the step word is put back."""
+        return self._t.clone()
+
+    def capture_restore(self, snap):
+        self._t.copy_(snap)
+
+    # ---- the chain
+    def fused_ok(self, s) -> bool:
+        lin_in, blocks, _ = self.model._parts()
+        w = lin_in.weight
+        return (s.is_cuda and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and len(blocks) <= 4 and lin_in.in_features <= 28
+                and self.S == 64 and os.environ.get("D3IL_POLICY_IBC_FUSED", "1") == "1")
+
+    def _banks(self, n, dev, need_host: bool):
+        """(x0, noise, u) as the torch path takes them / as the kernel is handed them: the given banks, or (``need_host``) the host form of the kernel's draws."""
+        f = lambda v, shape: torch.as_tensor(v, dtype=torch.float32).to(dev).reshape(shape).contiguous()
+        x0 = f(self.x0_in(n), (n, self.S, self.A)) if self.x0_in is not None else None
+        nz = f(self.noise_in(n), (self.K, n, self.S, self.A)) if self.noise_in is not None else None
+        u = f(self.u_in(n), (n,)) if self.u_in is not None else None
+        if need_host and (x0 is None or nz is None or u is None):
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("IBCPolicy: the torch chain draws its Philox numbers on the host and cannot be captured; the kernel draws on the device")
+            import numpy as np
+            t = int(self._t.item()) & 0xFFFFFFFF
+            if x0 is None:
+                uu = torch.as_tensor(ibc_start_uniforms(self.seed, self.env_offset, n, t, self.A, self.S)).to(dev)
+                x0 = self.lo + uu * (self.hi - self.lo)
+            if nz is None:
+                nz = f(np.stack([ibc_normals(self.seed, self.env_offset, n, t, k, self.A, self.S) for k in range(self.K)]) if self.K else np.zeros((0, n, self.S, self.A)),
+                       (self.K, n, self.S, self.A))
+            if u is None:
+                u = torch.as_tensor(ibc_pick_uniforms(self.seed, self.env_offset, n, t)).to(dev)
+        return x0, nz, u
+
+    def _chain_torch(self, s, x0=None, noise=None, u=None):
+        """Steps 1 - 3 of csrc/policy_ibc.h as torch ops in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too): returns
+        (actions, picks, final samples, energies)."""
+        n, S, A, dt = s.shape[0], self.S, self.A, s.dtype
+        c = lambda v: v.to(device=s.device, dtype=dt)
+        if x0 is None:
+            x0, noise, u = self._banks(n, s.device, True)
+        d = lambda v: v.to(device=s.device, dtype=torch.float64)
+        lo, hi, clip, coef = d(self.lo), d(self.hi), d(self.clip), d(self.coef)
+        x = d(x0).reshape(n * S, A)      # the samples are carried in f64 (the reference's f64 bounds promote them), the network runs in ``dt``
+        st = s.unsqueeze(1).expand(n, S, s.shape[1]).reshape(n * S, s.shape[1])
+        bad = ~torch.isfinite(s).all(dim=1) | ~torch.isfinite(x).reshape(n, -1).all(dim=1)
+        for k in range(self.K):
+            _, g = resmlp_energy_and_grad(self.model, torch.cat([st, x.to(dt)], dim=1), self.obs_dim)
+            raw = coef[k, 0] * g.double() + coef[k, 1] * (d(noise[k]).reshape(n * S, A) * self.noise_scale)
+            x = torch.minimum(torch.maximum(x - torch.minimum(torch.maximum(raw, -clip), clip), lo), hi)
+            bad |= ~(torch.isfinite(raw) & torch.isfinite(x)).reshape(n, -1).all(dim=1)
+        e, _ = resmlp_energy_and_grad(self.model, torch.cat([st, x.to(dt)], dim=1), self.obs_dim, grad=False)
+        e, x = e.reshape(n, S), x.reshape(n, S, A)
+        bad |= ~torch.isfinite(e).all(dim=1)
+        p = torch.exp(-(e - e.min(dim=1, keepdim=True).values))
+        cdf = torch.cumsum(p, dim=1)
+        picks = (cdf <= c(u).unsqueeze(1) * cdf[:, -1:]).sum(dim=1).clamp_max(S - 1)
+        y = (x[torch.arange(n, device=s.device), picks] * d(self.out_scale) + d(self.out_shift)).to(dt)
+        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        return y, torch.where(bad, torch.full_like(picks, -1), picks).to(torch.int32), x.to(dt), e
+
+    def _chain_kernel(self, s):
+        from . import capi
+        n, dev, S, A, K = s.shape[0], s.device, self.S, self.A, self.K
+        w = self._packed.current(self._pack_params(), self._pack)
+        x0, nz, u = self._banks(n, dev, False)
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+        y, picks, u_out = new(n, A), new(n, dtype=torch.int32), new(n)
+        rec = self.record
+        xf, en, x0o, nzo = (new(n, S, A), new(n, S), new(n, S, A), new(K, n, S, A)) if rec else (None, None, None, None)
+        ptr = lambda v: None if v is None else v.data_ptr()
+        lin_in, blocks, _ = self.model._parts()
+        assert s.is_contiguous() and self._t.device == dev
+        capi.check(capi.load().d3il_ibc_langevin_f32(s.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_out"].data_ptr(),
+                                                     w["b_out"].data_ptr(), w["wT_blk"].data_ptr(), w["wT_act"].data_ptr(), self.coef.data_ptr(), self.noise_scale, self.lo.data_ptr(),
+                                                     self.hi.data_ptr(), self.clip.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed, self.env_offset,
+                                                     self._t.data_ptr(), ptr(x0), ptr(nz), ptr(u), y.data_ptr(), picks.data_ptr(), ptr(xf), ptr(en), ptr(x0o), ptr(nzo), u_out.data_ptr(),
+                                                     n, self.obs_dim, A, lin_in.out_features, len(blocks), S, K, torch.cuda.current_stream(dev).cuda_stream))
+        self.last_picks, self.last_u, self.last_x, self.last_energies, self.last_x0, self.last_noise = picks, u_out, xf, en, x0o, nzo
+        return y
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "IBCPolicy: observation width %d, the energy network takes %d" % (s.shape[-1], self.obs_dim)
+        if self.fused_ok(s):
+            y = self._chain_kernel(s)
+        else:
+            if s.is_cuda and os.environ.get("D3IL_POLICY_IBC_FUSED", "1") == "1" and not getattr(self, "_warned", False):
+                import warnings
+                self._warned = True      # (once per policy; forks copy the flag)
+                warnings.warn("IBCPolicy: this network (hidden %d, %d blocks, %d inputs, %d samples) is not one the chain kernel is built for; every call runs the torch chain "
+                              "with its Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                              % (self.model._parts()[0].out_features, len(self.model._parts()[1]), self.model._parts()[0].in_features, self.S))
+            x0, nz, u = self._banks(s.shape[0], s.device, True)
+            y, self.last_picks, self.last_x, self.last_energies = self._chain_torch(s, x0, nz, u)
+            self.last_u, self.last_x0, self.last_noise = u, x0, nz
+        self._t.add_(1)
+        return y
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, action_scale: float = 0.002, policy_seed: int = 0,
+               weight_gain: float = 1.0, **kw):
+        """A policy of the reference's shape with fixed random weights (there are no checkpoints offline) and the shipped sampler settings of
+        configs/agents/ibc_agent.yaml (64 samples, 10 + 10 iterations, step sizes 0.5 / 0.0493 -> 1e-5 with power 2, then 1e-5; noise scale 0.5; clip 0.1): torch's
+        default layer initialisation times ``weight_gain``, unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-1.5."""
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            net = ResidualMLP(obs_dim + action_dim, hidden_dim, 2 * n_blocks, 1)
+        with torch.no_grad():
+            for p in net.parameters():
+                p.mul_(weight_gain)
+                p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
+        return cls(net.to(device), sc, ibc_step_sizes(10, 0.5, 0.0493, 1e-5, 2.0, 1e-5, True), noise_scale=0.5, delta_action_clip=0.1, seed=policy_seed, **kw)

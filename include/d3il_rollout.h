@@ -238,6 +238,25 @@ int d3il_ddpm_gpt_step_f32(const float* hk, const float* ln_weight, const float*
                            const float* bias_pos, const float* temb, const float* sched, const float* lo, const float* hi, const float* scale, const float* shift,
                            const int64_t* len, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* noise_in, float* x, float* xbuf, float* actions,
                            int32_t* bad, float* noise_out, long n_env, int C, int A, int W, int T, int k, void* stream);
+/* The whole inference of the batched Implicit-BC policy (policies.IBCPolicy; ibc_agent.py:248-286, samplers/langevin_mcmc.py:129-163,236-286, ebms.py:21-51) in one
+ * launch, f32 throughout: per environment S = 64 samples, K Langevin iterations on the energy network E([state | x]) (ResidualMLPNetwork, Mish, one output) with the
+ * analytic gradient, then a categorical draw from softmax(-E) of the final samples.  x_a starts at x0_in[n][s][a] or lo_a + u (hi_a - lo_a); iteration k:
+ * g = dE/dx, d_a = clamp(coef[k][0] g_a + coef[k][1] noise_scale z_a, -clip_a, clip_a), x_a = clamp(x_a - d_a, lo_a, hi_a) with z = noise_in[k][n][s] or Box-Muller
+ * normals; then p_s = exp(-(E_s - min E)), c = inclusive prefix sums, pick = min(#{s : c_s <= u c_63}, 63) with u = u_in[n] or a Philox uniform, and
+ * actions[n][a] = x[pick][a] scale_a + shift_a.  Random numbers: Philox4x32-10, key = seed, counter = (env_offset + n, *t_device, 0x49420000 | kind << 14 | k << 8 |
+ * s << 2 | q) with kind 0 = start point, 1 = noise, 2 = draw; component a = 4 q + m takes word m; uniforms (r >> 8) 2^-24, normals as d3il_ddpm_gpt_step_f32.
+ * state [n_env][obs_dim] (scaled); w_in .. b_out: policies.pack_resmlp_weights of the network (input row = [state | action]); wT_blocks: the same packing of the
+ * TRANSPOSED square layers, in the same order; wT_in_act: the action columns of the input layer as a 16-row output-style tile (row a = W_in[:, obs_dim + a]);
+ * coef [K][2] = (f32(step / 2), f32(step)) (may be NULL when K = 0); lo / hi (scaled space) / clip / scale / shift [A]; t_device: DEVICE u32.  x0_in [n_env][S][A], noise_in [K][n_env][S][A],
+ * u_in [n_env] and x_final [n_env][S][A], energies [n_env][S], x0_out, noise_out, u_out (what was used) may be NULL; picks i32 [n_env].  K = 0: the energies and the
+ * pick of the start points.  An environment with a NaN / Inf in its state row, a start point, a gradient, an iterate or a final energy gets picks = -1 and NaN in
+ * every action component; no other environment changes.  Built for hidden 128 / 256, 0 <= n_blocks <= 4, obs_dim + A <= 28, 1 <= A <= 8, S = 64, 0 <= K <= 63:
+ * D3IL_EUNSUPPORTED otherwise, answered before any launch.  Packed arrays 16-byte aligned. */
+int d3il_ibc_langevin_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out,
+                          const float* wT_blocks, const float* wT_in_act, const float* coef, float noise_scale, const float* lo, const float* hi, const float* clip,
+                          const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* x0_in, const float* noise_in,
+                          const float* u_in, float* actions, int32_t* picks, float* x_final, float* energies, float* x0_out, float* noise_out, float* u_out, long n_env,
+                          int obs_dim, int A, int hidden, int n_blocks, int S, int K, void* stream);
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
