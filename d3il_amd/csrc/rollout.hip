@@ -608,8 +608,17 @@ __global__ __launch_bounds__(256) void k_linear120_f32(const float* __restrict__
 // The first layer (x | time embedding | state = 26 -> 28 inputs, 7 steps per tile) and the output layer (2 of 16 outputs; every wave computes it for the DDPM
 // update of its copy of x) read their small packed matrices from L2.  The time embedding of step i is the same for every row (temb [T][8], evaluated once by the
 // caller); the noise of all T + 1 draws comes as one tensor.
+// Non-finite operands: the clip of the x0 prediction and the final clamp are fminf(fmaxf(..)), which return their bound for a NaN - a NaN observation would come out
+// as a finite in-bounds action where the torch chain (torch.clamp) gives NaN.  So the row's state, its T + 1 noise draws and its final x are tested on their bit
+// patterns (dd_nonfinite: a float test folds away under -ffinite-math-only) and a hit row gets 0x7FC00000 in both components by an integer select; the row's
+// arithmetic still runs, rows are independent, no other row changes and finite rows come out bit for bit as without the test.
 constexpr int DD_H = 256, DD_TILE_F4 = 16 * 64, DD_LAYER_F4 = 16 * DD_TILE_F4;      // float4 per packed output tile (16 KB), per packed layer
 constexpr int DD_NW = 8, DD_TPW = 16 / DD_NW;      // waves per workgroup (16 rows), output tiles per wave: eight waves of two tiles - two waves per SIMD hide each other's weight loads
+__device__ __forceinline__ unsigned dd_nonfinite(float x) {      // exponent field all ones (NaN, +-Inf), read from the bits
+  unsigned b = __float_as_uint(x);
+  asm("" : "+v"(b));
+  return (b & 0x7F800000u) == 0x7F800000u ? 1u : 0u;
+}
 __device__ __forceinline__ float dd_mish(float x) {      // x tanh(softplus(x)), softplus with torch's threshold 20; tanh(log(1 + n)) = (n^2 + 2 n) / (n^2 + 2 n + 2), n = e^x
   if (x > 20.f) return x;
   const float n = expf(x), p = n * (n + 2.f);
@@ -656,6 +665,10 @@ __global__ __launch_bounds__(64 * DD_NW) void k_ddpm_mlp_f32(const float* __rest
   for (int s2 = 0; s2 < 7; s2++) { const int f = 4 * s2 + g; st_k[s2] = (f >= 10 && f < 10 + SD) ? state[rr * SD + f - 10] : 0.f; }
   const float lo0 = bounds[0], lo1 = bounds[1], hi0 = bounds[2], hi1 = bounds[3];
   float x0 = noise[rr * 2], x1 = noise[rr * 2 + 1];
+  unsigned bad = dd_nonfinite(x0) | dd_nonfinite(x1);
+#pragma unroll
+  for (int s2 = 0; s2 < 7; s2++) bad |= dd_nonfinite(st_k[s2]);
+  bad |= (unsigned)__shfl_xor((int)bad, 16); bad |= (unsigned)__shfl_xor((int)bad, 32);      // the four lane groups of row j hold its features 4 s + g
   const mlp_f4* w_in4 = (const mlp_f4*)w_in;
   const mlp_f4* w_out4 = (const mlp_f4*)w_out;
   int buf = 0;
@@ -708,10 +721,16 @@ __global__ __launch_bounds__(64 * DD_NW) void k_ddpm_mlp_f32(const float* __rest
     const float sra = sched[i * 5], srm1 = sched[i * 5 + 1], c1 = sched[i * 5 + 2], c2 = sched[i * 5 + 3], sig = sched[i * 5 + 4];
     const float p0 = fminf(fmaxf(sra * x0 - srm1 * e0, lo0), hi0), p1 = fminf(fmaxf(sra * x1 - srm1 * e1, lo1), hi1);      // clipped x0 prediction
     const float z0 = noise[((long)(step + 1) * n + rr) * 2], z1 = noise[((long)(step + 1) * n + rr) * 2 + 1];
+    bad |= dd_nonfinite(z0) | dd_nonfinite(z1);
     x0 = (c1 * p0 + c2 * x0) + sig * z0;
     x1 = (c1 * p1 + c2 * x1) + sig * z1;
   }
-  if (live && w == 0 && g == 0) { out[row * 2] = fminf(fmaxf(x0, lo0), hi0); out[row * 2 + 1] = fminf(fmaxf(x1, lo1), hi1); }
+  if (live && w == 0 && g == 0) {
+    bad |= dd_nonfinite(x0) | dd_nonfinite(x1);
+    const unsigned y0 = __float_as_uint(fminf(fmaxf(x0, lo0), hi0)), y1 = __float_as_uint(fminf(fmaxf(x1, lo1), hi1));
+    ((unsigned*)out)[row * 2] = bad ? 0x7FC00000u : y0;
+    ((unsigned*)out)[row * 2 + 1] = bad ? 0x7FC00000u : y1;
+  }
 }
 // The reference's ResidualMLPNetwork (agents/models/common/mlp.py:114-182: Linear, n pre-activation residual blocks x + l2(mish(l1(mish(x)))), Linear - the network of
 // the BC agent, bc_agent.py:240-271, and the denoiser above without its sampling loop) in one launch, same operand scheme as k_ddpm_mlp_f32: 16 rows per
@@ -878,6 +897,18 @@ __global__ __launch_bounds__(256) void k_attention_causal_f32(const float* __res
     } else {
 #pragma unroll
       for (int d = 0; d < 32; d++) if (d < D) o[d] = acc[d] * inv;
+    }
+  }
+  // A NaN / Inf score of a later key makes l NaN by itself (exp of NaN, of Inf - Inf).  Query 0 has one key and never exponentiates its score: a non-finite
+  // score 0 hands out v_0 above, where the masked softmax of that single score is NaN.  Its lane (pair 0) forms that score once more, tests the bits and
+  // writes NaN over the row - behind the loop and apart from it, so that the arithmetic above compiles as it did (the f32 sums of finite rows keep their bits)
+  if (p == 0) {
+    float s0 = 0.0f;
+    for (int d = 0; d < D; d++) s0 += (base[d] * scale) * base[C + d];
+    if (dd_nonfinite(s0)) {
+      float* o = out + (b * T) * (long)C + h * D;      // (float stores, as the ones above: stores of another type could be ordered before them)
+      const float qnan = __uint_as_float(0x7FC00000u);
+      for (int d = 0; d < D; d++) o[d] = qnan;
     }
   }
 }

@@ -693,7 +693,8 @@ def pack_resmlp_weights(lin_in, blocks, lin_out) -> dict:
 
 class FusedResMLP:
     """The device path of a ResidualMLPNetwork (csrc/rollout.hip k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
-    ``parts`` = (lin_in, [(l1, l2), ..], lin_out) of the module it serves (no reference to the module is kept)."""
+    ``parts`` = (lin_in, [(l1, l2), ..], lin_out) of the module it serves (no reference to the module is kept).  Non-finite input: a row of x with a NaN / Inf comes
+    out NaN in every column, as from torch's layers, and no other row changes (tests/test_gpu_policy_f32_edges.py)."""
 
     def __init__(self):
         self._packed = PackedWeights()
@@ -831,7 +832,9 @@ def ddpm_schedule(betas: torch.Tensor) -> dict:
 class DDPMPolicy:
     """DiffusionAgent.predict (ddpm_agent.py:213-274) with the Diffusion sampler (gc_diffusion.py:101-216: epsilon prediction, clipped
     x0, posterior mean / variance, n_timesteps ancestral steps, final clamp) on a batch.  ``noise_fn(shape)`` supplies the Gaussian
-    noise (default torch.randn on the policy's device); window_size > 1 keeps the observation history per lane."""
+    noise (default torch.randn on the policy's device); window_size > 1 keeps the observation history per lane.  Non-finite input: an observation row with a
+    NaN / Inf (or such a noise draw) gives NaN in both action components of that row on the fused chain as on the torch chain (torch.clamp keeps a NaN; the
+    kernel tests the bit patterns, its own clips would return a bound), and no other row changes - the environment then raises D3IL_FLAG_SOLVER_FAIL in that lane."""
 
     def __init__(self, model: DiffusionMLP, scaler: Scaler, n_timesteps: int, window_size: int = 1, n_envs: int | None = None, noise_fn=None):
         self.model, self.scaler, self.T, self.W = model.eval(), scaler, int(n_timesteps), int(window_size)

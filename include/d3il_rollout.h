@@ -175,12 +175,14 @@ int d3il_auto_reset(d3il_handle h, int64_t* episode_counts_device, void* stream)
 /* Policy-side helper (batched policy adapters): causal self-attention of the reference's DiffusionGPT
  * (agents/models/beso/agents/diffusion_agents/k_diffusion/score_gpts.py:15-80) for its short token sequences, fused: qkv f32
  * [B * T][3 H D] (query | key | value per token), out f32 [B * T][H D]; softmax over the keys j <= i, scores scaled by
- * 1 / sqrt(D).  Device pointers, T <= 32, D <= 32; needs no handle. */
+ * 1 / sqrt(D).  Device pointers, T <= 32, D <= 32; needs no handle.  (D a multiple of 4 and both pointers 16-byte aligned: 16-byte loads; anything else takes the
+ * scalar instantiation, same sums in the same order.)  A NaN in a query, key or value makes NaN exactly the outputs whose masked softmax is NaN - the queries
+ * at and behind that key of that (sequence, head), query 0 with its single key included; no other (sequence, head) changes. */
 int d3il_attention_causal_f32(const float* qkv, float* out, int B, int T, int H, int D, void* stream);
 
 /* Policy-side helper: LayerNorm over the last dimension (torch.nn.LayerNorm semantics) for rows of 4 .. 128 floats (a multiple of 4):
  * the transformer of the reference's BESO policy normalises [B * T][120] activations 13 times per denoising call
- * (score_gpts.py:83-115, :353).  x, y f32 [rows][C]; 16-byte aligned device pointers. */
+ * (score_gpts.py:83-115, :353).  x, y f32 [rows][C]; 16-byte aligned device pointers.  A NaN / Inf in a row makes that row NaN and no other. */
 int d3il_layernorm_f32(const float* x, const float* weight, const float* bias, float* y, long rows, int C, float eps, void* stream);
 /* Fused transformer MLP of the batched DiffusionGPT (score_gpts.py:83-115: x + fc2(GELU(fc1(h))), h = ln2(x)) on the f32 matrix cores:
  * out[rows][C] = x + b2 + W2 GELU(W1 h + b1).  w_packed = both weight matrices in the per-chunk LDS order of the kernel (d3il_amd/policies.py
@@ -279,7 +281,9 @@ int d3il_f16x3_set_guard(long long* counts_device);
  *   state [rows][state_dim] (scaled observation), noise [n_timesteps + 1][rows][2] (draw 0 = x_T, draw 1 + k = the k-th step's noise), temb [n_timesteps][8] (the time
  *   embedding of step i, row i), sched [n_timesteps][5] = sqrt(1 / acp), sqrt(1 / acp - 1), posterior mean coefficients 1 and 2, sigma (0 for step 0), bounds = min[2] max[2],
  *   out [rows][2] (scaled action); weights in the kernel's tile order (d3il_amd/policies.py pack_ddpm_weights): w_in [16][64][8], w_blocks [2 n_blocks][16][16][64][4],
- *   w_out [16][64][4]; b_in [256], b_blocks [2 n_blocks][256], b_out [2].  Built for hidden 256, action 2, t_dim 8, state_dim <= 18 (D3IL_EUNSUPPORTED otherwise). */
+ *   w_out [16][64][4]; b_in [256], b_blocks [2 n_blocks][256], b_out [2].  Built for hidden 256, action 2, t_dim 8, state_dim <= 18 (D3IL_EUNSUPPORTED otherwise).
+ * A row with a NaN / Inf in its state, in one of its n_timesteps + 1 noise draws or in its final x gets NaN (0x7FC00000) in both output components - the clips
+ * alone would return a bound, a finite in-bounds action; no other row changes, and finite rows are bit for bit what they are without the test. */
 int d3il_ddpm_mlp_f32(const float* state, const float* noise, const float* temb, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks,
                       const float* w_out, const float* b_out, const float* sched, const float* bounds, float* out, long rows, int state_dim, int n_timesteps, int hidden,
                       int n_blocks, void* stream);
@@ -287,7 +291,9 @@ int d3il_ddpm_mlp_f32(const float* state, const float* noise, const float* temb,
 /* out[rows][out_dim] = the reference's ResidualMLPNetwork (agents/models/common/mlp.py:114-182: Linear, n_blocks pre-activation residual blocks with Mish, Linear; the
  * network of BC_Agent.predict, bc_agent.py:240-271) of x [rows][in_dim] in one launch on the f32 matrix cores.  Weights in the kernel's tile order
  * (d3il_amd/policies.py pack_resmlp_weights; NT = hidden / 16): w_in [NT][64][8], w_blocks [2 n_blocks][NT][NT][64][4], w_out [NT][64][4]; b_in [hidden],
- * b_blocks [2 n_blocks][hidden], b_out [16] (padded).  Built for hidden 128 / 256, in_dim <= 28, out_dim <= 16 (D3IL_EUNSUPPORTED otherwise). */
+ * b_blocks [2 n_blocks][hidden], b_out [16] (padded).  Built for hidden 128 / 256, in_dim <= 28, out_dim <= 16 (D3IL_EUNSUPPORTED otherwise).
+ * Nothing clips here, so a NaN / Inf in a row of x travels through the products by itself: that row comes out NaN in every column (an Inf meets weights of both
+ * signs in the first sum over a hidden layer), no other row changes - rows are independent, dead tail lanes re-read the last row and store nothing. */
 int d3il_resmlp_f32(const float* x, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out, float* out, long rows,
                     int in_dim, int hidden, int n_blocks, int out_dim, void* stream);
 
