@@ -28,6 +28,7 @@ constexpr int WAVE = 64;
 #include "policy_bet.h"
 #include "policy_ddpm_gpt.h"
 #include "policy_ibc.h"
+#include "policy_act.h"
 
 namespace d3il {
 
@@ -1788,6 +1789,26 @@ int d3il_ibc_langevin_f32(const float* state, const float* w_in, const float* b_
   const dim3 grid((unsigned)n_env), block(64 * IBC_NW);
   if (hidden == 128) hipLaunchKernelGGL(k_ibc_langevin<128>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_ibc_langevin<256>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_act_chunk_f32(const float* state, const float* w_in, const float* tab, const float* enc_w, const float* enc_v, const float* dec_w, const float* dec_v,
+                       const float* head_w, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset,
+                       const uint32_t* t_device, const float* latent_in, int32_t* counter, float* chunk, float* actions, float* latent_out, long n_env, int obs_dim, int A,
+                       int T, int width, int n_head, int latent, int n_enc, int n_dec, void* stream) {
+  if (width != ACT_C || n_head != ACT_NH || latent != ACT_LAT || obs_dim < 0 || obs_dim > ACT_OBSMAX || A < 1 || A > ACT_AMAX || T < 1 || T > ACT_TMAX || n_enc < 1 ||
+      n_enc > ACT_MAXENC || n_dec < 1 || n_dec > ACT_MAXDEC || n_env > 0x7FFFFFFFL)
+    return fail(D3IL_EUNSUPPORTED, "d3il_act_chunk_f32: built for width 64 in 4 heads, latent 32, obs_dim <= 32, 1 .. 8 action components, chunks of 1 .. 8, 1 .. 4 encoder and 1 .. 8 decoder layers");
+  if (!state || !w_in || !tab || !enc_w || !enc_v || !dec_w || !dec_v || !head_w || !lo || !hi || !scale || !shift || !t_device || !counter || !chunk || !actions)
+    return fail(D3IL_EINVAL, "d3il_act_chunk_f32: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_act_chunk_f32: negative environment count");
+  if (((uintptr_t)w_in | (uintptr_t)tab | (uintptr_t)enc_w | (uintptr_t)enc_v | (uintptr_t)dec_w | (uintptr_t)dec_v | (uintptr_t)head_w) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_act_chunk_f32: the packed weights and tables must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  ActArgs a{state, w_in, tab, enc_w, enc_v, dec_w, dec_v, head_w, lo, hi, scale, shift, t_device, latent_in, counter, chunk, actions, latent_out,
+            (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, T, n_enc, n_dec};
+  // one workgroup of four waves per 16 environments
+  hipLaunchKernelGGL(k_act_chunk, dim3((unsigned)((n_env + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

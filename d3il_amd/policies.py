@@ -2087,3 +2087,432 @@ class IBCPolicy:
                 p.requires_grad_(False)
         sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
         return cls(net.to(device), sc, ibc_step_sizes(10, 0.5, 0.0493, 1e-5, 2.0, 1e-5, True), noise_scale=0.5, delta_action_clip=0.1, seed=policy_seed, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ VAE-ACT: encoder-decoder transformer that emits action chunks
+ACT_TAG = 0x41430000          # fourth Philox counter word of the chunk kernel, or-ed with q < 8 (csrc/policy_act.h; never 0, BET_TAG, a DDPM_GPT_TAG or an IBC_TAG word)
+
+
+def act_latent_words(seed: int, env_offset: int, n: int, t: int):
+    """The Philox words of the chunk kernel: uint32 [n, 8 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t, ACT_TAG | q))."""
+    import numpy as np
+    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1)
+    q = np.arange(8, dtype=np.uint64).reshape(1, 8)
+    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, np.uint64(ACT_TAG) | q), axis=-1)
+
+
+def act_latent_uniforms(seed: int, env_offset: int, n: int, t: int):
+    """The kernel's latent of environments 0 .. n-1 at step word t: float32 [n, 32] in [0, 1 - 2^-24], component 4 q + m = 24 bits of word m of call q
+    (the reference draws torch.rand: uniform, not normal)."""
+    import numpy as np
+    r = act_latent_words(seed, env_offset, n, t).reshape(n, 32)
+    return ((r >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+
+
+def act_reference_shapes(obs_dim: int, action_dim: int, T: int, C: int = 64, enc_layers: int = 2, dec_layers: int = 4, latent_dim: int = 32, action_enc_layers: int = 2) -> dict:
+    """Name -> shape of every parameter of the reference's ActVAE (act_vae.py:325-376; the mask buffers are not parameters and are left out), the training-only
+    ones included: what ``act_synthetic_state`` is drawn over, so that the tests rebuild the golden generator's weights without storing them."""
+    out = {"state_encoder.weight": (C, obs_dim), "action_embed.weight": (C, action_dim), "latent_out_proj.weight": (C, latent_dim), "action_head.weight": (action_dim, C),
+           "action_head.bias": (action_dim,), "latent_proj.weight": (2 * latent_dim, C), "latent_proj.bias": (2 * latent_dim,), "query_embed.weight": (T, C),
+           "cls_embed.weight": (1, C), "pos_emb": (1, T, C), "act_pos_emb": (1, T + 1, C)}
+    for stack, n, cross in (("encoder", enc_layers, False), ("decoder", dec_layers, True), ("action_encoder", action_enc_layers, False)):
+        out[stack + ".ln.weight"] = (C,)
+        for i in range(n):
+            p = "%s.blocks.%d." % (stack, i)
+            out[p + "ln1.weight"] = out[p + "ln2.weight"] = (C,)
+            for l in ("key", "query", "value", "proj") + (("cross_key", "cross_query", "cross_value") if cross else ()):
+                out[p + "attn.%s.weight" % l], out[p + "attn.%s.bias" % l] = (C, C), (C,)
+            out[p + "mlp.0.weight"], out[p + "mlp.0.bias"], out[p + "mlp.2.weight"], out[p + "mlp.2.bias"] = (4 * C, C), (4 * C,), (C, 4 * C), (C,)
+    return out
+
+
+def act_synthetic_state(shapes: dict, seed: int) -> dict:
+    """Fixed-seed weights of trained-like magnitudes for an ActVAE-shaped state dict (there are no checkpoints offline; the reference's initialisation, std 0.02
+    and zero biases, makes the network nearly linear): one np.random.RandomState(seed), drawn in sorted key order - matrices N(0, 1) 1.2 / sqrt(fan-in) (the action head 2.4: scaled actions of order 2), LayerNorm
+    weights 1 + 0.15 N, biases 0.2 N, embeddings and position tables 0.4 N, all rounded to f32.  The golden generator and the tests rebuild the same arrays."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    out = {}
+    for k in sorted(shapes):
+        shape = tuple(shapes[k])
+        z = rs.standard_normal(shape)
+        leaf = k.split(".")
+        if leaf[-1] == "weight" and leaf[-2] in ("ln", "ln1", "ln2"):
+            v = 1.0 + 0.15 * z
+        elif leaf[-1] == "bias":
+            v = 0.2 * z
+        elif leaf[-1] == "weight" and len(shape) == 2 and leaf[-2] not in ("query_embed", "cls_embed"):
+            v = z * ((2.4 if leaf[-2] == "action_head" else 1.2) / math.sqrt(shape[1]))
+        else:
+            v = 0.4 * z
+        out[k] = v.astype(np.float32)
+    return out
+
+
+class _ActLayerNorm(nn.Module):      # act_vae.py:26-35 with bias=False
+    def __init__(self, ndim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(ndim))
+
+    def forward(self, x):
+        return F.layer_norm(x, self.weight.shape, self.weight, None, 1e-5)
+
+
+class _ActAttention(nn.Module):      # act_vae.py:38-102 (SelfAttention) and 105-167 (CausalSelfCrossAttention), dropout off
+    def __init__(self, n_embd, n_heads, block_size, cross):
+        super().__init__()
+        self.key, self.query, self.value = nn.Linear(n_embd, n_embd), nn.Linear(n_embd, n_embd), nn.Linear(n_embd, n_embd)
+        if cross:
+            self.cross_key, self.cross_query, self.cross_value = nn.Linear(n_embd, n_embd), nn.Linear(n_embd, n_embd), nn.Linear(n_embd, n_embd)
+        self.proj = nn.Linear(n_embd, n_embd)
+        self.register_buffer("mask", torch.tril(torch.ones(block_size, block_size)).view(1, 1, block_size, block_size), persistent=False)
+        self.n_head = n_heads
+
+    def forward(self, x, cross_input=None):
+        B, T, C = x.shape
+        hd = C // self.n_head
+        sp = lambda v: v.view(B, -1, self.n_head, hd).transpose(1, 2)
+        q, k, v = sp(self.query(x)), sp(self.key(x)), sp(self.value(x))
+        att = (q @ k.transpose(-2, -1)) * (1.0 / math.sqrt(hd))
+        att = att.masked_fill(self.mask[:, :, :T, :T] == 0, float("-inf"))      # (a 1 x 1 slice broadcasts: a block_size of 1 masks nothing on two tokens)
+        y = F.softmax(att, dim=-1) @ v
+        if cross_input is not None:
+            kc, vc, qc = sp(self.cross_key(cross_input)), sp(self.cross_value(cross_input)), sp(self.cross_query(x))
+            y = y + F.softmax((qc @ kc.transpose(-2, -1)) * (1.0 / math.sqrt(hd)), dim=-1) @ vc
+        return self.proj(y.transpose(1, 2).contiguous().view(B, T, C))
+
+
+class _ActBlock(nn.Module):          # act_vae.py:170-239
+    def __init__(self, n_embd, n_heads, block_size, cross):
+        super().__init__()
+        self.ln1, self.ln2 = _ActLayerNorm(n_embd), _ActLayerNorm(n_embd)
+        self.attn = _ActAttention(n_embd, n_heads, block_size, cross)
+        self.mlp = nn.Sequential(nn.Linear(n_embd, 4 * n_embd), nn.GELU(), nn.Linear(4 * n_embd, n_embd))
+
+    def forward(self, x, cond=None):
+        x = x + self.attn(self.ln1(x), cond)
+        return x + self.mlp(self.ln2(x))
+
+
+class _ActStack(nn.Module):          # act_vae.py:242-305
+    def __init__(self, n_embd, n_heads, n_layers, block_size, cross):
+        super().__init__()
+        self.blocks = nn.Sequential(*[_ActBlock(n_embd, n_heads, block_size, cross) for _ in range(n_layers)])
+        self.ln = _ActLayerNorm(n_embd)
+
+    def forward(self, x, cond=None):
+        for b in self.blocks:
+            x = b(x, cond)
+        return self.ln(x)
+
+
+class ActNet(nn.Module):
+    """The inference path of the reference's ActVAE (act_vae.py:389-445 with action = None, goal = None) under the reference's parameter names; the training-only
+    parts (action_encoder, action_embed, latent_proj, cls_embed, act_pos_emb) are not held.  ``forward(state [N, obs], latent [N, L]) -> [N, T, A]``; the latent is
+    an argument (the reference draws torch.rand inside)."""
+
+    def __init__(self, state_dim, action_dim, act_seq_size, hidden_dim=64, n_heads=4, enc_layers=2, dec_layers=4, latent_dim=32):
+        super().__init__()
+        self.encoder = _ActStack(hidden_dim, n_heads, enc_layers, act_seq_size, False)
+        self.decoder = _ActStack(hidden_dim, n_heads, dec_layers, act_seq_size, True)
+        self.state_encoder = nn.Linear(state_dim, hidden_dim, bias=False)
+        self.latent_out_proj = nn.Linear(latent_dim, hidden_dim, bias=False)
+        self.action_head = nn.Linear(hidden_dim, action_dim)
+        self.query_embed = nn.Embedding(act_seq_size, hidden_dim)
+        self.pos_emb = nn.Parameter(torch.zeros(1, act_seq_size, hidden_dim))
+        self.T, self.A, self.obs_dim, self.C, self.n_head, self.latent_dim = act_seq_size, action_dim, state_dim, hidden_dim, n_heads, latent_dim
+
+    def forward(self, state, latent):
+        n = state.shape[0]
+        x = torch.stack([self.state_encoder(state), self.latent_out_proj(latent)], dim=1)
+        x = x + self.pos_emb[:, :2]      # (T = 1: one row, broadcast onto both tokens)
+        enc = self.encoder(x)
+        dec = self.decoder(self.query_embed.weight.unsqueeze(0).expand(n, -1, -1), enc)
+        return self.action_head(dec)
+
+
+def pack_tiles(W: torch.Tensor) -> torch.Tensor:
+    """A weight matrix [out, in] in the A-operand fragment order of the f32 matrix instruction, rows and columns padded to multiples of 16 with zeros:
+    [To][t][lane (g, i)][r] = W[16 To + i][16 t + 4 g + r] (the order of pack_resmlp_weights' square layers)."""
+    dev = W.device
+    R, Cc = -(-W.shape[0] // 16) * 16, -(-W.shape[1] // 16) * 16
+    Wp = torch.zeros(R, Cc, device=dev, dtype=torch.float32)
+    Wp[:W.shape[0], :W.shape[1]] = W.detach()
+    ar = lambda k: torch.arange(k, device=dev)
+    To, t, g, i, r = ar(R // 16)[:, None, None, None, None], ar(Cc // 16)[None, :, None, None, None], ar(4)[None, None, :, None, None], ar(16)[None, None, None, :, None], ar(4)[None, None, None, None, :]
+    return Wp[16 * To + i, 16 * t + 4 * g + r].reshape(R // 16, Cc // 16, 64, 4).contiguous()
+
+
+def pack_act_weights(net: ActNet) -> dict:
+    """ActNet in the operand order of csrc/policy_act.h (width 64, latent 32, obs <= 32, T <= 8, A <= 8): every matrix through ``pack_tiles``;
+    w_in = [state_encoder (columns padded to 32) | latent_out_proj]; per encoder layer enc_w = [query key value proj fc1 fc2], enc_v = [ln1 ln2 b_query b_key b_value
+    b_proj b_fc1 b_fc2]; per decoder layer dec_w = [query key value cross_query cross_key cross_value proj fc1 fc2], dec_v alike; head_w = action_head (rows padded to
+    16); tab = [pos (2 rows: pos_emb[0, :2], for T = 1 row 0 twice) | query_embed (padded to 8 rows) | encoder.ln | decoder.ln | head bias (padded to 16)]."""
+    assert net.C == 64 and net.latent_dim == 32 and net.obs_dim <= 32 and net.T <= 8 and net.A <= 8
+    flat = lambda *xs: torch.cat([x.detach().to(torch.float32).reshape(-1) for x in xs])
+    dev = net.pos_emb.device
+    se = torch.zeros(64, 32, device=dev)
+    se[:, :net.obs_dim] = net.state_encoder.weight.detach()
+    pos = net.pos_emb.detach()[0, :2].expand(2, 64)
+    qe = torch.zeros(8, 64, device=dev)
+    qe[:net.T] = net.query_embed.weight.detach()
+    hb = torch.zeros(16, device=dev)
+    hb[:net.A] = net.action_head.bias.detach()
+    enc_w, enc_v, dec_w, dec_v = [], [], [], []
+    for b in net.encoder.blocks:
+        a = b.attn
+        enc_w.append(flat(*[pack_tiles(l.weight) for l in (a.query, a.key, a.value, a.proj, b.mlp[0], b.mlp[2])]))
+        enc_v.append(flat(b.ln1.weight, b.ln2.weight, a.query.bias, a.key.bias, a.value.bias, a.proj.bias, b.mlp[0].bias, b.mlp[2].bias))
+    for b in net.decoder.blocks:
+        a = b.attn
+        dec_w.append(flat(*[pack_tiles(l.weight) for l in (a.query, a.key, a.value, a.cross_query, a.cross_key, a.cross_value, a.proj, b.mlp[0], b.mlp[2])]))
+        dec_v.append(flat(b.ln1.weight, b.ln2.weight, a.query.bias, a.key.bias, a.value.bias, a.cross_query.bias, a.cross_key.bias, a.cross_value.bias, a.proj.bias, b.mlp[0].bias, b.mlp[2].bias))
+    return {"w_in": flat(pack_tiles(se), pack_tiles(net.latent_out_proj.weight)), "tab": flat(pos, qe, net.encoder.ln.weight, net.decoder.ln.weight, hb),
+            "enc_w": torch.stack(enc_w), "enc_v": torch.stack(enc_v), "dec_w": torch.stack(dec_w), "dec_v": torch.stack(dec_v), "head_w": flat(pack_tiles(net.action_head.weight))}
+
+
+class ACTPolicy:
+    """ActAgent.predict without goals (agents/act_agent.py:207-239) around ActVAE.forward without actions (act_vae.py:389-445), on a batch: scale the observation;
+    a lane whose ``counter`` equals the chunk length T is due and computes a new chunk of T actions from its CURRENT observation and a fresh uniform latent -
+    clamped to the scaler's bounds in the scaled space, inverse-scaled, stored -; every lane then emits chunk[counter] and counts on.  ``reset()`` makes all lanes
+    due, ``begin_episodes(mask)`` the masked ones (an environment that restarts mid-chunk falls out of phase with its neighbours: the state is per lane).
+
+    On a HIP device the whole call is ONE kernel (csrc/policy_act.h through d3il_act_chunk_f32: width 64, 4 heads, latent 32, obs <= 32, A <= 8, T <= 8, at most
+    4 encoder and 8 decoder layers), then a device-side add on the step word; a call in which no lane of a 16-lane tile is due costs that tile only the emit.  On the
+    CPU, for other shapes and with D3IL_POLICY_ACT_FUSED=0 the same arithmetic runs as torch ops (``_chunk_torch``) on the same Philox stream computed on the
+    host - that path cannot be captured.  Random numbers: Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word, ACT_TAG | q);
+    ``latent_in(n) -> [n, 32]`` replaces the draw when given (golden replay, tests).  A NaN / Inf in a due lane's state row or head outputs gives that lane a NaN
+    chunk."""
+
+    def __init__(self, model: ActNet, scaler: Scaler, seed: int = 0, n_envs: int | None = None, latent_in=None):
+        self.model, self.scaler = model.eval(), scaler
+        dev = scaler.x_mean.device
+        self.device = dev
+        self.T, self.A, self.obs_dim = int(model.T), int(model.A), int(model.obs_dim)
+        assert scaler.y_bounds is not None and tuple(scaler.y_bounds.shape) == (2, self.A), "ACTPolicy clamps to the scaler's y_bounds"
+        f = lambda a: a.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
+        self.seed, self.env_offset, self.n_envs = int(seed), 0, n_envs
+        self.latent_in = latent_in
+        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self._packed = PackedWeights()
+        self.counter = self.chunk = self.last_latent = None          # per-lane state: i32 [N], f32 [N, T, A] (clamped, inverse-scaled), the latent of the lane's chunk [N, 32]
+        self.record = False           # also keep a copy of the chunk table after every call (last_chunk)
+        self.last_chunk = None
+        if n_envs is not None:
+            self._state(int(n_envs))
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, n_envs: int | None = None, device=None, latent_in=None):
+        """From a live reference ``ActAgent`` (duck-typed): ``agent.model.state_dict()`` (the training-only keys are ignored) and ``agent.scaler``."""
+        sd = {k: torch.as_tensor(v) for k, v in agent.model.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["state_encoder.weight"].device
+        C, obs = sd["state_encoder.weight"].shape
+        layers = lambda p: len({k.split(".")[2] for k in sd if k.startswith(p + ".blocks.")})
+        net = ActNet(obs, sd["action_head.weight"].shape[0], sd["query_embed.weight"].shape[0], hidden_dim=C, n_heads=int(agent.model.encoder.blocks[0].attn.n_head),
+                     enc_layers=layers("encoder"), dec_layers=layers("decoder"), latent_dim=sd["latent_out_proj.weight"].shape[1])
+        sc = agent.scaler
+        pol = cls(net.to(dev), Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev), seed=seed, n_envs=n_envs, latent_in=latent_in)
+        pol.load_reference_state_dict(sd)
+        return pol
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: an ActAgent without goal conditioning, obs_size 1, window_size == action_seq_size, whose model is an
+        ActVAE without goal encoder whose encoder, decoder, cross and hidden widths are one, LayerNorms without bias?  Everything else stays on the row-by-row
+        adapter, which runs the reference's own code."""
+        try:
+            m = agent.model
+            gc = agent.gc if hasattr(agent, "gc") else agent.goal_conditioned
+            if gc is not False or int(agent.obs_size) != 1 or int(agent.window_size) != int(agent.action_seq_size) or hasattr(m, "goal_encoder"):
+                return False
+            if not hasattr(agent, "scaler") or agent.scaler.y_bounds is None or not hasattr(agent, "predict") or not hasattr(agent, "action_counter"):
+                return False
+            C, T = int(m.state_encoder.out_features), int(agent.action_seq_size)
+            if m.state_encoder.bias is not None or m.latent_out_proj.bias is not None or int(m.latent_out_proj.out_features) != C:
+                return False
+            if tuple(m.query_embed.weight.shape) != (T, C) or tuple(m.pos_emb.shape) != (1, T, C) or int(m.action_head.in_features) != C:
+                return False
+            heads = set()
+            for stack, cross in ((m.encoder, False), (m.decoder, True)):
+                if tuple(stack.ln.weight.shape) != (C,) or getattr(stack.ln, "bias", None) is not None or len(stack.blocks) < 1:
+                    return False
+                for b in stack.blocks:
+                    a = b.attn
+                    lins = [a.key, a.query, a.value, a.proj] + ([a.cross_key, a.cross_query, a.cross_value] if cross else [])
+                    if hasattr(a, "cross_key") != cross or not all(isinstance(l, nn.Linear) and l.in_features == C and l.out_features == C and l.bias is not None for l in lins):
+                        return False
+                    if any(getattr(ln, "bias", None) is not None or tuple(ln.weight.shape) != (C,) for ln in (b.ln1, b.ln2)):
+                        return False
+                    if not (isinstance(b.mlp[0], nn.Linear) and isinstance(b.mlp[1], nn.GELU) and getattr(b.mlp[1], "approximate", "none") == "none" and isinstance(b.mlp[2], nn.Linear)):
+                        return False
+                    if (b.mlp[0].in_features, b.mlp[0].out_features, b.mlp[2].in_features, b.mlp[2].out_features) != (C, 4 * C, 4 * C, C):
+                        return False
+                    if tuple(a.mask.shape) != (1, 1, T, T):
+                        return False
+                    heads.add(int(a.n_head))
+            return len(heads) == 1 and C % heads.pop() == 0
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet
+    def _state(self, n):
+        """counter / chunk / last_latent for n lanes; a new size starts with every lane due."""
+        if self.counter is None or self.counter.shape[0] != n:
+            dev = self.device
+            self.counter = torch.full((n,), self.T, dtype=torch.int32, device=dev)
+            self.chunk = torch.zeros(n, self.T, self.A, dtype=torch.float32, device=dev)
+            self.last_latent = torch.zeros(n, self.model.latent_dim, dtype=torch.float32, device=dev)
+
+    def reset(self):
+        """ActAgent.reset for every lane: the next call computes a chunk everywhere."""
+        if self.counter is not None:
+            self.counter.fill_(self.T)
+
+    def begin_episodes(self, mask):
+        """Lanes that start a new trajectory are due at their next step (in place on the device, also under a captured graph)."""
+        self._state(int(mask.shape[0]))
+        self.counter.masked_fill_(mask.to(device=self.device, dtype=torch.bool), self.T)
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+        self._state(int(count))
+
+    def fork(self):
+        """A clone for another sub-batch: network, scaler and tables shared; per-lane state, step word and packed buffers its own."""
+        import copy
+        c = copy.copy(self)
+        c._t = self._t.clone()
+        c._packed = PackedWeights()
+        if self.counter is not None:
+            c.counter, c.chunk, c.last_latent = self.counter.clone(), self.chunk.clone(), self.last_latent.clone()
+        c.last_chunk = None
+        return c
+
+    def captured(self):
+        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: one kernel and the add on the step word)."""
+        return CapturedPolicy(self)
+
+    def load_reference_state_dict(self, sd):
+        """``ActVAE.state_dict()`` of the reference: a plain load of the keys the inference path has (masks and the training-only modules are ignored)."""
+        own = self.model.state_dict()
+        self.model.load_state_dict({k: torch.as_tensor(sd[k]).to(own[k].dtype) for k in own})
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+
+    # ---- packed tables
+    def _pack_params(self):
+        return list(self.model.parameters())
+
+    def _pack(self):
+        return pack_act_weights(self.model)
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        self._packed.invalidate()
+
+    def ensure_packed(self):
+        if next(self.model.parameters()).is_cuda and self._kernel_shape():
+            self._packed.ensure(self._pack_params(), self._pack)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Warm-up and capture consume neither a step nor a chunk position: step word, counters and chunks are put back."""
+        self._state(int(obs.shape[0]))
+        return self._t.clone(), self.counter.clone(), self.chunk.clone(), self.last_latent.clone()
+
+    def capture_restore(self, snap):
+        for dst, src in zip((self._t, self.counter, self.chunk, self.last_latent), snap):
+            dst.copy_(src)
+
+    # ---- the step
+    def _kernel_shape(self) -> bool:
+        m = self.model
+        return (m.C == 64 and m.n_head == 4 and m.latent_dim == 32 and m.obs_dim <= 32 and 1 <= m.A <= 8 and 1 <= m.T <= 8 and 1 <= len(m.encoder.blocks) <= 4
+                and 1 <= len(m.decoder.blocks) <= 8)
+
+    def fused_ok(self, s) -> bool:
+        w = self.model.state_encoder.weight
+        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and os.environ.get("D3IL_POLICY_ACT_FUSED", "1") == "1"
+
+    def _latent(self, n, dev, need_host: bool):
+        """The latent as the torch path takes it / as the kernel is handed it: the given bank, or (``need_host``) the host form of the kernel's draw."""
+        if self.latent_in is not None:
+            return torch.as_tensor(self.latent_in(n), dtype=torch.float32).to(dev).reshape(n, self.model.latent_dim).contiguous()
+        if not need_host:
+            return None
+        return torch.as_tensor(act_latent_uniforms(self.seed, self.env_offset, n, int(self._t.item()) & 0xFFFFFFFF)).to(dev)
+
+    def _chunk_torch(self, s, z):
+        """A new chunk for every row, in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too): network, clamp to the bounds in the
+        scaled space, inverse scaling as two operations; rows with a NaN / Inf in the state or a head output are NaN."""
+        dt = s.dtype
+        c = lambda v: v.to(device=s.device, dtype=dt)
+        a_hat = self.model(s, c(z))
+        bad = ~torch.isfinite(s).all(dim=1) | ~torch.isfinite(a_hat).reshape(s.shape[0], -1).all(dim=1)
+        y = torch.minimum(torch.maximum(a_hat, c(self.lo)), c(self.hi)) * c(self.out_scale) + c(self.out_shift)
+        return torch.where(bad.reshape(-1, 1, 1), torch.full_like(y, float("nan")), y)
+
+    def _step_torch(self, s):
+        if s.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ACTPolicy: the torch path decides on the host which lanes are due and draws its Philox numbers there; it cannot be captured - the kernel can")
+        n = s.shape[0]
+        due = (self.counter >= self.T) | (self.counter < 0)
+        if bool(due.any()):
+            z = self._latent(n, s.device, True)
+            new = self._chunk_torch(torch.where(due.unsqueeze(1), s, torch.zeros_like(s)), z)
+            self.chunk.copy_(torch.where(due.reshape(-1, 1, 1), new, self.chunk))
+            self.last_latent.copy_(torch.where(due.unsqueeze(1), z, self.last_latent))
+            self.counter.masked_fill_(due, 0)
+        y = self.chunk[torch.arange(n, device=s.device), self.counter.long()]
+        self.counter.add_(1)
+        return y
+
+    def _step_kernel(self, s):
+        from . import capi
+        n, dev, m = s.shape[0], s.device, self.model
+        w = self._packed.current(self._pack_params(), self._pack)
+        z = self._latent(n, dev, False)
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        assert s.is_contiguous() and self._t.device == dev and self.counter.device == dev
+        capi.check(capi.load().d3il_act_chunk_f32(s.data_ptr(), w["w_in"].data_ptr(), w["tab"].data_ptr(), w["enc_w"].data_ptr(), w["enc_v"].data_ptr(), w["dec_w"].data_ptr(),
+                                                  w["dec_v"].data_ptr(), w["head_w"].data_ptr(), self.lo.data_ptr(), self.hi.data_ptr(), self.out_scale.data_ptr(),
+                                                  self.out_shift.data_ptr(), self.seed, self.env_offset, self._t.data_ptr(), None if z is None else z.data_ptr(),
+                                                  self.counter.data_ptr(), self.chunk.data_ptr(), y.data_ptr(), self.last_latent.data_ptr(), n, self.obs_dim, self.A, self.T,
+                                                  m.C, m.n_head, m.latent_dim, len(m.encoder.blocks), len(m.decoder.blocks), torch.cuda.current_stream(dev).cuda_stream))
+        return y
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "ACTPolicy: observation width %d, the state encoder takes %d" % (s.shape[-1], self.obs_dim)
+        self._state(s.shape[0])
+        if self.fused_ok(s):
+            y = self._step_kernel(s)
+        else:
+            if s.is_cuda and os.environ.get("D3IL_POLICY_ACT_FUSED", "1") == "1" and not getattr(self, "_warned", False):
+                import warnings
+                self._warned = True      # (once per policy; forks copy the flag)
+                warnings.warn("ACTPolicy: this network (width %d, %d heads, latent %d, T %d) is not one the chunk kernel is built for; every call runs the torch path "
+                              "with a device synchronisation per call and no graph capture" % (self.model.C, self.model.n_head, self.model.latent_dim, self.T))
+            y = self._step_torch(s)
+        if self.record:
+            self.last_chunk = self.chunk.clone()
+        self._t.add_(1)
+        return y
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, act_seq_size: int = 3, device="cuda", seed: int = 0, enc_layers: int = 2, dec_layers: int = 4, hidden_dim: int = 64,
+               n_heads: int = 4, latent_dim: int = 32, action_scale: float = 0.002, bound: float = 1.5, policy_seed: int = 0, **kw):
+        """A policy of the reference's shape (configs/agents/act_agent.yaml: 2 encoder and 4 decoder layers, width 64, 4 heads, latent 32) with the fixed
+        trained-like weights of ``act_synthetic_state`` (there are no checkpoints offline), unit observation scaling, actions of ``action_scale`` per unit of the
+        scaled space, bounds +-``bound``."""
+        net = ActNet(obs_dim, action_dim, act_seq_size, hidden_dim, n_heads, enc_layers, dec_layers, latent_dim)
+        net.load_state_dict({k: torch.as_tensor(v) for k, v in act_synthetic_state({k: v.shape for k, v in net.state_dict().items()}, seed).items()})
+        for p in net.parameters():
+            p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        return cls(net.to(device), sc, seed=policy_seed, **kw)

@@ -259,6 +259,24 @@ int d3il_ibc_langevin_f32(const float* state, const float* w_in, const float* b_
                           const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* x0_in, const float* noise_in,
                           const float* u_in, float* actions, int32_t* picks, float* x_final, float* energies, float* x0_out, float* noise_out, float* u_out, long n_env,
                           int obs_dim, int A, int hidden, int n_blocks, int S, int K, void* stream);
+/* One step of the batched VAE-ACT policy (policies.ACTPolicy; act_agent.py:207-239 around act_vae.py:389-445, ActVAE.forward without actions) in one launch, f32
+ * throughout.  Persistent per-environment state on the device: counter i32 [n_env] and chunk [n_env][T][A] (already clamped and inverse-scaled).  An environment with
+ * counter == T (or outside 0 .. T) is due: z = latent_in[n] or 32 Philox uniforms; the encoder runs on [W_s state + pos[0], W_z z + pos[1]] (causal mask for T >= 2, as
+ * the reference slices it; LayerNorm with weight only, eps 1e-5; exact GELU), the decoder on the T query embeddings (x + proj(causal self-attention(ln1 x) +
+ * cross-attention(ln1 x, encoder output)), x + mlp(ln2 x), final LayerNorm, action head); chunk[n][t][a] = clamp(head, lo_a, hi_a) scale_a + shift_a and counter = 0.
+ * Every environment then emits actions[n] = chunk[n][counter] and stores counter + 1.  A workgroup (16 environments) without a due environment runs no network;
+ * an environment's result never depends on which of its neighbours are due.  Random numbers: Philox4x32-10, key = seed, counter = (env_offset + n, *t_device,
+ * 0x41430000 | q), q < 8; latent component 4 q + m = (word m >> 8) 2^-24.  state [n_env][obs_dim] (scaled); w_in, tab, enc_w, enc_v, dec_w, dec_v, head_w:
+ * policies.pack_act_weights of the network (fragment order [To][t][lane (g, i)][r] = W[16 To + i][16 t + 4 g + r]; per layer the matrices q k v proj fc1 fc2 /
+ * q k v cq ck cv proj fc1 fc2 and the vectors ln1 ln2, the biases in the same order, b1 b2; tab = pos [2][64] | query_embed [8][64] | encoder ln | decoder ln | head
+ * bias [16]); lo / hi (scaled space) / scale / shift [A]; t_device: DEVICE u32, read only.  latent_in [n_env][32] and latent_out [n_env][32] (what was used; written
+ * for due environments only) may be NULL.  A due environment with a NaN / Inf in its state row or in a head output gets NaN in its whole chunk and in the emitted
+ * action; no other environment changes; the state row of an environment that is not due is not read.  Built for width 64, 4 heads, latent 32, obs_dim <= 32,
+ * 1 <= A <= 8, 1 <= T <= 8, 1 .. 4 encoder and 1 .. 8 decoder layers: D3IL_EUNSUPPORTED otherwise, answered before any launch.  Packed arrays 16-byte aligned. */
+int d3il_act_chunk_f32(const float* state, const float* w_in, const float* tab, const float* enc_w, const float* enc_v, const float* dec_w, const float* dec_v,
+                       const float* head_w, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset,
+                       const uint32_t* t_device, const float* latent_in, int32_t* counter, float* chunk, float* actions, float* latent_out, long n_env, int obs_dim, int A,
+                       int T, int width, int n_head, int latent, int n_enc, int n_dec, void* stream);
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
