@@ -820,6 +820,7 @@ __global__ __launch_bounds__(512) void k_resmlp_f32(const float* __restrict__ x,
     for (int r = 0; r < 4; r++) if (4 * g + r < OUT) out[row * OUT + 4 * g + r] = acc[r] + b_out[4 * g + r];
   }
 }
+#include "policy_cvae.h"      // k_cvae_decode: the scheme above with an in-kernel [state | latent] row and a fused action tail
 __global__ __launch_bounds__(256) void k_layernorm_f32(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ y,
                                                        long rows, int C, float eps) {
   const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
@@ -1809,6 +1810,27 @@ int d3il_act_chunk_f32(const float* state, const float* w_in, const float* tab, 
             (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, T, n_enc, n_dec};
   // one workgroup of four waves per 16 environments
   hipLaunchKernelGGL(k_act_chunk, dim3((unsigned)((n_env + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out,
+                         const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device,
+                         const float* z_in, float* actions, float* z_out, long n_env, int obs_dim, int latent, int A, int hidden, int n_blocks, void* stream) {
+  if ((hidden != 128 && hidden != 256) || latent < 1 || latent > CVAE_LMAX || obs_dim < 1 || obs_dim + latent > CVAE_INMAX || A < 1 || A > CVAE_AMAX || n_blocks < 0 ||
+      n_env > 0x7FFFFFFFL * 16)
+    return fail(D3IL_EUNSUPPORTED, "d3il_cvae_decode_f32: built for hidden 128 / 256, a latent of 1 .. 32, obs_dim >= 1 with obs_dim + latent <= 64, 1 .. 16 action components and n_blocks >= 0");
+  if (!state || !w_in || !b_in || !w_blocks || !b_blocks || !w_out || !b_out || !lo || !hi || !scale || !shift || !t_device || !actions)
+    return fail(D3IL_EINVAL, "d3il_cvae_decode_f32: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_cvae_decode_f32: negative environment count");
+  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_out) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_cvae_decode_f32: the packed weights and biases must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  CvaeArgs a{state, w_in, b_in, w_blocks, b_blocks, w_out, b_out, lo, hi, scale, shift, t_device, z_in, actions, z_out, (unsigned long long)seed, (unsigned long long)env_offset,
+             n_env, obs_dim, latent, A, n_blocks};
+  // one workgroup of eight waves per 16 environments; the last one may be partly filled
+  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
+  if (hidden == 128) hipLaunchKernelGGL(k_cvae_decode<128>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_cvae_decode<256>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

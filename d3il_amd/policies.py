@@ -664,19 +664,21 @@ class BCPolicy:
         return self.scaler.inverse_scale_output(torch.clamp(out, self.min_action, self.max_action))
 
 
-def pack_resmlp_weights(lin_in, blocks, lin_out) -> dict:
+def pack_resmlp_weights(lin_in, blocks, lin_out, in_cols: int = 32) -> dict:
     """Linear, residual blocks [(l1, l2), ..], Linear of a ResidualMLPNetwork in the operand order of k_resmlp_f32 and k_ddpm_mlp_f32, for any hidden
     width that is a multiple of 16: [T_out][t][lane (g, i)][r] = W[16 T_out + i][16 t + 4 g + r] for the square layers and the output layer (rows and bias padded
-    to 16 with zeros; k_ddpm_mlp_f32 reads two of them); the input layer, columns padded to 32: [T_out][lane (g, i)][s] = W[16 T_out + i][4 s + g]."""
+    to 16 with zeros; k_ddpm_mlp_f32 reads two of them); the input layer, columns padded to ``in_cols`` (32; 64 for k_cvae_decode): [T_out][lane (g, i)][s] =
+    W[16 T_out + i][4 s + g], s < in_cols / 4."""
     dev = lin_in.weight.device
     H = lin_in.out_features
     NT = H // 16
     ar = lambda k: torch.arange(k, device=dev)
     To, t, g, i, r = ar(NT)[:, None, None, None, None], ar(NT)[None, :, None, None, None], ar(4)[None, None, :, None, None], ar(16)[None, None, None, :, None], ar(4)[None, None, None, None, :]
     pack = lambda W: W[16 * To + i, 16 * t + 4 * g + r].reshape(NT, NT, 64, 4)
-    wi = torch.zeros(H, 32, device=dev)
+    assert in_cols % 4 == 0 and lin_in.in_features <= in_cols
+    wi = torch.zeros(H, in_cols, device=dev)
     wi[:, :lin_in.in_features] = lin_in.weight
-    w_in = wi[16 * ar(NT)[:, None, None, None] + ar(16)[None, None, :, None], 4 * ar(8)[None, None, None, :] + ar(4)[None, :, None, None]].reshape(NT, 64, 8)
+    w_in = wi[16 * ar(NT)[:, None, None, None] + ar(16)[None, None, :, None], 4 * ar(in_cols // 4)[None, None, None, :] + ar(4)[None, :, None, None]].reshape(NT, 64, in_cols // 4)
     wo = torch.zeros(16, H, device=dev)
     wo[:lin_out.out_features] = lin_out.weight
     w_out = wo[i[0], 16 * t[0] + 4 * g[0] + r[0]].reshape(NT, 64, 4)
@@ -2516,3 +2518,240 @@ class ACTPolicy:
             p.requires_grad_(False)
         sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
         return cls(net.to(device), sc, seed=policy_seed, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ conditional VAE: a clamped prior sample through the decoder
+CVAE_TAG = 0x43560000         # fourth Philox counter word of the decode kernel, or-ed with q < 8 (csrc/policy_cvae.h; never 0, BET_TAG, a DDPM_GPT_TAG, IBC_TAG or ACT_TAG word)
+CVAE_Z_BOUND = 0.5            # VariationalAE.predict clamps its prior sample to +-0.5 (cvae.py:58)
+
+
+def cvae_words(seed: int, env_offset: int, n: int, t: int):
+    """The Philox words of the decode kernel: uint32 [n, 8 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t, CVAE_TAG | q))."""
+    import numpy as np
+    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1)
+    q = np.arange(8, dtype=np.uint64).reshape(1, 8)
+    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, np.uint64(CVAE_TAG) | q), axis=-1)
+
+
+def cvae_latent_normals(seed: int, env_offset: int, n: int, t: int, L: int):
+    """The kernel's UNCLAMPED standard normals of environments 0 .. n-1 at step word t: float64 [n, L], component a = 4 q + m from word m of call q.  Exact on the
+    words and f64 from there on, Box-Muller as ``ddpm_gpt_normals`` (words 0, 1 -> components 0, 1; words 2, 3 -> components 2, 3)."""
+    import numpy as np
+    assert 1 <= L <= 32, "the counter layout holds eight calls of four components"
+    r = cvae_words(seed, env_offset, n, t)
+    out = np.zeros((n, 8, 4))
+    for p in range(2):
+        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+        rad = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
+    return out.reshape(n, 32)[:, :L]
+
+
+class CVAEPolicy:
+    """CVAEAgent.predict (agents/cvae_agent.py:155-170) around VariationalAE.predict (agents/models/vae/cvae.py:55-62) on a batch: scale the observation, draw a
+    standard-normal latent per environment and CLAMP IT TO +-0.5 - the reference clamps its prior sample, so 2 (1 - Phi(0.5)) = 61.7 % of all latent components sit
+    exactly on a bound; kept as it is -, run the decoder (a Mish ResidualMLPNetwork) on [state | z] (state first), clamp to the data bounds (scaled space),
+    inverse-scale.  The reference's clamp bounds and output scaler are float64: the clamp of the f32 output against them equals the clamp against their f32
+    roundings, and the inverse scaling is an f64 product and sum, here on the f32 scale and shift and rounded to f32 once.  The encoder is not part of inference
+    and is neither held nor loaded.  No history: the reference runs this agent with window_size 1.
+
+    On a HIP device the whole call is ONE kernel (csrc/policy_cvae.h through d3il_cvae_decode_f32: hidden 128 / 256, latent <= 32, obs + latent <= 64, at most 16
+    action components, any number of blocks), then a device-side add on the step word.  On the CPU, for other shapes and with D3IL_POLICY_CVAE_FUSED=0 the same
+    arithmetic runs as torch ops (``_decode_torch``) on the same Philox stream computed on the host - that path cannot be captured.  Random numbers: Philox4x32-10
+    keyed by ``seed`` with counter (env_offset + lane, step word, CVAE_TAG | q), so results do not depend on batch order, sub-batches or ranks;
+    ``z_in(n) -> [n, L]`` (UNCLAMPED normals; the policy clamps them) replaces the draw when given (golden replay, tests); ``last_z`` is the clamped latent that
+    was used.  A NaN / Inf in an environment's scaled state row, unclamped latent or decoder output gives that environment NaN in every action component."""
+
+    def __init__(self, decoder: ResidualMLP, scaler: Scaler, latent_dim: int, seed: int = 0, n_envs: int | None = None, z_in=None):
+        self.model, self.scaler = decoder.eval(), scaler
+        dev = scaler.x_mean.device
+        self.device = dev
+        lin_in, _, lin_out = decoder._parts()
+        self.L, self.A = int(latent_dim), int(lin_out.out_features)
+        self.obs_dim = int(lin_in.in_features) - self.L
+        assert 1 <= self.L <= 32, "the Philox counter layout holds a latent of at most 32 components"
+        assert self.obs_dim >= 1, "the decoder reads [state | latent]"
+        f = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self.seed, self.env_offset, self.n_envs = int(seed), 0, n_envs
+        self.z_in = z_in
+        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self._packed = PackedWeights()
+        self.last_z = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, n_envs: int | None = None, device=None, z_in=None):
+        """From a live reference ``CVAEAgent`` (duck-typed): ``agent.model.decoder.state_dict()``, ``agent.model.latent_dim``, ``agent.scaler`` (its ``y_bounds`` are
+        the clamp).  The encoder is left where it is."""
+        sd = {k: torch.as_tensor(v) for k, v in agent.model.decoder.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["layers.0.weight"].device
+        hidden, in_dim = sd["layers.0.weight"].shape
+        n_blocks = len({k.split(".")[1] for k in sd if ".l1." in k})
+        last = max(int(k.split(".")[1]) for k in sd)
+        net = ResidualMLP(in_dim, hidden, 2 * n_blocks, sd["layers.%d.weight" % last].shape[0])
+        net.load_state_dict(sd)
+        net = net.to(dev)
+        for p in net.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        return cls(net, scaler, int(agent.model.latent_dim), seed=seed, n_envs=n_envs, z_in=z_in)
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: a CVAEAgent whose model is a VariationalAE with a decoder made of plain ``nn.Linear`` layers and Mish
+        blocks without norm and without spectral norm, a latent of 1 .. 32 components, at most 64 decoder inputs and 16 outputs?  Everything else stays on the
+        row-by-row adapter, which runs the reference's own code."""
+        try:
+            vae = agent.model
+            if type(agent).__name__ != "CVAEAgent" or type(vae).__name__ != "VariationalAE" or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None:
+                return False
+            layers = list(vae.decoder.layers)
+            if len(layers) < 2 or not all(type(l) is nn.Linear for l in (layers[0], layers[-1])):
+                return False
+            blocks = layers[1:-1]
+            lins = [layers[0], layers[-1]] + [l for b in blocks for l in (b.l1, b.l2)]
+            if not all(type(l) is nn.Linear and not hasattr(l, "weight_orig") and l.bias is not None for l in lins):
+                return False
+            if not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in blocks):
+                return False
+            L, H = int(vae.latent_dim), layers[0].out_features
+            if not all(l.in_features == H and l.out_features == H for b in blocks for l in (b.l1, b.l2)) or layers[-1].in_features != H:
+                return False
+            return 1 <= L <= 32 and L < layers[0].in_features <= 64 and 1 <= layers[-1].out_features <= 16
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet
+    def reset(self):
+        pass
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+
+    def fork(self):
+        """A clone for another sub-batch: network, scaler and tables shared; step word and packed buffers its own."""
+        import copy
+        c = copy.copy(self)
+        c._t = self._t.clone()
+        c._packed = PackedWeights()
+        c.last_z = None
+        return c
+
+    def captured(self):
+        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: the scaling, one kernel and the add on the step word)."""
+        return CapturedPolicy(self)
+
+    def load_reference_state_dict(self, sd):
+        """``VariationalAE.state_dict()`` of the reference: the decoder sits under ``decoder.``; the encoder's entries are ignored."""
+        self.model.load_state_dict({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")})
+
+    # ---- packed tables
+    def _pack_params(self):
+        return list(self.model.parameters())
+
+    def _pack(self):
+        """pack_resmlp_weights of the decoder with the input layer packed to 64 columns."""
+        return pack_resmlp_weights(*self.model._parts(), in_cols=64)
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        self._packed.invalidate()
+
+    def ensure_packed(self):
+        if next(self.model.parameters()).is_cuda:
+            self._packed.ensure(self._pack_params(), self._pack)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Warm-up and capture do not count as steps: the step word is put back."""
+        return self._t.clone()
+
+    def capture_restore(self, snap):
+        self._t.copy_(snap)
+
+    # ---- the decode
+    def fused_ok(self, s) -> bool:
+        lin_in, _, lin_out = self.model._parts()
+        w = lin_in.weight
+        return (s.is_cuda and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and lin_in.in_features <= 64 and self.L <= 32
+                and lin_out.out_features <= 16 and os.environ.get("D3IL_POLICY_CVAE_FUSED", "1") == "1")
+
+    def _bank(self, n, dev, need_host: bool):
+        """The unclamped latent as the torch path takes it / as the kernel is handed it: ``z_in``, or (``need_host``) the host form of the kernel's draw, or None."""
+        if self.z_in is not None:
+            return torch.as_tensor(self.z_in(n), dtype=torch.float32).to(dev).reshape(n, self.L).contiguous()
+        if not need_host:
+            return None
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("CVAEPolicy: the torch path draws its Philox numbers on the host and cannot be captured; the kernel draws on the device")
+        t = int(self._t.item()) & 0xFFFFFFFF
+        return torch.as_tensor(cvae_latent_normals(self.seed, self.env_offset, n, t, self.L), dtype=torch.float32).to(dev)
+
+    def _decode_torch(self, s, z):
+        """Steps 1 - 3 of csrc/policy_cvae.h as torch ops in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too) on the unclamped
+        latent ``z``: returns (actions, the clamped latent)."""
+        dt = s.dtype
+        z = z.to(device=s.device, dtype=dt)
+        zc = z.clamp(-CVAE_Z_BOUND, CVAE_Z_BOUND)
+        x = torch.cat([s, zc], dim=1)
+        for layer in self.model.layers:
+            x = layer(x)
+        bad = ~(torch.isfinite(s).all(dim=1) & torch.isfinite(z).all(dim=1) & torch.isfinite(x).all(dim=1))
+        d = lambda v: v.to(device=s.device, dtype=torch.float64)
+        y = (torch.minimum(torch.maximum(x, self.lo.to(s.device, dt)), self.hi.to(s.device, dt)).double() * d(self.out_scale) + d(self.out_shift)).to(dt)
+        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        return y, torch.where(torch.isfinite(z), zc, torch.full_like(zc, float("nan")))
+
+    def _decode_kernel(self, s):
+        from . import capi
+        n, dev = s.shape[0], s.device
+        w = self._packed.current(self._pack_params(), self._pack)
+        z = self._bank(n, dev, False)
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        z_out = torch.empty(n, self.L, dtype=torch.float32, device=dev)
+        lin_in, blocks, _ = self.model._parts()
+        assert s.is_contiguous() and self._t.device == dev
+        capi.check(capi.load().d3il_cvae_decode_f32(s.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_out"].data_ptr(),
+                                                    w["b_out"].data_ptr(), self.lo.data_ptr(), self.hi.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed,
+                                                    self.env_offset, self._t.data_ptr(), None if z is None else z.data_ptr(), y.data_ptr(), z_out.data_ptr(), n, self.obs_dim, self.L,
+                                                    self.A, lin_in.out_features, len(blocks), torch.cuda.current_stream(dev).cuda_stream))
+        self.last_z = z_out
+        return y
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "CVAEPolicy: observation width %d, the decoder takes %d next to its latent" % (s.shape[-1], self.obs_dim)
+        if self.fused_ok(s):
+            y = self._decode_kernel(s)
+        else:
+            if s.is_cuda and os.environ.get("D3IL_POLICY_CVAE_FUSED", "1") == "1" and not getattr(self, "_warned", False):
+                import warnings
+                self._warned = True      # (once per policy; forks copy the flag)
+                warnings.warn("CVAEPolicy: this decoder (hidden %d, %d inputs, %d outputs) is not one the decode kernel is built for; every call runs torch's layers "
+                              "with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                              % (self.model._parts()[0].out_features, self.model._parts()[0].in_features, self.A))
+            y, self.last_z = self._decode_torch(s, self._bank(s.shape[0], s.device, True))
+        self._t.add_(1)
+        return y
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, latent_dim: int = 16, action_scale: float = 0.002,
+               policy_seed: int = 0, weight_gain: float = 1.0, bound: float = 1.5, **kw):
+        """A policy of the reference's shape with fixed random weights (there are no checkpoints offline): the shipped scripts use hidden 128 / 256 with 6 / 8 hidden
+        layers (3 / 4 blocks) and a latent of 16, 24 or 32; torch's default layer initialisation times ``weight_gain``, unit observation scaling, actions of
+        ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            net = ResidualMLP(obs_dim + latent_dim, hidden_dim, 2 * n_blocks, action_dim)
+        with torch.no_grad():
+            for p in net.parameters():
+                p.mul_(weight_gain)
+                p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        return cls(net.to(device), sc, latent_dim, seed=policy_seed, **kw)

@@ -277,6 +277,19 @@ int d3il_act_chunk_f32(const float* state, const float* w_in, const float* tab, 
                        const float* head_w, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset,
                        const uint32_t* t_device, const float* latent_in, int32_t* counter, float* chunk, float* actions, float* latent_out, long n_env, int obs_dim, int A,
                        int T, int width, int n_head, int latent, int n_enc, int n_dec, void* stream);
+/* The whole inference of the batched conditional-VAE policy (policies.CVAEPolicy; cvae_agent.py:155-170 around cvae.py:55-62) in one launch, f32 throughout: per
+ * environment z = clamp(z_in[n] or `latent` Box-Muller normals, -0.5, 0.5) (the reference clamps its prior sample: 61.7 % of the components sit on a bound), the
+ * decoder (ResidualMLPNetwork, Mish) on the row [state | z], actions[n][a] = clamp(out_a, lo_a, hi_a) scale_a + shift_a (product and sum in f64, rounded once).
+ * Random numbers: Philox4x32-10, key = seed, counter = (env_offset + n, *t_device, 0x43560000 | q), q < 8; component 4 q + m from word m, normals as
+ * d3il_ddpm_gpt_step_f32.  state [n_env][obs_dim] (scaled); w_in: the input layer packed to 64 columns, [NT][64][16] (policies.pack_resmlp_weights with
+ * in_cols=64; NT = hidden / 16); b_in .. b_out as d3il_resmlp_f32; lo / hi (scaled space) / scale / shift [A]; t_device: DEVICE u32, read only.  z_in [n_env][latent]
+ * (unclamped) and z_out [n_env][latent] (the clamped latent that was used) may be NULL.  An environment with a NaN / Inf in its state row, in its unclamped latent
+ * or in a decoder output gets NaN in every action component (z_out: NaN where the latent was hit); no other environment changes.  Built for hidden 128 / 256,
+ * 1 <= latent <= 32, obs_dim >= 1, obs_dim + latent <= 64, 1 <= A <= 16, n_blocks >= 0: D3IL_EUNSUPPORTED otherwise, answered before any launch.  Packed arrays
+ * 16-byte aligned. */
+int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out,
+                         const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device,
+                         const float* z_in, float* actions, float* z_out, long n_env, int obs_dim, int latent, int A, int hidden, int n_blocks, void* stream);
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
