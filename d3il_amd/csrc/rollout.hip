@@ -235,8 +235,21 @@ struct RareXch {
 };
 constexpr size_t AVOID_LDS_SERVE = (size_t)RX_ROWS * WAVE * sizeof(double) + 4 * sizeof(int);
 
-template <bool FAST, bool SERVE>
-__global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(const PandaConsts* __restrict__ cp, double* __restrict__ state,
+// GROUP = true (the step group, d3il_group_create): ONE dispatch steps the sub-batches of up to AVOID_GROUP_MAX handles.  The first parameter
+// is then the group's device table instead of the (unused) constants pointer; a workgroup finds its member by the first workgroup index with wave-uniform
+// scalar loads, takes the member's buffers, n, stride and epilogue block from the row and runs the code below with its workgroup index inside the member: the
+// instructions a launch of that member alone would execute.  n_substeps, max_steps and t_next are the same for all members (the host merges nothing else).
+constexpr int AVOID_GROUP_MAX = 8;
+struct AvoidGroupMember {
+  double* state; unsigned* flags; int* steps; const double* actions; float* obs; unsigned char* done; unsigned char* success; unsigned short* mode;
+  const AvoidEpilogue* ep;
+  int n, stride;
+  unsigned first_wg, pad_;      // first workgroup of the member in the merged dispatch; 0xFFFFFFFF in the unused rows
+};
+struct AvoidGroupTable { AvoidGroupMember m[AVOID_GROUP_MAX]; };
+typedef const __attribute__((address_space(4))) AvoidGroupTable CGroupTable4;
+template <bool FAST, bool SERVE, bool GROUP = false>
+__global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(typename std::conditional<GROUP, const AvoidGroupTable*, const PandaConsts*>::type __restrict__ cp, double* __restrict__ state,
                                                                   unsigned* __restrict__ flags, int* __restrict__ steps,
                                                                   const double* __restrict__ actions, float* __restrict__ obs,
                                                                   unsigned char* __restrict__ done, unsigned char* __restrict__ success,
@@ -249,7 +262,17 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
   const int lane = threadIdx.x & (WAVE - 1);
   const int role = threadIdx.x / WAVE;          // wave-uniform: 0 controller, 1 physics, 2 (SERVE) the rare constraint paths
   RareXch rx; rx.buf = rx_smem; rx.ctl = (int*)(rx_smem + RX_ROWS * WAVE); rx.lane = lane; rx.seq = 0;
-  int e = blockIdx.x * WAVE + lane;
+  unsigned wg_index = blockIdx.x;               // the workgroup's index inside its handle
+  if constexpr (GROUP) {
+    CGroupTable4* gt = (CGroupTable4*)(unsigned long long)cp;
+    int k = 0;
+#pragma unroll
+    for (int j = 1; j < AVOID_GROUP_MAX; j++) if (blockIdx.x >= gt->m[j].first_wg) k = j;      // rows are in dispatch order; unused rows never match
+    state = gt->m[k].state; flags = gt->m[k].flags; steps = gt->m[k].steps; actions = gt->m[k].actions; obs = gt->m[k].obs;
+    done = gt->m[k].done; success = gt->m[k].success; mode = gt->m[k].mode; ep = gt->m[k].ep; n = gt->m[k].n; stride = gt->m[k].stride;
+    wg_index = blockIdx.x - gt->m[k].first_wg;
+  }
+  int e = wg_index * WAVE + lane;
   const bool live = e < n;
   if (!live) e = n - 1;                         // keep every lane in the barriers; dead lanes recompute env n-1 and store nothing
   const PandaConsts& c = kAvoidingConsts;
@@ -341,7 +364,7 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
   } else {
     // parked for this wave's own epilogue.  Every lane stores the same words, unconditionally: a store by one lane needs a saved exec mask here, where all the
     // kernel arguments are alive, and that pair costs the two-wave form two more spilled SGPRs
-    ep_arg[0] = (unsigned long long)ep; ep_arg[1] = t_next; ep_arg[2] = blockIdx.x;
+    ep_arg[0] = (unsigned long long)ep; ep_arg[1] = t_next; ep_arg[2] = wg_index;
     EnvState st;
     load_state(state, flags, steps, stride, e, st);
     float o[2]; unsigned char dn;
@@ -1090,6 +1113,19 @@ struct d3il_handle_s {
   // link-near guard of the generic engine (link_guard.h, d3il_set_link_guard): lg.n = 0 = off
   d3il_model_blob model;   // the blob the handle was made from (the body tree places the guard's capsules)
   LinkGuardConsts lg; LinkGuardConsts* d_lg; int64_t* lg_flagged;   // lg_flagged: caller-owned device counter, may be null
+  // step group (d3il_group_create): the group of this handle and its deferred d3il_random_rollout_step call of the current round
+  struct d3il_group_s* group; bool grp_pending; uint64_t grp_seed, grp_off; uint32_t grp_t; double* grp_actions; int64_t* grp_counts; hipStream_t grp_stream;
+  hipEvent_t ring_alt0[128], ring_alt1[128];      // ring slot of a merged launch: the group's shared event pair (null: the handle's own pair)
+};
+// A step group: Avoiding handles of one device whose d3il_random_rollout_step calls of one step go out as ONE dispatch.  The round's key
+// (t, n_substeps, max_steps, timing) is that of its first pending member.
+struct d3il_group_s {
+  int device, count; d3il_handle_s* m[AVOID_GROUP_MAX];
+  int n_pending; bool busy;      // busy: a flush or a merged launch is running (the library calls it makes must not flush again)
+  uint32_t t; int n_substeps, max_steps; bool timing;
+  AvoidGroupTable* d_table; AvoidGroupTable table_host; bool table_valid;
+  hipEvent_t ev_join[AVOID_GROUP_MAX], ev_done; bool ev_made;
+  hipEvent_t ring0[128], ring1[128]; bool ring_created; long ring_head;      // the shared event pairs of the timed merged launches
 };
 
 // The Stacking kernels read their model from one __constant__ object per device (scalar loads, no pointer across call boundaries).  Stacking handles on one
@@ -1115,11 +1151,18 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 extern "C" {
 
+// Step group: every library call on a member other than an eligible d3il_random_rollout_step ends the round first - the pending members run through the
+// single-handle path, in group order - so that no call sees buffers a deferred step has not advanced yet.
+static int group_flush(d3il_group_s* g);
+static inline int group_settle(d3il_handle_s* h) { return (h && h->group && h->group->n_pending && !h->group->busy) ? group_flush(h->group) : D3IL_OK; }
+#define GROUP_SETTLE(h) do { if (int rc_g_ = group_settle(h)) return rc_g_; } while (0)
+
 const char* d3il_last_error(void) { return g_err.c_str(); }
 size_t d3il_blob_sizeof(void) { return sizeof(d3il_model_blob); }
 int d3il_version(void) { return 2; }
 
 static void rg_drop(d3il_handle_s* h);
+static void group_leave(d3il_handle_s* h);
 static void rg_drop_for_free(d3il_handle_s* h) {
   if (h->rg_ready) for (int k = 0; k < RG_SLOTS; k++) { (void)hipGraphExecDestroy(h->rg_exec[k]); (void)hipGraphDestroy(h->rg_graph[k]); }
   if (h->rg_t_dev) (void)hipFree(h->rg_t_dev);
@@ -1286,12 +1329,14 @@ int d3il_create(int task_id, int n_envs, int device_id, const void* model_blob, 
 int d3il_destroy(d3il_handle h) {
   if (!h) return fail(D3IL_EINVAL, "d3il_destroy: null handle");
   (void)hipSetDevice(h->device);
+  group_leave(h);      // a member of a step group: the round is flushed, the others go on without it
   (void)hipDeviceSynchronize();
   free_handle(h);
   return D3IL_OK;
 }
 
 int d3il_start(d3il_handle h, const double* init_qpos7) {
+  GROUP_SETTLE(h);
   if (!h || !init_qpos7) return fail(D3IL_EINVAL, "d3il_start: null argument");
   for (int k = 0; k < 7; k++) if (!(init_qpos7[k] == init_qpos7[k])) return fail(D3IL_EINVAL, "d3il_start: init_qpos contains NaN");
   HIPCHK(hipSetDevice(h->device));
@@ -1389,6 +1434,7 @@ static int drop_prepared_action(d3il_handle_s* h) {
   return D3IL_OK;
 }
 int d3il_reset(d3il_handle h, const uint8_t* env_mask, const double* contexts, void* stream) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_reset: null handle");
   if (int rc_ = drop_prepared_action(h)) return rc_;
   if (!h->started) return fail(D3IL_ESTATE, "d3il_reset: d3il_start() has not been called (env.start() before env.reset())");
@@ -1443,8 +1489,9 @@ int d3il_reset(d3il_handle h, const uint8_t* env_mask, const double* contexts, v
 static int timing_drain_one(d3il_handle h) {
   const int slot = (int)(h->ring_drained % 128);
   float ms = 0;
-  HIPCHK(hipEventSynchronize(h->ring1[slot]));
-  HIPCHK(hipEventElapsedTime(&ms, h->ring0[slot], h->ring1[slot]));
+  hipEvent_t e0 = h->ring_alt0[slot] ? h->ring_alt0[slot] : h->ring0[slot], e1 = h->ring_alt1[slot] ? h->ring_alt1[slot] : h->ring1[slot];
+  HIPCHK(hipEventSynchronize(e1));
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
   h->t_sum += ms; h->t_n++; if (ms < h->t_min) h->t_min = ms; if (ms > h->t_max) h->t_max = ms;
   h->ring_drained++;
   return D3IL_OK;
@@ -1452,14 +1499,14 @@ static int timing_drain_one(d3il_handle h) {
 static int timing_begin(d3il_handle h, hipStream_t s) {
   if (h->ring_head - h->ring_drained >= 128) { if (int rc = timing_drain_one(h)) return rc; }      // the pair recorded 128 launches ago: long finished
   const int slot = (int)(h->ring_head % 128);
-  h->ev0 = h->ring0[slot]; h->ev1 = h->ring1[slot];
+  h->ev0 = h->ring0[slot]; h->ev1 = h->ring1[slot]; h->ring_alt0[slot] = nullptr; h->ring_alt1[slot] = nullptr;
   HIPCHK(hipEventRecord(h->ev0, s));
   return D3IL_OK;
 }
 // ep / t_next: the rollout epilogue of the Avoiding split kernels (AvoidEpilogue in device memory; null: none).  The caller has checked split_step_kernel(h).
 static bool split_step_kernel(const d3il_handle_s* h) { return h->task_id == D3IL_TASK_AVOIDING && h->fast && h->lanes == WAVE && h->split != 0; }
 static int step_launch(d3il_handle h, const double* actions, void* stream, const AvoidEpilogue* ep, unsigned t_next);
-int d3il_step(d3il_handle h, const double* actions, void* stream) { return step_launch(h, actions, stream, nullptr, 0u); }
+int d3il_step(d3il_handle h, const double* actions, void* stream) { GROUP_SETTLE(h); return step_launch(h, actions, stream, nullptr, 0u); }
 static int step_launch(d3il_handle h, const double* actions, void* stream, const AvoidEpilogue* ep, unsigned t_next) {
   if (!h || !actions) return fail(D3IL_EINVAL, "d3il_step: null argument");
   if (int rc_ = drop_prepared_action(h)) return rc_;
@@ -1553,6 +1600,7 @@ static int check_state_rows(d3il_handle h, const void* state, int32_t state_rows
   return D3IL_OK;
 }
 int d3il_get_state(d3il_handle h, double* state, int32_t state_rows, uint32_t* flags, int32_t* steps) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_get_state: null handle");
   if (int rc_ = check_state_rows(h, state, state_rows, "d3il_get_state")) return rc_;
   HIPCHK(hipSetDevice(h->device));
@@ -1563,6 +1611,7 @@ int d3il_get_state(d3il_handle h, double* state, int32_t state_rows, uint32_t* f
   return D3IL_OK;
 }
 int d3il_set_state(d3il_handle h, const double* state, int32_t state_rows, const uint32_t* flags, const int32_t* steps) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_set_state: null handle");
   if (int rc_ = check_state_rows(h, state, state_rows, "d3il_set_state")) return rc_;
   if (int rc_ = drop_prepared_action(h)) return rc_;
@@ -1575,6 +1624,7 @@ int d3il_set_state(d3il_handle h, const double* state, int32_t state_rows, const
 }
 
 int d3il_policy_begin(d3il_handle h, const uint8_t* env_mask, void* stream) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_policy_begin: null handle");
   if (int rc_ = drop_prepared_action(h)) return rc_;
   HIPCHK(hipSetDevice(h->device));
@@ -1583,6 +1633,7 @@ int d3il_policy_begin(d3il_handle h, const uint8_t* env_mask, void* stream) {
   return D3IL_OK;
 }
 int d3il_policy_action(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, void* stream) {
+  GROUP_SETTLE(h);
   if (!h || !actions) return fail(D3IL_EINVAL, "d3il_policy_action: null argument");
   if (int rc_ = drop_prepared_action(h)) return rc_;
   if (h->buf.action_dim != 7) return fail(D3IL_EUNSUPPORTED, "d3il_policy_action: the random Cartesian policy writes 7-wide rows (Avoiding / Pushing / Sorting); Stacking actions are 8 wide");
@@ -1835,6 +1886,7 @@ int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_i
   return D3IL_OK;
 }
 int d3il_set_tally(d3il_handle h, const int32_t* ctx_id_device, int n_ctx, int64_t* table_device) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_set_tally: null handle");
   if (table_device && n_ctx <= 0) return fail(D3IL_EINVAL, "d3il_set_tally: n_ctx must be positive");
   if (h->rg_ready) { HIPCHK(hipDeviceSynchronize()); rg_drop(h); }
@@ -1843,6 +1895,7 @@ int d3il_set_tally(d3il_handle h, const int32_t* ctx_id_device, int n_ctx, int64
 }
 
 int d3il_auto_reset(d3il_handle h, int64_t* episode_counts_device, void* stream) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_auto_reset: null handle");
   if (int rc_ = drop_prepared_action(h)) return rc_;
   if (!h->started) return fail(D3IL_ESTATE, "d3il_auto_reset: d3il_start() has not been called");
@@ -1872,6 +1925,7 @@ int d3il_auto_reset(d3il_handle h, int64_t* episode_counts_device, void* stream)
 }
 
 int d3il_count_metrics(d3il_handle h, int64_t* out_counts_device, void* stream) {
+  GROUP_SETTLE(h);
   if (!h || !out_counts_device) return fail(D3IL_EINVAL, "d3il_count_metrics: null argument");
   if (h->task_id != D3IL_TASK_AVOIDING) return fail(D3IL_EUNSUPPORTED, "d3il_count_metrics: Avoiding only");
   HIPCHK(hipSetDevice(h->device));
@@ -1955,6 +2009,7 @@ int d3il_comm_destroy(d3il_comm comm) {
   return D3IL_OK;
 }
 int d3il_reduce_metrics(d3il_handle h, d3il_comm comm, int64_t* table_device, size_t count, void* stream) {
+  GROUP_SETTLE(h);
   if (!comm || (!h && !table_device)) return fail(D3IL_EINVAL, "d3il_reduce_metrics: null argument");      // h may be NULL with an explicit table (a rank without environments)
   if (!table_device) { table_device = h->tally_table; count = (size_t)h->tally_nctx * D3IL_TALLY_ROW; }      // default: the table of d3il_set_tally
   if (!table_device || count == 0) return fail(D3IL_EINVAL, "d3il_reduce_metrics: no table (pass one, or register it with d3il_set_tally)");
@@ -1967,6 +2022,7 @@ int d3il_reduce_metrics(d3il_handle h, d3il_comm comm, int64_t* table_device, si
 }
 
 int d3il_set_timing(d3il_handle h, int enabled) {
+  GROUP_SETTLE(h);
   if (!h) return fail(D3IL_EINVAL, "d3il_set_timing: null handle");
   HIPCHK(hipSetDevice(h->device));
   if (enabled && !h->ring_created) {
@@ -1979,6 +2035,7 @@ int d3il_set_timing(d3il_handle h, int enabled) {
   return D3IL_OK;
 }
 int d3il_timing_stats(d3il_handle h, double* out4) {
+  GROUP_SETTLE(h);
   if (!h || !out4) return fail(D3IL_EINVAL, "d3il_timing_stats: null argument");
   HIPCHK(hipSetDevice(h->device));
   while (h->ring_drained < h->ring_head) { if (int rc = timing_drain_one(h)) return rc; }
@@ -1986,6 +2043,7 @@ int d3il_timing_stats(d3il_handle h, double* out4) {
   return D3IL_OK;
 }
 int d3il_step_auto_reset(d3il_handle h, const double* actions, int64_t* episode_counts_device, void* stream) {
+  GROUP_SETTLE(h);
   // Avoiding, split kernels: the reset kernels of this same call overwrite every finished lane and read only done / success / the mode of a successful one,
   // so the step kernel is told (t_next = 1 without an epilogue block) to retire the lanes that are finished and not successful at step_begin.  Whatever would
   // make d3il_auto_reset refuse is checked BEFORE the step is enqueued: a retired lane must not be left in memory unreset.
@@ -2046,6 +2104,7 @@ static int rg_capture(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_
 // captures the graphs of the NEXT d3il_random_rollout_step calls with these arguments without launching anything (a harness does this outside its timed region);
 // a no-op without option graph_rollout
 int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream) {
+  GROUP_SETTLE(h);
   if (!h || !actions) return fail(D3IL_EINVAL, "d3il_random_rollout_prepare: null argument");
   if (!(h->rg_enabled && h->task_id == D3IL_TASK_AVOIDING && stream != nullptr && h->started)) return D3IL_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -2058,7 +2117,43 @@ int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offse
   if (!h->rg_ready) return rg_capture(h, seed, env_offset, t, actions, episode_counts_device, s);
   return D3IL_OK;
 }
-int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream) {
+// The fused rollout step (option fuse_rollout_tail), first half: everything before the step launch.  `a` receives the epilogue's argument block; with the
+// split step kernel its device copy is brought up to date.
+static bool continues_sequence(const d3il_handle_s* h, uint64_t seed, uint64_t env_offset, uint32_t t, const double* actions, void* stream) {
+  return h->prep_valid && h->prep_t == t && h->prep_seed == seed && h->prep_off == env_offset && h->prep_actions == actions && h->prep_stream == (hipStream_t)stream;
+}
+static int fused_step_begin(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream, AvoidEpilogue& a) {
+  // ONE launch per step: the split step kernel with its rollout epilogue (mask, tally, reset from the cached image, the NEXT step's action); the one-wave
+  // step kernel is followed by k_avoiding_tail instead.  The first call of a sequence (or one whose arguments / step counter do not continue the previous
+  // call) starts with the separate policy kernel
+  const bool cont = continues_sequence(h, seed, env_offset, t, actions, stream);
+  if (!h->d_des_before) { HIPCHK(hipSetDevice(h->device)); HIPCHK(hipMalloc(&h->d_des_before, (size_t)h->stride * 2 * sizeof(double))); }
+  if (cont) h->prep_valid = 0;          // consumed: the calls below must not put the pose back
+  else { if (int rc = d3il_policy_action(h, seed, env_offset, t, actions, stream)) return rc; }      // (d3il_policy_action drops a stale prepared action first)
+  d3il_buffers& b = h->buf;
+  a = AvoidEpilogue{};
+  a.img = h->reset_img; a.state = b.state; a.flags = b.flags; a.steps = b.step_count; a.obs = b.obs; a.done = b.done; a.success = b.success; a.mode = b.mode;
+  a.n = h->n; a.stride = h->stride; a.des = b.policy_des; a.episode_counts = (long long*)episode_counts_device; a.mask = h->d_mask; a.ctx_id = h->tally_ctx;
+  a.table = (long long*)h->tally_table; a.actions = actions; a.des_before = h->d_des_before; a.seed = seed; a.env_offset = env_offset; a.n_ctx = h->tally_nctx;
+  if (split_step_kernel(h)) {
+    // the device copy of the block follows the arguments: rewritten (on this stream, before the launch that reads it) only when one of them changed.
+    // A launch that still reads the old block is ordered before the copy on its own stream only: when the stream changed too - or the handle is in a step
+    // group, whose merged launches read the block on the first member's stream - wait for the device first
+    if (!h->epilogue_valid || std::memcmp(&h->epilogue_host, &a, sizeof a) != 0) {
+      HIPCHK(hipSetDevice(h->device));
+      if (h->epilogue_valid && (h->epilogue_stream != (hipStream_t)stream || h->group)) HIPCHK(hipDeviceSynchronize());
+      HIPCHK(hipMemcpyAsync(h->d_epilogue, &a, sizeof a, hipMemcpyHostToDevice, (hipStream_t)stream));
+      HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // `a` is on the stack
+      h->epilogue_host = a; h->epilogue_valid = true; h->epilogue_stream = (hipStream_t)stream;
+    }
+  }
+  return D3IL_OK;
+}
+static void fused_step_end(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, void* stream) {
+  h->prep_valid = true; h->prep_t = t + 1u; h->prep_seed = seed; h->prep_off = env_offset; h->prep_actions = actions; h->prep_stream = (hipStream_t)stream;
+}
+// d3il_random_rollout_step of ONE handle (a handle outside a step group; a member whose call is not merged)
+static int rollout_step_single(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream) {
   if (h && h->rg_enabled && h->task_id == D3IL_TASK_AVOIDING && stream != nullptr && actions && h->started) {
     hipStream_t s = (hipStream_t)stream;
     if (int rc_ = drop_prepared_action(h)) return rc_;      // (the graph path draws its own action: a pending fused-tail draw ends here)
@@ -2078,42 +2173,198 @@ int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, 
     return D3IL_OK;
   }
   if (h && h->fuse_tail && h->task_id == D3IL_TASK_AVOIDING && actions && episode_counts_device && h->started) {
-    // ONE launch per step: the split step kernel with its rollout epilogue (mask, tally, reset from the cached image, the NEXT step's action); the one-wave
-    // step kernel is followed by k_avoiding_tail instead.  The first call of a sequence (or one whose arguments / step counter do not continue the previous
-    // call) starts with the separate policy kernel
-    const bool cont = h->prep_valid && h->prep_t == t && h->prep_seed == seed && h->prep_off == env_offset && h->prep_actions == actions && h->prep_stream == (hipStream_t)stream;
-    if (!h->d_des_before) { HIPCHK(hipSetDevice(h->device)); HIPCHK(hipMalloc(&h->d_des_before, (size_t)h->stride * 2 * sizeof(double))); }
-    if (cont) h->prep_valid = 0;          // consumed: the calls below must not put the pose back
-    else { if (int rc = d3il_policy_action(h, seed, env_offset, t, actions, stream)) return rc; }      // (d3il_policy_action drops a stale prepared action first)
-    d3il_buffers& b = h->buf;
-    AvoidEpilogue a{};
-    a.img = h->reset_img; a.state = b.state; a.flags = b.flags; a.steps = b.step_count; a.obs = b.obs; a.done = b.done; a.success = b.success; a.mode = b.mode;
-    a.n = h->n; a.stride = h->stride; a.des = b.policy_des; a.episode_counts = (long long*)episode_counts_device; a.mask = h->d_mask; a.ctx_id = h->tally_ctx;
-    a.table = (long long*)h->tally_table; a.actions = actions; a.des_before = h->d_des_before; a.seed = seed; a.env_offset = env_offset; a.n_ctx = h->tally_nctx;
+    AvoidEpilogue a;
+    if (int rc = fused_step_begin(h, seed, env_offset, t, actions, episode_counts_device, stream, a)) return rc;
     if (split_step_kernel(h)) {
-      // the device copy of the block follows the arguments: rewritten (on this stream, before the launch that reads it) only when one of them changed.
-      // A launch that still reads the old block is ordered before the copy on its own stream only: when the stream changed too, wait for the device first
-      if (!h->epilogue_valid || std::memcmp(&h->epilogue_host, &a, sizeof a) != 0) {
-        HIPCHK(hipSetDevice(h->device));
-        if (h->epilogue_valid && h->epilogue_stream != (hipStream_t)stream) HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpyAsync(h->d_epilogue, &a, sizeof a, hipMemcpyHostToDevice, (hipStream_t)stream));
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // `a` is on the stack
-        h->epilogue_host = a; h->epilogue_valid = true; h->epilogue_stream = (hipStream_t)stream;
-      }
       if (int rc = step_launch(h, actions, stream, h->d_epilogue, t + 1u)) return rc;
     } else {
       if (int rc = d3il_step(h, actions, stream)) return rc;
       hipLaunchKernelGGL(k_avoiding_tail, dim3(h->stride / WAVE), dim3(WAVE), 0, (hipStream_t)stream, a, t + 1u);
       HIPCHK(hipGetLastError());
     }
-    h->prep_valid = true; h->prep_t = t + 1u; h->prep_seed = seed; h->prep_off = env_offset; h->prep_actions = actions; h->prep_stream = (hipStream_t)stream;
+    fused_step_end(h, seed, env_offset, t, actions, stream);
     return D3IL_OK;
   }
   if (int rc = d3il_policy_action(h, seed, env_offset, t, actions, stream)) return rc;
   if (int rc = d3il_step(h, actions, stream)) return rc;
   return d3il_auto_reset(h, episode_counts_device, stream);
 }
+
+// ---- the step group.  With fewer hardware queues than streams, the step launches of two sub-batches share a queue and run one after
+// the other although each fills a sixteenth of the chip.  A group sends the launches of one step as ONE dispatch on the first member's stream: a call on a
+// member only marks it pending, the call that completes the round launches.  Stream order is kept for the caller: the first member's stream waits for
+// an event on every other member's stream before the launch, and every other member's stream waits for the launch afterwards.
+static int group_flush(d3il_group_s* g) {
+  if (g->busy) return D3IL_OK;
+  g->busy = true;
+  int rc = D3IL_OK;
+  for (int i = 0; i < g->count; i++) {
+    d3il_handle_s* h = g->m[i];
+    if (!h->grp_pending) continue;
+    h->grp_pending = false; g->n_pending--;
+    if (!rc) rc = rollout_step_single(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, h->grp_counts, (void*)h->grp_stream);      // (after a failure the others are only un-marked)
+  }
+  g->n_pending = 0; g->busy = false;
+  return rc;
+}
+static int group_launch_locked(d3il_group_s* g) {
+  HIPCHK(hipSetDevice(g->device));
+  if (!g->ev_made) {
+    for (int i = 0; i < AVOID_GROUP_MAX; i++) HIPCHK(hipEventCreateWithFlags(&g->ev_join[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
+    HIPCHK(hipMalloc(&g->d_table, sizeof(AvoidGroupTable)));
+    g->ev_made = true;
+  }
+  // every member's own part of the call, as in the single path: the prepared action is consumed, the epilogue block brought up to date
+  AvoidGroupTable tab;
+  std::memset(&tab, 0, sizeof tab);
+  unsigned total = 0; int serve_budget = 0;
+  for (int i = 0; i < AVOID_GROUP_MAX; i++) tab.m[i].first_wg = 0xFFFFFFFFu;
+  for (int i = 0; i < g->count; i++) {
+    d3il_handle_s* h = g->m[i];
+    AvoidEpilogue a;
+    if (int rc = fused_step_begin(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, h->grp_counts, (void*)h->grp_stream, a)) return rc;
+    const d3il_buffers& b = h->buf;
+    AvoidGroupMember& r = tab.m[i];
+    r.state = b.state; r.flags = b.flags; r.steps = b.step_count; r.actions = h->grp_actions; r.obs = b.obs; r.done = b.done; r.success = b.success; r.mode = b.mode;
+    r.ep = h->d_epilogue; r.n = h->n; r.stride = h->stride; r.first_wg = total;
+    total += (unsigned)((h->n + WAVE - 1) / WAVE); serve_budget += h->serve_max_wg;
+  }
+  hipStream_t s0 = g->m[0]->grp_stream;
+  // the table follows its fields like the epilogue block: rewritten only when one changed, and then behind everything that may still read the old one
+  if (!g->table_valid || std::memcmp(&g->table_host, &tab, sizeof tab) != 0) {
+    if (g->table_valid) HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(g->d_table, &tab, sizeof tab, hipMemcpyHostToDevice));
+    g->table_host = tab; g->table_valid = true;
+  }
+  for (int i = 1; i < g->count; i++) {
+    if (g->m[i]->grp_stream == s0) continue;
+    HIPCHK(hipEventRecord(g->ev_join[i], g->m[i]->grp_stream));
+    HIPCHK(hipStreamWaitEvent(s0, g->ev_join[i], 0));
+  }
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  if (g->timing) {
+    if (!g->ring_created) {
+      for (int i = 0; i < 128; i++) { HIPCHK(hipEventCreate(&g->ring0[i])); HIPCHK(hipEventCreate(&g->ring1[i])); }
+      g->ring_created = true;
+    }
+    // a member reads the pair of a slot before the group records it again: a slot comes round after 128 merged launches, and each was a launch of every member
+    for (int i = 0; i < g->count; i++) { d3il_handle_s* h = g->m[i]; if (h->ring_head - h->ring_drained >= 128) { if (int rc = timing_drain_one(h)) return rc; } }
+    t0 = g->ring0[g->ring_head % 128]; t1 = g->ring1[g->ring_head % 128];
+    HIPCHK(hipEventRecord(t0, s0));
+  }
+  const d3il_handle_s* h0 = g->m[0];
+  const unsigned t_next = g->t + 1u;
+  // three waves while the merged dispatch stays inside what the members' thresholds allow together (one workgroup per CU), otherwise two
+  if ((long)total <= (long)serve_budget)
+    hipLaunchKernelGGL((k_avoiding_step_split<true, true, true>), dim3(total), dim3(3 * WAVE), AVOID_LDS_SERVE, s0, (const AvoidGroupTable*)g->d_table, (double*)nullptr, (unsigned*)nullptr,
+                       (int*)nullptr, (const double*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, (unsigned short*)nullptr, 0, 0, h0->hc.n_substeps,
+                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next);
+  else
+    hipLaunchKernelGGL((k_avoiding_step_split<true, false, true>), dim3(total), dim3(2 * WAVE), 0, s0, (const AvoidGroupTable*)g->d_table, (double*)nullptr, (unsigned*)nullptr,
+                       (int*)nullptr, (const double*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, (unsigned short*)nullptr, 0, 0, h0->hc.n_substeps,
+                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next);
+  HIPCHK(hipGetLastError());
+  hipEvent_t done_ev = g->ev_done;
+  if (g->timing) {
+    HIPCHK(hipEventRecord(t1, s0));
+    done_ev = t1;      // the end of the timed pair is the event the other streams wait for
+    for (int i = 0; i < g->count; i++) {
+      d3il_handle_s* h = g->m[i];
+      const int slot = (int)(h->ring_head % 128);
+      h->ring_alt0[slot] = t0; h->ring_alt1[slot] = t1; h->ev0 = t0; h->ev1 = t1; h->ev_valid = true; h->ring_head++;
+    }
+    g->ring_head++;
+  } else HIPCHK(hipEventRecord(done_ev, s0));
+  for (int i = 1; i < g->count; i++) if (g->m[i]->grp_stream != s0) HIPCHK(hipStreamWaitEvent(g->m[i]->grp_stream, done_ev, 0));
+  for (int i = 0; i < g->count; i++) { d3il_handle_s* h = g->m[i]; fused_step_end(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, (void*)h->grp_stream); }
+  return D3IL_OK;
+}
+static int group_launch(d3il_group_s* g) {
+  g->busy = true;
+  const int rc = group_launch_locked(g);
+  for (int i = 0; i < g->count; i++) g->m[i]->grp_pending = false;
+  g->n_pending = 0; g->busy = false;
+  return rc;
+}
+// the call of a member: *handled = 1 when it was deferred or launched with its round, 0 when the caller runs it through the single path (the round, if any, has been flushed)
+static int group_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream, int* handled) {
+  d3il_group_s* g = h->group;
+  *handled = 0;
+  if (g->busy) return D3IL_OK;
+  const bool eligible = h->fuse_tail && !h->rg_enabled && h->task_id == D3IL_TASK_AVOIDING && actions && episode_counts_device && h->started && split_step_kernel(h) &&
+                        h->serve_avail && continues_sequence(h, seed, env_offset, t, actions, stream);
+  if (!eligible) return g->n_pending ? group_flush(g) : D3IL_OK;
+  if (g->n_pending && (h->grp_pending || g->t != t || g->n_substeps != h->hc.n_substeps || g->max_steps != h->hc.max_steps || g->timing != h->timing)) {
+    if (int rc = group_flush(g)) return rc;      // a second call of a member, or a call that does not fit the round: nothing is merged
+  }
+  if (!g->n_pending) { g->t = t; g->n_substeps = h->hc.n_substeps; g->max_steps = h->hc.max_steps; g->timing = h->timing; }
+  h->grp_pending = true; h->grp_seed = seed; h->grp_off = env_offset; h->grp_t = t; h->grp_actions = actions; h->grp_counts = episode_counts_device; h->grp_stream = (hipStream_t)stream;
+  g->n_pending++;
+  *handled = 1;
+  return g->n_pending == g->count ? group_launch(g) : D3IL_OK;
+}
+int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream) {
+  if (h && h->group) {
+    int handled = 0;
+    if (int rc = group_rollout_step(h, seed, env_offset, t, actions, episode_counts_device, stream, &handled)) return rc;
+    if (handled) return D3IL_OK;
+  }
+  return rollout_step_single(h, seed, env_offset, t, actions, episode_counts_device, stream);
+}
+static void timing_drain_all(d3il_handle_s* h) { while (h->ring_drained < h->ring_head) { if (timing_drain_one(h)) { h->ring_drained = h->ring_head; break; } } }
+// the member leaves its group: the round ends, the durations it still has to read from the group's shared event pairs are read now
+static void group_leave(d3il_handle_s* h) {
+  d3il_group_s* g = h->group;
+  if (!g) return;
+  (void)group_flush(g);
+  timing_drain_all(h);
+  // nothing of the handle may name an event of the group any more (d3il_group_destroy destroys them, a group that lives on records them again): the ring
+  // is drained, and a last timed launch that was a merged one is no longer there for d3il_last_step_ms - its duration is in d3il_timing_stats
+  if (h->ring_head > 0 && h->ring_alt0[(h->ring_head - 1) % 128]) { h->ev_valid = false; h->ev0 = h->ev1 = nullptr; }
+  for (int i = 0; i < 128; i++) h->ring_alt0[i] = h->ring_alt1[i] = nullptr;
+  int k = 0;
+  for (int i = 0; i < g->count; i++) if (g->m[i] != h) g->m[k++] = g->m[i];
+  g->count = k; h->group = nullptr; h->grp_pending = false;
+}
+int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out) {
+  if (!handles || !out) return fail(D3IL_EINVAL, "d3il_group_create: null argument");
+  *out = nullptr;
+  if (count < 1 || count > AVOID_GROUP_MAX) return fail(D3IL_EINVAL, "d3il_group_create: a group has 1 .. 8 members");
+  for (int i = 0; i < count; i++) {
+    d3il_handle_s* h = handles[i];
+    if (!h) return fail(D3IL_EINVAL, "d3il_group_create: null handle");
+    if (h->task_id != D3IL_TASK_AVOIDING) return fail(D3IL_EUNSUPPORTED, "d3il_group_create: Avoiding handles only");
+    if (h->device != handles[0]->device) return fail(D3IL_EINVAL, "d3il_group_create: the members must live on one device");
+    if (h->group) return fail(D3IL_ESTATE, "d3il_group_create: a handle is already in a group");
+    for (int j = 0; j < i; j++) if (handles[j] == h) return fail(D3IL_EINVAL, "d3il_group_create: a handle is listed twice");
+  }
+  HIPCHK(hipSetDevice(handles[0]->device));
+  // the group forms of the step kernel need the same LDS grant as the three-wave form
+  if (hipFuncSetAttribute((const void*)k_avoiding_step_split<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AVOID_LDS_SERVE) != hipSuccess) (void)hipGetLastError();
+  d3il_group_s* g = new d3il_group_s();
+  g->device = handles[0]->device; g->count = count;
+  for (int i = 0; i < count; i++) { g->m[i] = handles[i]; handles[i]->group = g; handles[i]->grp_pending = false; }
+  *out = g;
+  return D3IL_OK;
+}
+int d3il_group_flush(d3il_group g) {
+  if (!g) return fail(D3IL_EINVAL, "d3il_group_flush: null group");
+  return g->n_pending ? group_flush(g) : D3IL_OK;
+}
+int d3il_group_destroy(d3il_group g) {
+  if (!g) return fail(D3IL_EINVAL, "d3il_group_destroy: null group");
+  (void)hipSetDevice(g->device);
+  const int rc = group_flush(g);
+  while (g->count > 0) group_leave(g->m[g->count - 1]);
+  (void)hipDeviceSynchronize();      // the last merged launch reads the table
+  if (g->ev_made) { for (int i = 0; i < AVOID_GROUP_MAX; i++) (void)hipEventDestroy(g->ev_join[i]); (void)hipEventDestroy(g->ev_done); (void)hipFree(g->d_table); }
+  if (g->ring_created) for (int i = 0; i < 128; i++) { (void)hipEventDestroy(g->ring0[i]); (void)hipEventDestroy(g->ring1[i]); }
+  delete g;
+  return rc;
+}
 int d3il_last_step_ms(d3il_handle h, float* ms) {
+  GROUP_SETTLE(h);
   if (!h || !ms) return fail(D3IL_EINVAL, "d3il_last_step_ms: null argument");
   if (!h->ev_valid) return fail(D3IL_ESTATE, "d3il_last_step_ms: timing not enabled or no step recorded");
   HIPCHK(hipEventSynchronize(h->ev1));
@@ -2163,6 +2414,7 @@ int d3il_debug_stats(uint64_t* out32, int reset) {
 /* diagnostics: one environment's column of the solver scratch area (contact records of its last sub-step; layout in the task's
  * *_step.h) copied to the host */
 int d3il_debug_scratch(d3il_handle h, int env, double* out, int count) {
+  GROUP_SETTLE(h);
   if (!h || !out) return fail(D3IL_EINVAL, "d3il_debug_scratch: null argument");
   if (!h->d_scratch || env < 0 || env >= h->n) return fail(D3IL_EINVAL, "d3il_debug_scratch: no scratch area / env out of range");
   HIPCHK(hipSetDevice(h->device));
@@ -2219,6 +2471,7 @@ int d3il_set_link_guard(d3il_handle h, const double* capsules, int n, double mar
 }
 
 int d3il_set_option(d3il_handle h, const char* name, int value) {
+  GROUP_SETTLE(h);
   if (!h || !name) return fail(D3IL_EINVAL, "d3il_set_option: null argument");
   if (h->rg_ready) { HIPCHK(hipDeviceSynchronize()); rg_drop(h); }      // an option may change what a step launches
   if (std::strcmp(name, "graph_rollout") == 0) { if (int rc_ = drop_prepared_action(h)) return rc_; h->rg_enabled = value != 0; return D3IL_OK; }

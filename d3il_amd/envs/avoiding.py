@@ -31,6 +31,40 @@ def _view(ptr, shape, typestr, device, owner):
     return torch.as_tensor(_DevArray(ptr, shape, typestr, owner), device=device)
 
 
+class StepGroup:
+    """A step group of the library (d3il_group_create, include/d3il_rollout.h): the ``random_rollout_step`` calls that up to 8 Avoiding environments of one
+    device make for one step go out as ONE dispatch.  Between the first and the last call of a round the buffers of the members called so far are not yet
+    advanced; ``flush()`` ends a round early, every other call on a member does so by itself."""
+
+    MAX_MEMBERS = 8
+
+    def __init__(self, envs):
+        envs = list(envs)
+        if not capi.has_step_group():
+            raise capi.D3ilError("the loaded libd3il_rollout has no step group (d3il_group_create)")
+        self.L = capi.load()
+        arr = (C.c_void_p * len(envs))(*[e.h for e in envs])
+        g = C.c_void_p()
+        capi.check(self.L.d3il_group_create(arr, len(envs), C.byref(g)))
+        self.g = g
+
+    def flush(self):
+        if self.g:
+            capi.check(self.L.d3il_group_flush(self.g))
+
+    def close(self):
+        """Ends the round and returns the members to the single-handle path (before the members themselves are closed, or after: a closed member has left)."""
+        if getattr(self, "g", None):
+            self.L.d3il_group_destroy(self.g)
+            self.g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ObstacleAvoidanceVecEnv:
     task = "avoiding"
     action_dim = 7

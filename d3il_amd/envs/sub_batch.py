@@ -92,8 +92,8 @@ class SubBatchSet:
         self.parts = plan(n, n_sub_batches, min_envs)
         self.n = n
         S = len(self.parts)
-        if S > 1:
-            ensure_hw_queues(S)
+        hw_queues = ensure_hw_queues(S) if S > 1 else DEFAULT_HW_QUEUES
+        self.group = None
         if S > MAX_CONCURRENT:
             warnings.warn("%d sub-batches: the GPU runs %d dispatches of different streams at a time, the others wait their turn (DESIGN section 19.6)" % (S, MAX_CONCURRENT))
         self.default_stream = torch.cuda.current_stream(self.device)
@@ -112,6 +112,23 @@ class SubBatchSet:
         if S > 1:
             for b in self.batches:      # set-up work of the sub-batch streams is ordered before whatever the caller does next on its stream
                 self.default_stream.wait_stream(b.stream)
+            self.group = self._step_group(hw_queues)
+
+    def _step_group(self, hw_queues: int):
+        """Avoiding: with fewer hardware queues than the S streams and the null stream need, two sub-batches share a queue and their step launches run one after
+        the other; the library then sends the ``random_rollout_step`` calls of one step as ONE dispatch (a step group).  With a queue per
+        stream nothing is grouped.  ``D3IL_STEP_GROUP=0|1`` overrides the choice (A/B runs)."""
+        envs = [b.env for b in self.batches]
+        want = hw_queues < len(envs) + 1
+        if os.environ.get("D3IL_STEP_GROUP") in ("0", "1"):
+            want = os.environ["D3IL_STEP_GROUP"] == "1"
+        if not want or not all(type(e).__name__ == "ObstacleAvoidanceVecEnv" for e in envs):
+            return None
+        from .avoiding import StepGroup
+        from .. import capi
+        if len(envs) > StepGroup.MAX_MEMBERS or not capi.has_step_group():      # (an older library loaded through D3IL_LIB_PATH: today's path)
+            return None
+        return StepGroup(envs)
 
     def __len__(self):
         return len(self.batches)
@@ -134,6 +151,8 @@ class SubBatchSet:
 
     def join(self):
         """The caller's stream waits for everything queued on the sub-batch streams (no host synchronisation)."""
+        if self.group is not None:
+            self.group.flush()      # a round that not every sub-batch has joined goes out now
         if len(self.batches) > 1:
             for b in self.batches:
                 self.default_stream.wait_stream(b.stream)
@@ -157,6 +176,9 @@ class SubBatchSet:
         return sum(int(getattr(b.env, "link_near_episodes", 0)) for b in self.batches if b.env is not None)
 
     def close(self):
+        if self.group is not None:
+            self.group.close()
+            self.group = None
         for b in self.batches:
             if b.env is not None:
                 b.env.close()

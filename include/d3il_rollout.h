@@ -384,6 +384,34 @@ int d3il_timing_stats(d3il_handle h, double* out4);
  * bit what d3il_step followed by d3il_auto_reset leaves. */
 int d3il_step_auto_reset(d3il_handle h, const double* actions, int64_t* episode_counts_device, void* stream);
 int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream);
+/* Step group (Avoiding): up to 8 handles of one device whose d3il_random_rollout_step calls of one step go out as ONE dispatch of
+ * sum(ceil(n_i / 64)) workgroups on the first member's stream - for processes whose streams outnumber their hardware queues (GPU_MAX_HW_QUEUES; HIP's default
+ * is 4, one of which serves the null stream), where the launches of two sub-batches would share a queue and run one after the other.
+ * A call on a member is ELIGIBLE when it would be the one-launch form on its own: option "fuse_rollout_tail", the split step kernel, d3il_start done, no
+ * "graph_rollout", and it continues the member's sequence (see above).  An eligible call only marks the member pending and returns; the call that makes every
+ * member pending - a ROUND: the same t, n_substeps, max_steps and timing setting for all - launches once.  Results are bit for bit those of the separate launches.
+ * CONTRACT: between the first and the last call of a round the buffers of the pending members are NOT yet advanced, and nothing has been enqueued for them;
+ * d3il_group_flush ends a round early.  Every call that is not eligible (the first call of a sequence, a jump of t, a member called twice, other arguments) and every
+ * other library call on a member that reads or changes its state, buffers, options, timing or tally (d3il_step, d3il_get_state, d3il_reset, d3il_set_option, ...) first
+ * flushes the round - each pending member runs through the single-handle path, in group order - and then runs as it does without a group; a round that is never
+ * completed is exactly the code path of ungrouped handles.  Two calls that take a handle do NOT end a round: d3il_get_buffers, which only hands out the
+ * pointers (what the caller reads through them falls under the contract above), and d3il_set_link_guard, which refuses Avoiding handles.
+ * Stream order as seen by the caller is kept: before the merged launch the first member's stream waits for an event recorded on every other member's stream, after it
+ * every other member's stream waits for the launch.  Work queued on a member's stream before that member's own call of the round, or after the round's last call,
+ * sees what it would see ungrouped.  Work queued on it BETWEEN those two calls is ordered before the step (the event is recorded at the launch), where ungrouped it
+ * would come behind it: that is the contract above seen from the stream.
+ * Timing: every member counts the merged launch as its launch of that step, with the duration of the whole dispatch (one event pair, shared, owned by the group).
+ * A handle that leaves its group reads the durations it still owes from those pairs first, so d3il_timing_stats loses nothing; d3il_last_step_ms of a handle whose
+ * last timed launch was a merged one returns D3IL_ESTATE after it left, until its next timed launch.
+ * Errors: when a HIP call fails inside a flush or a merged launch, the call that triggered it returns the error and the round is abandoned - deferred steps of
+ * members whose calls had already returned D3IL_OK may not have been enqueued, and a member handled before the failure has had its prepared action consumed
+ * without a launch.  The sequences of all members are then undefined: reset them (d3il_reset) before stepping on.
+ * The third wave runs while the dispatch has at most the sum of the members' "serve_wave_max_workgroups" workgroups.  d3il_destroy of a member flushes and leaves
+ * the group; d3il_group_destroy flushes and returns the handles to the single path.  One host thread per group. */
+typedef struct d3il_group_s* d3il_group;
+int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out);
+int d3il_group_flush(d3il_group g);
+int d3il_group_destroy(d3il_group g);
 /* Option "graph_rollout": captures the graphs the next d3il_random_rollout_step calls with these arguments will launch, without launching anything (outside a timed region). */
 int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream);
 
