@@ -144,6 +144,7 @@ VARIANTS = {"gtstatic": ["D3IL_GT_STATIC"],
             "gtinline": ["D3IL_GT_INLINE"],      # the tree solver inlined into the step kernel (no callee-saved register traffic)
             "nsub1": ["D3IL_GEN_NSUB=1"],      # the generic engine with one lane per cube and one physics wave (A/B of the sub-lanes)
             "loneenv": ["D3IL_LONE_PER_ENV=1"],      # lone-cube / tree solver chosen per environment instead of per wave (A/B)
+            "evfence": ["D3IL_EVENT_SYSTEM_FENCE"],      # the library's own events created with their default system-scope fence (A/B)
             "poison": ["D3IL_POISON"], "raw": ["D3IL_SK_PRELOAD_RAW"], "nopreload": ["D3IL_SK_NO_PRELOAD"], "poisonraw": ["D3IL_POISON", "D3IL_SK_PRELOAD_RAW"]}
 
 if __name__ == "__main__":

@@ -1126,7 +1126,21 @@ struct d3il_group_s {
   AvoidGroupTable* d_table; AvoidGroupTable table_host; bool table_valid;
   hipEvent_t ev_join[AVOID_GROUP_MAX], ev_done; bool ev_made;
   hipEvent_t ring0[128], ring1[128]; bool ring_created; long ring_head;      // the shared event pairs of the timed merged launches
+  // option "quiet_streams" (DESIGN section 32): the pre-launch joins of the other members' streams are queued only in an ARMED round - the first one, and
+  // the first after anything but a merged round happened to the group (group_arm).  Off: every round joins.  Host counters: merged rounds, and those that joined
+  bool quiet, armed; int64_t n_merged, n_joined;
 };
+static inline void group_arm(d3il_group_s* g) { g->armed = true; }
+// Creation flags of the library's own events: the ordering events of a step group (ev_join, ev_done) and the timing rings, the
+// group's and every handle's.  hipEventDisableSystemFence: the record carries no system-scope cache writeback and invalidation (measured: about 1.4 us less per
+// record on the launch queue, tools/probe/event_hops.hip).  Nothing reads results through these events: the host sees device memory only behind a stream or
+// device synchronisation or a hipMemcpy, hipEventSynchronize is called for timestamps alone, and a kernel behind a wait acquires at its own start like one
+// behind a same-stream boundary.  -DD3IL_EVENT_SYSTEM_FENCE: the events with their default fence (A/B build "evfence" of d3il_amd/build.py).
+#if defined(D3IL_EVENT_SYSTEM_FENCE)
+constexpr unsigned EV_ORDER_FLAGS = hipEventDisableTiming, EV_TIMING_FLAGS = hipEventDefault;
+#else
+constexpr unsigned EV_ORDER_FLAGS = hipEventDisableTiming | hipEventDisableSystemFence, EV_TIMING_FLAGS = hipEventDefault | hipEventDisableSystemFence;
+#endif
 
 // The Stacking kernels read their model from one __constant__ object per device (scalar loads, no pointer across call boundaries).  Stacking handles on one
 // device therefore have to share the model: d3il_create refuses a different one while another handle is alive (a second model would silently
@@ -1152,9 +1166,14 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 extern "C" {
 
 // Step group: every library call on a member other than an eligible d3il_random_rollout_step ends the round first - the pending members run through the
-// single-handle path, in group order - so that no call sees buffers a deferred step has not advanced yet.
+// single-handle path, in group order - so that no call sees buffers a deferred step has not advanced yet.  Such a call may queue work on the member's stream
+// or change what a step launches: the next merged round joins the members' streams again (group_arm), pending round or not.
 static int group_flush(d3il_group_s* g);
-static inline int group_settle(d3il_handle_s* h) { return (h && h->group && h->group->n_pending && !h->group->busy) ? group_flush(h->group) : D3IL_OK; }
+static inline int group_settle(d3il_handle_s* h) {
+  if (!h || !h->group || h->group->busy) return D3IL_OK;
+  group_arm(h->group);
+  return h->group->n_pending ? group_flush(h->group) : D3IL_OK;
+}
 #define GROUP_SETTLE(h) do { if (int rc_g_ = group_settle(h)) return rc_g_; } while (0)
 
 const char* d3il_last_error(void) { return g_err.c_str(); }
@@ -2026,7 +2045,7 @@ int d3il_set_timing(d3il_handle h, int enabled) {
   if (!h) return fail(D3IL_EINVAL, "d3il_set_timing: null handle");
   HIPCHK(hipSetDevice(h->device));
   if (enabled && !h->ring_created) {
-    for (int i = 0; i < 128; i++) { HIPCHK(hipEventCreate(&h->ring0[i])); HIPCHK(hipEventCreate(&h->ring1[i])); }
+    for (int i = 0; i < 128; i++) { HIPCHK(hipEventCreateWithFlags(&h->ring0[i], EV_TIMING_FLAGS)); HIPCHK(hipEventCreateWithFlags(&h->ring1[i], EV_TIMING_FLAGS)); }
     h->ring_created = true;
   }
   if (h->rg_ready) { HIPCHK(hipDeviceSynchronize()); rg_drop(h); }
@@ -2193,9 +2212,11 @@ static int rollout_step_single(d3il_handle h, uint64_t seed, uint64_t env_offset
 // ---- the step group.  With fewer hardware queues than streams, the step launches of two sub-batches share a queue and run one after
 // the other although each fills a sixteenth of the chip.  A group sends the launches of one step as ONE dispatch on the first member's stream: a call on a
 // member only marks it pending, the call that completes the round launches.  Stream order is kept for the caller: the first member's stream waits for
-// an event on every other member's stream before the launch, and every other member's stream waits for the launch afterwards.
+// an event on every other member's stream before the launch, and every other member's stream waits for the launch afterwards.  Group option "quiet_streams"
+// (DESIGN section 32): the caller queues nothing on those streams between rounds, and only an ARMED round waits before its launch.
 static int group_flush(d3il_group_s* g) {
   if (g->busy) return D3IL_OK;
+  group_arm(g);      // the members launch on their own streams now: the next merged round has to come behind them
   g->busy = true;
   int rc = D3IL_OK;
   for (int i = 0; i < g->count; i++) {
@@ -2210,8 +2231,8 @@ static int group_flush(d3il_group_s* g) {
 static int group_launch_locked(d3il_group_s* g) {
   HIPCHK(hipSetDevice(g->device));
   if (!g->ev_made) {
-    for (int i = 0; i < AVOID_GROUP_MAX; i++) HIPCHK(hipEventCreateWithFlags(&g->ev_join[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
+    for (int i = 0; i < AVOID_GROUP_MAX; i++) HIPCHK(hipEventCreateWithFlags(&g->ev_join[i], EV_ORDER_FLAGS));
+    HIPCHK(hipEventCreateWithFlags(&g->ev_done, EV_ORDER_FLAGS));
     HIPCHK(hipMalloc(&g->d_table, sizeof(AvoidGroupTable)));
     g->ev_made = true;
   }
@@ -2237,7 +2258,10 @@ static int group_launch_locked(d3il_group_s* g) {
     HIPCHK(hipMemcpy(g->d_table, &tab, sizeof tab, hipMemcpyHostToDevice));
     g->table_host = tab; g->table_valid = true;
   }
-  for (int i = 1; i < g->count; i++) {
+  // the join: s0 comes behind everything queued on the other members' streams.  A continuing round of a quiet group queues none: the other streams hold
+  // only their waits for the earlier rounds, and the dispatch follows the previous one on its own queue
+  const bool join = !g->quiet || g->armed;
+  if (join) for (int i = 1; i < g->count; i++) {
     if (g->m[i]->grp_stream == s0) continue;
     HIPCHK(hipEventRecord(g->ev_join[i], g->m[i]->grp_stream));
     HIPCHK(hipStreamWaitEvent(s0, g->ev_join[i], 0));
@@ -2245,7 +2269,7 @@ static int group_launch_locked(d3il_group_s* g) {
   hipEvent_t t0 = nullptr, t1 = nullptr;
   if (g->timing) {
     if (!g->ring_created) {
-      for (int i = 0; i < 128; i++) { HIPCHK(hipEventCreate(&g->ring0[i])); HIPCHK(hipEventCreate(&g->ring1[i])); }
+      for (int i = 0; i < 128; i++) { HIPCHK(hipEventCreateWithFlags(&g->ring0[i], EV_TIMING_FLAGS)); HIPCHK(hipEventCreateWithFlags(&g->ring1[i], EV_TIMING_FLAGS)); }
       g->ring_created = true;
     }
     // a member reads the pair of a slot before the group records it again: a slot comes round after 128 merged launches, and each was a launch of every member
@@ -2278,11 +2302,14 @@ static int group_launch_locked(d3il_group_s* g) {
   } else HIPCHK(hipEventRecord(done_ev, s0));
   for (int i = 1; i < g->count; i++) if (g->m[i]->grp_stream != s0) HIPCHK(hipStreamWaitEvent(g->m[i]->grp_stream, done_ev, 0));
   for (int i = 0; i < g->count; i++) { d3il_handle_s* h = g->m[i]; fused_step_end(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, (void*)h->grp_stream); }
+  g->n_merged++; g->n_joined += join ? 1 : 0;
+  g->armed = false;      // the next round continues this one, unless something else happens to the group first
   return D3IL_OK;
 }
 static int group_launch(d3il_group_s* g) {
   g->busy = true;
   const int rc = group_launch_locked(g);
+  if (rc) group_arm(g);      // a HIP failure: whatever the group does next starts from the joined form
   for (int i = 0; i < g->count; i++) g->m[i]->grp_pending = false;
   g->n_pending = 0; g->busy = false;
   return rc;
@@ -2294,7 +2321,10 @@ static int group_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset,
   if (g->busy) return D3IL_OK;
   const bool eligible = h->fuse_tail && !h->rg_enabled && h->task_id == D3IL_TASK_AVOIDING && actions && episode_counts_device && h->started && split_step_kernel(h) &&
                         h->serve_avail && continues_sequence(h, seed, env_offset, t, actions, stream);
-  if (!eligible) return g->n_pending ? group_flush(g) : D3IL_OK;
+  if (!eligible) {      // (another stream or `actions` buffer, a jump of t, the first call of a sequence: the member launches on its own stream)
+    group_arm(g);
+    return g->n_pending ? group_flush(g) : D3IL_OK;
+  }
   if (g->n_pending && (h->grp_pending || g->t != t || g->n_substeps != h->hc.n_substeps || g->max_steps != h->hc.max_steps || g->timing != h->timing)) {
     if (int rc = group_flush(g)) return rc;      // a second call of a member, or a call that does not fit the round: nothing is merged
   }
@@ -2318,6 +2348,7 @@ static void group_leave(d3il_handle_s* h) {
   d3il_group_s* g = h->group;
   if (!g) return;
   (void)group_flush(g);
+  group_arm(g);      // (also when a flush is running: the table and the first stream may change)
   timing_drain_all(h);
   // nothing of the handle may name an event of the group any more (d3il_group_destroy destroys them, a group that lives on records them again): the ring
   // is drained, and a last timed launch that was a merged one is no longer there for d3il_last_step_ms - its duration is in d3il_timing_stats
@@ -2344,13 +2375,31 @@ int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out) {
   if (hipFuncSetAttribute((const void*)k_avoiding_step_split<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AVOID_LDS_SERVE) != hipSuccess) (void)hipGetLastError();
   d3il_group_s* g = new d3il_group_s();
   g->device = handles[0]->device; g->count = count;
+  g->armed = true;      // the first merged round comes behind the members' single launches
   for (int i = 0; i < count; i++) { g->m[i] = handles[i]; handles[i]->group = g; handles[i]->grp_pending = false; }
   *out = g;
   return D3IL_OK;
 }
 int d3il_group_flush(d3il_group g) {
   if (!g) return fail(D3IL_EINVAL, "d3il_group_flush: null group");
+  group_arm(g);      // the caller's re-arming point of "quiet_streams", pending round or not
   return g->n_pending ? group_flush(g) : D3IL_OK;
+}
+int d3il_group_set_option(d3il_group g, const char* name, int value) {
+  if (!g || !name) return fail(D3IL_EINVAL, "d3il_group_set_option: null argument");
+  if (std::strcmp(name, "quiet_streams") == 0) {
+    if (value != 0 && value != 1) return fail(D3IL_EINVAL, "quiet_streams must be 0 or 1");
+    group_arm(g);
+    if (g->n_pending) { if (int rc = group_flush(g)) return rc; }      // a round that has begun ends under the setting it began with
+    g->quiet = value != 0;
+    return D3IL_OK;
+  }
+  return fail(D3IL_EINVAL, std::string("d3il_group_set_option: unknown option ") + name);
+}
+int d3il_group_stats(d3il_group g, int64_t* merged_rounds, int64_t* joined_rounds) {
+  if (!g || !merged_rounds || !joined_rounds) return fail(D3IL_EINVAL, "d3il_group_stats: null argument");
+  *merged_rounds = g->n_merged; *joined_rounds = g->n_joined;      // host counters: no flush, no device access
+  return D3IL_OK;
 }
 int d3il_group_destroy(d3il_group g) {
   if (!g) return fail(D3IL_EINVAL, "d3il_group_destroy: null group");

@@ -34,11 +34,18 @@ def _view(ptr, shape, typestr, device, owner):
 class StepGroup:
     """A step group of the library (d3il_group_create, include/d3il_rollout.h): the ``random_rollout_step`` calls that up to 8 Avoiding environments of one
     device make for one step go out as ONE dispatch.  Between the first and the last call of a round the buffers of the members called so far are not yet
-    advanced; ``flush()`` ends a round early, every other call on a member does so by itself."""
+    advanced; ``flush()`` ends a round early, every other call on a member does so by itself.
+
+    ``quiet_streams=True`` (option "quiet_streams" of the library) is a promise of the caller: between two merged rounds it queues nothing
+    on the members' streams - the first member's excepted - that reads or writes what the step touches (the members' buffers, ``actions``, counters, tally).
+    The rounds of a running sequence then follow each other on the first member's stream without the join through the other streams.  ``flush()`` (and
+    every other library call on a member) re-arms the join for the next merged round: call it before a round that has to see a write queued on another
+    member's stream, and before queueing a read there that the NEXT round must not overtake.  Work queued on a member's stream after a round still sees
+    that round."""
 
     MAX_MEMBERS = 8
 
-    def __init__(self, envs):
+    def __init__(self, envs, quiet_streams: bool = False):
         envs = list(envs)
         if not capi.has_step_group():
             raise capi.D3ilError("the loaded libd3il_rollout has no step group (d3il_group_create)")
@@ -47,8 +54,22 @@ class StepGroup:
         g = C.c_void_p()
         capi.check(self.L.d3il_group_create(arr, len(envs), C.byref(g)))
         self.g = g
+        if quiet_streams:
+            self.set_option("quiet_streams", 1)
+
+    def set_option(self, name: str, value: int):
+        if not capi.has_group_options():
+            raise capi.D3ilError("the loaded libd3il_rollout has no group options (d3il_group_set_option)")
+        capi.check(self.L.d3il_group_set_option(self.g, name.encode(), int(value)))
+
+    def stats(self):
+        """(merged rounds, merged rounds that joined the other members' streams before the launch) since the group was created; host counters."""
+        merged, joined = C.c_int64(), C.c_int64()
+        capi.check(self.L.d3il_group_stats(self.g, C.byref(merged), C.byref(joined)))
+        return merged.value, joined.value
 
     def flush(self):
+        """Ends a round early; with ``quiet_streams`` also the caller's re-arming point: the next merged round joins the members' streams again."""
         if self.g:
             capi.check(self.L.d3il_group_flush(self.g))
 

@@ -85,6 +85,13 @@ class SubBatchSet:
 
     make_env(count, offset) -> environment (constructed under the sub-batch's stream; the set then binds the stream to the handle, so every library
     call of that environment - step, reset, auto-reset, tally - is launched on it without a stream context per call).
+
+    THE RULE when the set has formed a step group (``self.group``; Avoiding with fewer hardware queues than streams): the group runs with the library's
+    ``quiet_streams`` option, so between two ``random_rollout_step`` rounds the caller queues nothing on the sub-batch streams that reads or writes what the
+    step touches (the environments' buffers, ``actions``, episode counters, tally) - except on the first sub-batch's stream, or after ``join()``.
+    ``join()`` flushes the group, which re-arms the library's join of the streams: torch work queued on any sub-batch stream before ``join()`` is ordered
+    before the next round, work queued after a round sees that round.  Library calls on an environment (reset, get_state, options, timing) re-arm by
+    themselves.  Without a group every stream is ordered as usual.
     """
 
     def __init__(self, n: int, n_sub_batches: int, device, make_env, min_envs: int = MIN_ENVS):
@@ -117,7 +124,8 @@ class SubBatchSet:
     def _step_group(self, hw_queues: int):
         """Avoiding: with fewer hardware queues than the S streams and the null stream need, two sub-batches share a queue and their step launches run one after
         the other; the library then sends the ``random_rollout_step`` calls of one step as ONE dispatch (a step group).  With a queue per
-        stream nothing is grouped.  ``D3IL_STEP_GROUP=0|1`` overrides the choice (A/B runs)."""
+        stream nothing is grouped.  ``D3IL_STEP_GROUP=0|1`` overrides the choice (A/B runs).  The group runs with ``quiet_streams`` (the
+        rule is in the class docstring) where the library has the option."""
         envs = [b.env for b in self.batches]
         want = hw_queues < len(envs) + 1
         if os.environ.get("D3IL_STEP_GROUP") in ("0", "1"):
@@ -128,7 +136,7 @@ class SubBatchSet:
         from .. import capi
         if len(envs) > StepGroup.MAX_MEMBERS or not capi.has_step_group():      # (an older library loaded through D3IL_LIB_PATH: today's path)
             return None
-        return StepGroup(envs)
+        return StepGroup(envs, quiet_streams=capi.has_group_options())
 
     def __len__(self):
         return len(self.batches)
@@ -138,7 +146,8 @@ class SubBatchSet:
 
     def each(self, fn):
         """fn(sub_batch) for every sub-batch with torch's current stream set to the sub-batch's (the policy's torch kernels go there); the caller's
-        stream is restored afterwards."""
+        stream is restored afterwards.  Under a step group (class docstring): torch work that fn queues on a sub-batch stream and that touches what the
+        Avoiding rollout step touches needs a ``join()`` before the next round."""
         if len(self.batches) == 1:
             fn(self.batches[0])
             return
@@ -150,9 +159,10 @@ class SubBatchSet:
             torch.cuda.set_stream(self.default_stream)
 
     def join(self):
-        """The caller's stream waits for everything queued on the sub-batch streams (no host synchronisation)."""
+        """The caller's stream waits for everything queued on the sub-batch streams (no host synchronisation).  The set's synchronisation point: under a
+        step group it also re-arms the group, so the next round is ordered behind what the sub-batch streams hold by then."""
         if self.group is not None:
-            self.group.flush()      # a round that not every sub-batch has joined goes out now
+            self.group.flush()      # a round that not every sub-batch has joined goes out now; the next merged round joins the streams again
         if len(self.batches) > 1:
             for b in self.batches:
                 self.default_stream.wait_stream(b.stream)

@@ -407,10 +407,27 @@ int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, 
  * members whose calls had already returned D3IL_OK may not have been enqueued, and a member handled before the failure has had its prepared action consumed
  * without a launch.  The sequences of all members are then undefined: reset them (d3il_reset) before stepping on.
  * The third wave runs while the dispatch has at most the sum of the members' "serve_wave_max_workgroups" workgroups.  d3il_destroy of a member flushes and leaves
- * the group; d3il_group_destroy flushes and returns the handles to the single path.  One host thread per group. */
+ * the group; d3il_group_destroy flushes and returns the handles to the single path.  One host thread per group.
+ *
+ * Group option "quiet_streams" (d3il_group_set_option; default 0 = everything above holds for every round).  With 1 the caller DECLARES:
+ * between two merged rounds it queues nothing on the members' streams that reads or writes memory the step touches - the members' buffers, `actions`, the
+ * episode counters, the tally - except on the FIRST member's stream, which stays fully ordered.  The library then keeps the post-launch waits (after every
+ * round every other member's stream waits for the launch: work queued on a member's stream after a round sees that round, as above) but queues the
+ * pre-launch joins - the event on every other member's stream and the first member's wait for it - only in an ARMED round.  A round is armed when it is the
+ * first merged round of the group, or the first after any of: a flush of a round (a call that is not eligible or does not fit, d3il_group_flush), any library
+ * call on a member other than a merged d3il_random_rollout_step (pending round or not), a member leaving, another stream or `actions` buffer of a member,
+ * a switch of this option, a HIP failure.  Every other round CONTINUES the previous one: nothing is recorded or waited for before the launch, the dispatch
+ * follows the previous one on the first member's stream.  d3il_group_flush is the caller's re-arming point: it arms the next merged round also when no
+ * round is pending.  THE HAZARD, in both directions: a write queued on another member's stream before a continuing round is NOT ordered before that step;
+ * and a read queued there after round N is ordered behind round N but NOT before round N+1, which may overwrite what it reads.  In both cases call d3il_group_flush
+ * after queueing that work and before the next round (the armed round joins what the streams hold when it launches), or use the first member's stream.
+ * d3il_group_stats: merged rounds and merged rounds that joined, since the group was created; plain host counters (no flush, no device access).  With the
+ * option off the two are equal. */
 typedef struct d3il_group_s* d3il_group;
 int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out);
 int d3il_group_flush(d3il_group g);
+int d3il_group_set_option(d3il_group g, const char* name, int value);
+int d3il_group_stats(d3il_group g, int64_t* merged_rounds, int64_t* joined_rounds);
 int d3il_group_destroy(d3il_group g);
 /* Option "graph_rollout": captures the graphs the next d3il_random_rollout_step calls with these arguments will launch, without launching anything (outside a timed region). */
 int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream);
