@@ -29,6 +29,7 @@ constexpr int WAVE = 64;
 #include "policy_ddpm_gpt.h"
 #include "policy_ibc.h"
 #include "policy_act.h"
+#include "policy_ddpm_act.h"
 
 namespace d3il {
 
@@ -1880,6 +1881,30 @@ int d3il_act_chunk_f32(const float* state, const float* w_in, const float* tab, 
             (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, T, n_enc, n_dec};
   // one workgroup of four waves per 16 environments
   hipLaunchKernelGGL(k_act_chunk, dim3((unsigned)((n_env + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_ddpm_act_chunk_f32(const float* window, const int64_t* len, const float* w_in, const float* tab, const float* enc_w, const float* enc_v, const float* dec_w,
+                            const float* dec_v, const float* head_w, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed,
+                            uint64_t env_offset, const uint32_t* t_device, const float* noise_in, const float* x_in, int32_t* counter, float* chunk, float* actions,
+                            int32_t* bad, float* x_out, float* noise_out, long n_env, int obs_dim, int A, int obs_seq_len, int action_seq_len, int width, int n_head,
+                            int n_enc, int n_dec, int n_timesteps, int linear_head, int k_start, int k_stop, void* stream) {
+  if (width != ACT_C || n_head != ACT_NH || obs_dim < 1 || obs_dim > ACT_OBSMAX || A < 1 || A > ACT_AMAX || obs_seq_len < 1 || obs_seq_len > DA_SMAX || action_seq_len < 1 ||
+      action_seq_len > DA_TAMAX || n_enc < 1 || n_enc > ACT_MAXENC || n_dec < 1 || n_dec > ACT_MAXDEC || n_timesteps < 1 || n_timesteps > DA_TMAX || linear_head != 1 ||
+      n_env > 0x7FFFFFFFL)
+    return fail(D3IL_EUNSUPPORTED, "d3il_ddpm_act_chunk_f32: built for width 64 in 4 heads, obs_dim 1 .. 32, 1 .. 8 action components, obs_seq_len 1 .. 5, action_seq_len 1 .. 4, 1 .. 4 encoder and 1 .. 8 decoder layers, 1 .. 255 timesteps and a linear head");
+  if (!window || !len || !w_in || !tab || !enc_w || !enc_v || !dec_w || !dec_v || !head_w || !lo || !hi || !scale || !shift || !t_device || !counter || !chunk || !actions)
+    return fail(D3IL_EINVAL, "d3il_ddpm_act_chunk_f32: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_ddpm_act_chunk_f32: negative environment count");
+  if (k_start < 0) { k_start = n_timesteps - 1; k_stop = 0; }      // the whole chain
+  else if (k_stop < 0 || k_stop > k_start + 1 || k_start > n_timesteps - 1) return fail(D3IL_EINVAL, "d3il_ddpm_act_chunk_f32: 0 <= k_stop <= k_start + 1 <= n_timesteps");
+  if (((uintptr_t)w_in | (uintptr_t)tab | (uintptr_t)enc_w | (uintptr_t)enc_v | (uintptr_t)dec_w | (uintptr_t)dec_v | (uintptr_t)head_w) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_ddpm_act_chunk_f32: the packed weights and tables must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  DdpmActArgs a{window, (const long long*)len, w_in, tab, enc_w, enc_v, dec_w, dec_v, head_w, lo, hi, scale, shift, t_device, noise_in, x_in, counter, chunk, actions, bad, x_out,
+                noise_out, (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, obs_seq_len, action_seq_len, n_enc, n_dec, n_timesteps, k_start, k_stop};
+  // one workgroup of four waves per 16 environments
+  hipLaunchKernelGGL(k_ddpm_act_chunk, dim3((unsigned)((n_env + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -2755,3 +2755,500 @@ class CVAEPolicy:
                 p.requires_grad_(False)
         sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
         return cls(net.to(device), sc, latent_dim, seed=policy_seed, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ DDPM-ACT: encoder-decoder diffusion sampler that emits action chunks
+DDPM_ACT_TAG = 0x44410000     # fourth Philox counter word of the chain kernel, or-ed with k << 8 | j << 1 | q (csrc/policy_ddpm_act.h; never 0, never a word of the five tags above)
+
+
+def ddpm_act_words(seed: int, env_offset: int, n: int, t: int, k: int, Ta: int):
+    """The Philox words behind ``ddpm_act_normals``: uint32 [n, Ta, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
+    DDPM_ACT_TAG | k << 8 | j << 1 | q)), j the action token."""
+    import numpy as np
+    assert 1 <= k <= 255 and 1 <= Ta <= 4, "the counter layout holds k <= 255; chain index 0 is never drawn; chunks of at most 4"
+    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1, 1)
+    j = np.arange(Ta, dtype=np.uint64).reshape(1, Ta, 1)
+    q = np.arange(2, dtype=np.uint64).reshape(1, 1, 2)
+    tag = np.uint64(DDPM_ACT_TAG | (k << 8)) | (j << np.uint64(1)) | q
+    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+
+
+def ddpm_act_normals(seed: int, env_offset: int, n: int, t: int, k: int, Ta: int, A: int):
+    """The chain kernel's normals of environments 0 .. n-1 at step word t and chain index k (T = the first iterate, i = reverse step i), on the host: float64
+    [n, Ta, A].  Exact on the 32-bit words and f64 from there on, Box-Muller as ``ddpm_gpt_normals``; component a = 4 q + m."""
+    import numpy as np
+    assert 1 <= A <= 8
+    r = ddpm_act_words(seed, env_offset, n, t, k, Ta)
+    out = np.zeros((n, Ta, 2, 4))
+    for p in range(2):
+        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+        rad = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
+    return out.reshape(n, Ta, 8)[:, :, :A]
+
+
+def ddpm_act_reference_shapes(obs_dim: int, action_dim: int, obs_seq_len: int, action_seq_len: int, C: int = 64, enc_layers: int = 2, dec_layers: int = 4) -> dict:
+    """Name -> shape of every parameter of the reference's DiffusionEncDec with a linear head (diffusion_models.py:687-765; the mask buffers are not parameters), in
+    the reference's ``named_parameters()`` order: what ``ddpm_act_synthetic_state`` is drawn over."""
+    out = {"pos_emb": (1, obs_seq_len - 1 + action_seq_len, C)}
+    for stack, n, cross in (("encoder", enc_layers, False), ("decoder", dec_layers, True)):
+        for i in range(n):
+            p = "%s.blocks.%d." % (stack, i)
+            out[p + "ln1.weight"] = out[p + "ln2.weight"] = (C,)
+            for l in ("key", "query", "value") + (("cross_key", "cross_query", "cross_value") if cross else ()) + ("proj",):
+                out[p + "attn.%s.weight" % l], out[p + "attn.%s.bias" % l] = (C, C), (C,)
+            out[p + "mlp.0.weight"], out[p + "mlp.0.bias"], out[p + "mlp.2.weight"], out[p + "mlp.2.bias"] = (4 * C, C), (4 * C,), (C, 4 * C), (C,)
+        out[stack + ".ln.weight"] = (C,)
+    out.update({"tok_emb.weight": (C, obs_dim), "tok_emb.bias": (C,), "time_emb.1.weight": (2 * C, C), "time_emb.1.bias": (2 * C,), "time_emb.3.weight": (C, 2 * C),
+                "time_emb.3.bias": (C,), "action_emb.weight": (C, action_dim), "action_emb.bias": (C,), "action_pred.weight": (action_dim, C), "action_pred.bias": (action_dim,)})
+    return out
+
+
+DDPM_ACT_HEAD_ALIGN = 3.0
+
+
+def ddpm_act_synthetic_state(shapes: dict, seed: int) -> dict:
+    """Fixed-seed weights of trained-like magnitudes for a DiffusionEncDec-shaped state dict (there are no checkpoints offline; the reference's initialisation, std
+    0.02 and zero biases, makes the network nearly linear): the rule of ``act_synthetic_state`` - one np.random.RandomState(seed), drawn in sorted key order,
+    matrices N(0, 1) 1.2 / sqrt(fan-in), LayerNorm weights 1 + 0.15 N, biases 0.2 N, the position table 0.4 N, all rounded to f32.  One trait of a trained
+    denoiser is added afterwards: row a of the noise head ``action_pred`` gets DDPM_ACT_HEAD_ALIGN times the direction in which ``action_emb`` writes component a
+    into the residual stream (column a over its squared norm), so that the noise estimate follows the iterate.  A head that ignores the iterate makes
+    x0 = sqrt(1 / ac) x - sqrt(1 / ac - 1) eps grow from step to step and EVERY chain ends on the clamp bounds; with it some final entries sit on a bound and most
+    do not."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    out = {}
+    for k in sorted(shapes):
+        shape = tuple(shapes[k])
+        z = rs.standard_normal(shape)
+        leaf = k.split(".")
+        if leaf[-1] == "weight" and leaf[-2] in ("ln", "ln1", "ln2"):
+            v = 1.0 + 0.15 * z
+        elif leaf[-1] == "bias":
+            v = 0.2 * z
+        elif leaf[-1] == "weight" and len(shape) == 2:
+            v = z * (1.2 / math.sqrt(shape[1]))
+        else:
+            v = 0.4 * z
+        out[k] = v.astype(np.float32)
+    if "action_pred.weight" in out and "action_emb.weight" in out:      # the trained trait: the noise estimate follows the iterate
+        e = out["action_emb.weight"].astype(np.float64)
+        out["action_pred.weight"] = (out["action_pred.weight"] + DDPM_ACT_HEAD_ALIGN * (e / (e * e).sum(axis=0, keepdims=True)).T).astype(np.float32)
+    return out
+
+
+class EncDecDenoiser(nn.Module):
+    """The inference path of the reference's DiffusionEncDec (diffusion_models.py:687-905), not goal conditioned, under the reference's parameter names - ``pos_emb``,
+    ``encoder.*``, ``decoder.*``, ``tok_emb``, ``time_emb.1 / .3``, ``action_emb``, ``action_pred``, registered in the reference's order - so the entries of
+    ``Diffusion.state_dict()`` under ``model.`` load with ``load_state_dict`` and EMA shadow lists zip onto ``parameters()``.  Encoder input [time token, state
+    tokens + pos[0:L]] through ``_ActStack`` with its causal mask; the action tokens add pos[L-1 : L-1+Ta] - the offset follows the window length L -; the decoder
+    attends causally over the action tokens and unmasked over all 1 + L encoder rows."""
+
+    def __init__(self, state_dim, action_dim, embed_dim=64, n_heads=4, enc_layers=2, dec_layers=4, obs_seq_len=5, action_seq_len=4, block_size=9, linear_output=True):
+        super().__init__()
+        assert block_size >= 1 + obs_seq_len and block_size >= action_seq_len, "the causal masks are block_size wide: they must cover 1 + obs_seq_len encoder tokens"
+        self.encoder = _ActStack(embed_dim, n_heads, enc_layers, block_size, False)
+        self.decoder = _ActStack(embed_dim, n_heads, dec_layers, block_size, True)
+        self.tok_emb = nn.Linear(state_dim, embed_dim)
+        self.pos_emb = nn.Parameter(torch.zeros(1, obs_seq_len - 1 + action_seq_len, embed_dim))
+        self.time_emb = nn.Sequential(_SinusoidalPosEmb(embed_dim), nn.Linear(embed_dim, embed_dim * 2), nn.Mish(), nn.Linear(embed_dim * 2, embed_dim))
+        self.action_emb = nn.Linear(action_dim, embed_dim)
+        self.action_pred = nn.Linear(embed_dim, action_dim) if linear_output else nn.Sequential(nn.Linear(embed_dim, 100), nn.GELU(), nn.Linear(100, action_dim))
+        self.goal_conditioned = False
+        self.state_dim, self.action_dim, self.embed_dim, self.n_heads, self.linear_output = state_dim, action_dim, embed_dim, n_heads, bool(linear_output)
+        self.obs_seq_len, self.action_seq_len, self.block_size = obs_seq_len, action_seq_len, block_size
+
+    def time_tokens(self, time):
+        """time_emb of integer chain steps [b] -> [b, C], the sinusoid's frequencies in the parameters' dtype (the reference builds them in the default dtype)."""
+        dt, half = self.tok_emb.weight.dtype, self.embed_dim // 2
+        freq = torch.exp(torch.arange(half, device=time.device).to(dt) * -(math.log(10000) / (half - 1)))
+        emb = time.reshape(-1).to(dt)[:, None] * freq[None, :]
+        x = torch.cat((emb.sin(), emb.cos()), dim=-1)
+        for layer in list(self.time_emb)[1:]:
+            x = layer(x)
+        return x
+
+    def encode(self, time, states):
+        """The encoder output [b, 1 + L, C] of chain step ``time`` [b] on the window ``states`` [b, L, obs]: it does not depend on the iterate."""
+        L = states.shape[1]
+        return self.encoder(torch.cat([self.time_tokens(time).unsqueeze(1), self.tok_emb(states) + self.pos_emb[:, :L]], dim=1))
+
+    def decode(self, actions, enc):
+        L = enc.shape[1] - 1
+        Ta = actions.shape[1]
+        return self.action_pred(self.decoder(self.action_emb(actions) + self.pos_emb[:, L - 1:L - 1 + Ta], enc))
+
+    def forward(self, actions, time, states, goals=None):
+        """The reference's forward without goals: eps [b, Ta, A] for actions [b, Ta, A], time [b] (integers) and states [b, L, state_dim], 1 <= L <= obs_seq_len."""
+        assert actions.shape[1] == self.action_seq_len and 1 <= states.shape[1] <= self.obs_seq_len
+        return self.decode(actions, self.encode(time, states))
+
+
+def pack_ddpm_act_weights(net: EncDecDenoiser, n_timesteps: int) -> dict:
+    """EncDecDenoiser in the operand order of csrc/policy_ddpm_act.h (width 64, obs <= 32, obs_seq_len <= 5, action_seq_len <= 4, A <= 8, linear head): every matrix
+    through ``pack_tiles``; w_in = [tok_emb (columns padded to 32) | action_emb (columns padded to 16)]; the per-layer arrays enc_w, enc_v, dec_w, dec_v in the order of
+    ``pack_act_weights``; head_w = action_pred (rows padded to 16); tab = [pos_emb (padded to 8 rows) | encoder.ln | decoder.ln | tok_emb bias | action_emb bias | head
+    bias (padded to 16) | temb [T][64] = the module's own time_emb of steps 0 .. T-1 in f32 | sched [T][5] = ddpm_schedule of the cosine betas]."""
+    assert net.embed_dim == 64 and net.state_dim <= 32 and net.action_dim <= 8 and net.obs_seq_len <= 5 and net.action_seq_len <= 4 and net.linear_output
+    flat = lambda *xs: torch.cat([x.detach().to(torch.float32).reshape(-1) for x in xs])
+    dev = net.pos_emb.device
+    te = torch.zeros(64, 32, device=dev)
+    te[:, :net.state_dim] = net.tok_emb.weight.detach()
+    pos = torch.zeros(8, 64, device=dev)
+    pos[:net.pos_emb.shape[1]] = net.pos_emb.detach()[0]
+    hb = torch.zeros(16, device=dev)
+    hb[:net.action_dim] = net.action_pred.bias.detach()
+    enc_w, enc_v, dec_w, dec_v = [], [], [], []
+    for b in net.encoder.blocks:
+        a = b.attn
+        enc_w.append(flat(*[pack_tiles(l.weight) for l in (a.query, a.key, a.value, a.proj, b.mlp[0], b.mlp[2])]))
+        enc_v.append(flat(b.ln1.weight, b.ln2.weight, a.query.bias, a.key.bias, a.value.bias, a.proj.bias, b.mlp[0].bias, b.mlp[2].bias))
+    for b in net.decoder.blocks:
+        a = b.attn
+        dec_w.append(flat(*[pack_tiles(l.weight) for l in (a.query, a.key, a.value, a.cross_query, a.cross_key, a.cross_value, a.proj, b.mlp[0], b.mlp[2])]))
+        dec_v.append(flat(b.ln1.weight, b.ln2.weight, a.query.bias, a.key.bias, a.value.bias, a.cross_query.bias, a.cross_key.bias, a.cross_value.bias, a.proj.bias, b.mlp[0].bias, b.mlp[2].bias))
+    temb = net.time_tokens(torch.arange(n_timesteps, device=dev))
+    sched = ddpm_schedule(cosine_beta_schedule(n_timesteps).to(dev))["sched"]
+    return {"w_in": flat(pack_tiles(te), pack_tiles(net.action_emb.weight)),
+            "tab": flat(pos, net.encoder.ln.weight, net.decoder.ln.weight, net.tok_emb.bias, net.action_emb.bias, hb, temb, sched),
+            "enc_w": torch.stack(enc_w), "enc_v": torch.stack(enc_v), "dec_w": torch.stack(dec_w), "dec_v": torch.stack(dec_v), "head_w": flat(pack_tiles(net.action_pred.weight))}
+
+
+class DDPMACTPolicy:
+    """DiffusionAgent.predict of the encoder-decoder agent without goals (agents/ddpm_encdec_agent.py:222-257) around Diffusion.sample (diffusion_policy.py:117-217)
+    and DiffusionEncDec.forward (diffusion_models.py:844-905), on a batch: the scaled observation enters the lane's window (deque maxlen obs_seq_len S) on EVERY
+    step; a lane whose ``counter`` equals the chunk length Ta is due and samples a new chunk of Ta actions from its window as it stands (L entries, 1 <= L <= S; the
+    first step of an episode computes with L = 1): first iterate = noise, T reverse steps - epsilon prediction, x0 clipped to the data bounds in scaled space,
+    posterior mean, posterior noise except at step 0 -, final clamp, inverse scaling as two f32 operations; every lane then emits chunk[counter] and counts on.
+    ``reset()`` clears every window and makes all lanes due, ``begin_episodes(mask)`` the masked ones.
+
+    All per-lane state lives on the device: ``counter``, ``chunk``, the window (``hist``, kept in place), its lengths, the step word.  On a HIP device the whole call
+    is ONE kernel (csrc/policy_ddpm_act.h through d3il_ddpm_act_chunk_f32: width 64, 4 heads, obs <= 32, A <= 8, S <= 5, Ta <= 4, at most 4 encoder and 8 decoder
+    layers, T <= 255, linear head) on the window in its ``padded()`` form, then a device-side add on the step word; lanes with different L and different counters
+    run in one batch, and a call in which no lane of a 16-lane tile is due costs that tile only the emit.  On the CPU, for other shapes and with
+    D3IL_POLICY_DDPM_ACT_FUSED=0 the same arithmetic runs as torch ops (``_chain_torch``, lanes grouped by L on the host) with the Philox normals computed on the
+    host - that path cannot be captured.  Noise: Box-Muller on Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word, DDPM_ACT_TAG | k << 8 |
+    j << 1 | q) - chain index k = T for the first iterate, i for reverse step i; index 0 is never drawn -, so results do not depend on batch order, sub-batches or
+    ranks (``ddpm_act_normals`` is the host form); or ``noise_in(n) -> [n, T + 1, Ta, A]`` (index = chain index) when given (golden replay, tests).  A NaN / Inf in
+    a due lane's valid window rows, head outputs or iterates marks the lane (``last_bad``) and gives it a NaN chunk (D3IL_FLAG_SOLVER_FAIL in that lane's steps)."""
+
+    def __init__(self, model: EncDecDenoiser, scaler: Scaler, n_timesteps: int, obs_seq_len: int | None = None, seed: int = 0, n_envs: int | None = None, noise_in=None):
+        self.model, self.scaler, self.T = model.eval(), scaler, int(n_timesteps)
+        self.S = int(model.obs_seq_len if obs_seq_len is None else obs_seq_len)
+        self.Ta, self.A, self.obs_dim = int(model.action_seq_len), int(model.action_dim), int(model.state_dim)
+        assert 1 <= self.T <= 255 and 1 <= self.Ta <= 4 and 1 <= self.A <= 8, "the Philox counter layout holds T <= 255, chunks of at most 4 tokens and 8 components"
+        assert 1 <= self.S <= model.obs_seq_len, "the window cannot exceed the denoiser's obs_seq_len"
+        assert scaler.y_bounds is not None and tuple(scaler.y_bounds.shape) == (2, self.A), "DDPMACTPolicy clamps to the scaler's y_bounds"
+        dev = scaler.x_mean.device
+        self.device = dev
+        self._sched = ddpm_schedule(cosine_beta_schedule(self.T).to(dev))["sched"]
+        f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
+        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
+        self.seed, self.env_offset, self.n_envs, self.noise_in = int(seed), 0, n_envs, noise_in
+        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self._packed = PackedWeights()
+        self.counter = self.chunk = self.hist = self.last_bad = None      # per-lane state: i32 [N], f32 [N, Ta, A] (clamped, inverse-scaled), the window, i32 [N]
+        self.record = False           # also keep the chunk table and what was drawn after every call (last_chunk, last_noise [N, T + 1, Ta, A]: zero where nothing was drawn)
+        self.last_chunk = self.last_noise = None
+        if n_envs is not None:
+            self._state(int(n_envs))
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, n_envs: int | None = None, device=None, noise_in=None):
+        """From a live reference enc-dec ``DiffusionAgent`` (duck-typed) whose ``model`` is a ``Diffusion`` around a ``DiffusionEncDec``: the denoiser's state dict,
+        ``n_timesteps``, ``agent.scaler``, ``agent.obs_seq_len``; with ``agent.use_ema`` the EMA shadow parameters (the reference swaps them in for every predict)."""
+        diff = agent.model
+        net = diff.model
+        sd = {k: torch.as_tensor(v) for k, v in net.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["tok_emb.weight"].device
+        C, state_dim = sd["tok_emb.weight"].shape
+        A, Ta = sd["action_emb.weight"].shape[1], int(net.action_seq_len)
+        layers = lambda p: len({k.split(".")[2] for k in sd if k.startswith(p + ".blocks.")})
+        den = EncDecDenoiser(state_dim, A, C, int(net.encoder.blocks[0].attn.n_head), layers("encoder"), layers("decoder"), sd["pos_emb"].shape[1] - Ta + 1, Ta,
+                             int(net.encoder.blocks[0].attn.mask.shape[-1]), linear_output="action_pred.weight" in sd)
+        own = den.state_dict()
+        den.load_state_dict({k: sd[k].to(own[k].dtype) for k in own})
+        den = den.to(dev)
+        for p in den.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        pol = cls(den, Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev), int(diff.n_timesteps), obs_seq_len=int(agent.obs_seq_len), seed=seed,
+                  n_envs=n_envs, noise_in=noise_in)
+        if getattr(agent, "use_ema", False):
+            pol.use_ema(agent.ema_helper.shadow_params)
+        return pol
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: the reference's DiffusionAgent around a DiffusionEncDec without goals (``encoder`` / ``decoder`` stacks of one
+        width, LayerNorms without bias, exact GELU, masks that cover 1 + obs_seq_len tokens), configured as the sampler restated here (``model.betas`` = the cosine
+        schedule, epsilon prediction, clip_denoised, neither diffusion_x nor diffusion_kde)?  The GPT denoiser (``blocks``) and the MLP denoiser do not; everything
+        else stays on the row-by-row adapter, which runs the reference's own code."""
+        try:
+            diff = agent.model
+            net = diff.model
+            if not all(hasattr(net, k) for k in ("encoder", "decoder", "time_emb", "action_emb", "tok_emb", "pos_emb", "action_pred", "state_dict")) or hasattr(net, "blocks"):
+                return False
+            if net.goal_conditioned is not False or getattr(agent, "goal_condition", False) or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None:
+                return False
+            if getattr(diff, "diffusion_x", False) or getattr(agent, "diffusion_kde", False) or not getattr(diff, "predict_epsilon", True) or not getattr(diff, "clip_denoised", True):
+                return False
+            T = int(diff.n_timesteps)
+            betas = torch.as_tensor(diff.betas).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+            if not (1 <= T <= 255 and betas.shape[0] == T and bool(torch.equal(betas, cosine_beta_schedule(T)))):
+                return False
+            C, Ta, S = int(net.tok_emb.out_features), int(agent.action_seq_size), int(agent.obs_seq_len)
+            if Ta != int(net.action_seq_len) or not 1 <= Ta <= 4 or not 1 <= S <= int(net.obs_seq_len) or tuple(net.pos_emb.shape) != (1, int(net.obs_seq_len) - 1 + Ta, C):
+                return False
+            if net.tok_emb.bias is None or net.action_emb.bias is None or int(net.action_emb.out_features) != C or not 1 <= int(net.action_emb.in_features) <= 8:
+                return False
+            if not (isinstance(net.time_emb[1], nn.Linear) and isinstance(net.time_emb[2], nn.Mish) and isinstance(net.time_emb[3], nn.Linear)):
+                return False
+            if (net.time_emb[1].in_features, net.time_emb[1].out_features, net.time_emb[3].in_features, net.time_emb[3].out_features) != (C, 2 * C, 2 * C, C):
+                return False
+            heads = set()
+            for stack, cross in ((net.encoder, False), (net.decoder, True)):
+                if tuple(stack.ln.weight.shape) != (C,) or getattr(stack.ln, "bias", None) is not None or len(stack.blocks) < 1:
+                    return False
+                for b in stack.blocks:
+                    a = b.attn
+                    lins = [a.key, a.query, a.value, a.proj] + ([a.cross_key, a.cross_query, a.cross_value] if cross else [])
+                    if hasattr(a, "cross_key") != cross or not all(isinstance(l, nn.Linear) and l.in_features == C and l.out_features == C and l.bias is not None for l in lins):
+                        return False
+                    if any(getattr(ln, "bias", None) is not None or tuple(ln.weight.shape) != (C,) for ln in (b.ln1, b.ln2)):
+                        return False
+                    if not (isinstance(b.mlp[0], nn.Linear) and isinstance(b.mlp[1], nn.GELU) and getattr(b.mlp[1], "approximate", "none") == "none" and isinstance(b.mlp[2], nn.Linear)):
+                        return False
+                    if (b.mlp[0].in_features, b.mlp[0].out_features, b.mlp[2].in_features, b.mlp[2].out_features) != (C, 4 * C, 4 * C, C):
+                        return False
+                    if a.mask.dim() != 4 or a.mask.shape[-1] != a.mask.shape[-2] or a.mask.shape[-1] < max(1 + int(net.obs_seq_len), Ta):
+                        return False
+                    heads.add(int(a.n_head))
+            return len(heads) == 1 and C % heads.pop() == 0
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet
+    def _state(self, n):
+        """counter / chunk / window / last_bad for n lanes; a new size starts with every lane due on an empty window."""
+        if self.counter is None or self.counter.shape[0] != n:
+            dev = self.device
+            self.counter = torch.full((n,), self.Ta, dtype=torch.int32, device=dev)
+            self.chunk = torch.zeros(n, self.Ta, self.A, dtype=torch.float32, device=dev)
+            self.last_bad = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.hist = _History(n, self.S, self.obs_dim, dev)
+
+    def reset(self):
+        """DiffusionAgent.reset for every lane: empty windows, the next call computes a chunk everywhere."""
+        if self.counter is not None:
+            self.counter.fill_(self.Ta)
+            self.hist.reset()
+
+    def begin_episodes(self, mask):
+        """Lanes that start a new trajectory: window length 0, due at their next step (in place on the device, also under a captured graph)."""
+        self._state(int(mask.shape[0]))
+        m = mask.to(device=self.device, dtype=torch.bool).reshape(-1)
+        self.counter.masked_fill_(m, self.Ta)
+        self.hist.reset_(m)
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+        self._state(int(count))
+
+    def fork(self):
+        """A clone for another sub-batch: denoiser, scaler and schedule shared; per-lane state, step word and packed buffers its own."""
+        import copy
+        c = copy.copy(self)
+        c._t = self._t.clone()
+        c._packed = PackedWeights()
+        if self.counter is not None:
+            c.counter, c.chunk, c.last_bad = self.counter.clone(), self.chunk.clone(), self.last_bad.clone()
+            c.hist = _History(self.counter.shape[0], self.S, self.obs_dim, self.device)
+            c.hist.buf.copy_(self.hist.buf); c.hist.len.copy_(self.hist.len)
+            c.hist.lockstep = self.hist.lockstep
+        c.last_chunk = c.last_noise = None
+        return c
+
+    def captured(self):
+        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: scaling, the window shift, one kernel, the add on the step word)."""
+        return CapturedPolicy(self)
+
+    def load_reference_state_dict(self, sd):
+        """``Diffusion.state_dict()`` of the reference: the denoiser sits under ``model.`` (a bare DiffusionEncDec state dict is taken as it is); masks are ignored."""
+        if any(k.startswith("model.") for k in sd):
+            sd = {k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")}
+        own = self.model.state_dict()
+        self.model.load_state_dict({k: torch.as_tensor(sd[k]).to(own[k].dtype) for k in own})
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+
+    def use_ema(self, shadow_params):
+        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order, which is the reference's."""
+        with torch.no_grad():
+            for p, s in zip(self.model.parameters(), shadow_params):
+                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
+
+    # ---- packed tables
+    def _pack_params(self):
+        return list(self.model.parameters())
+
+    def _pack(self):
+        return pack_ddpm_act_weights(self.model, self.T)
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        self._packed.invalidate()
+
+    def ensure_packed(self):
+        if next(self.model.parameters()).is_cuda and self._kernel_shape():
+            self._packed.ensure(self._pack_params(), self._pack)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Warm-up and capture consume neither a step, a window entry nor a chunk position: step word, counters, chunks, window, lengths and last_bad are put back."""
+        self._state(int(obs.shape[0]))
+        return (self._t.clone(), self.counter.clone(), self.chunk.clone(), self.hist.buf.clone(), self.hist.len.clone(), self.last_bad.clone()), self.hist.lockstep
+
+    def capture_restore(self, snap):
+        tensors, lock = snap
+        for dst, src in zip((self._t, self.counter, self.chunk, self.hist.buf, self.hist.len, self.last_bad), tensors):
+            dst.copy_(src)
+        self.hist.lockstep = lock
+
+    # ---- the step
+    def _kernel_shape(self) -> bool:
+        m = self.model
+        return (m.embed_dim == 64 and m.n_heads == 4 and 1 <= m.state_dim <= 32 and 1 <= m.action_dim <= 8 and 1 <= self.S <= 5 and m.obs_seq_len <= 5 and 1 <= self.Ta <= 4
+                and 1 <= len(m.encoder.blocks) <= 4 and 1 <= len(m.decoder.blocks) <= 8 and 1 <= self.T <= 255 and m.linear_output)
+
+    def fused_ok(self, s) -> bool:
+        w = self.model.tok_emb.weight
+        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and os.environ.get("D3IL_POLICY_DDPM_ACT_FUSED", "1") == "1"
+
+    def _noise(self, n, dev, need_host: bool):
+        """The normals [n, T + 1, Ta, A] (index = chain index) as the torch path takes them / as the kernel is handed them: the given bank, or (``need_host``) the
+        host form of the kernel's draw (index 0, which is never drawn, is zero)."""
+        if self.noise_in is not None:
+            return torch.as_tensor(self.noise_in(n), dtype=torch.float32).to(dev).reshape(n, self.T + 1, self.Ta, self.A).contiguous()
+        if not need_host:
+            return None
+        import numpy as np
+        t = int(self._t.item()) & 0xFFFFFFFF
+        z = np.zeros((n, self.T + 1, self.Ta, self.A))
+        for k in range(1, self.T + 1):
+            z[:, k] = ddpm_act_normals(self.seed, self.env_offset, n, t, k, self.Ta, self.A)
+        return torch.as_tensor(z, dtype=torch.float32).to(dev)
+
+    def _sched_for(self, dt, dev):
+        if dt == torch.float32:
+            return self._sched.to(dev)
+        return ddpm_schedule(cosine_beta_schedule(self.T).to(device=dev, dtype=dt))["sched"]
+
+    def _chain_torch(self, st, noise, x=None, k_start=None, k_stop=0):
+        """A new chunk for every row of one window length: ``st`` [m, L, obs] (scaled), ``noise`` [m, T + 1, Ta, A]; in the dtype of ``st`` and the parameters (f32
+        in the policy; the tests run it in f64 too), in the reference's order of operations.  ``x`` / ``k_start`` / ``k_stop``: only chain steps k_start .. k_stop
+        from the given iterate.  Returns (chunk [m, Ta, A] clamped and inverse-scaled, NaN for marked rows; marked [m] bool; the last iterate before the final clamp)."""
+        dt, dev = st.dtype, st.device
+        c = lambda v: v.to(device=dev, dtype=dt)
+        m, sched, lo, hi = self.model, self._sched_for(dt, dev), c(self.lo), c(self.hi)
+        noise = c(noise)
+        if x is None:
+            x, k_start = noise[:, self.T], self.T - 1
+        else:
+            x = c(x)
+        bad = ~torch.isfinite(st).reshape(st.shape[0], -1).all(dim=1) | ~torch.isfinite(x).reshape(st.shape[0], -1).all(dim=1)
+        for i in range(k_start, k_stop - 1, -1):
+            eps = m(x, torch.full((st.shape[0],), i, dtype=torch.long, device=dev), st)
+            s = sched[i]
+            x0 = torch.minimum(torch.maximum(s[0] * x - s[1] * eps, lo), hi)
+            mean = s[2] * x0 + s[3] * x
+            x = mean if i == 0 else mean + s[4] * noise[:, i]
+            bad |= ~torch.isfinite(eps).reshape(st.shape[0], -1).all(dim=1) | ~torch.isfinite(x).reshape(st.shape[0], -1).all(dim=1)
+        y = torch.minimum(torch.maximum(x, lo), hi) * c(self.out_scale) + c(self.out_shift)
+        return torch.where(bad.reshape(-1, 1, 1), torch.full_like(y, float("nan")), y), bad, x
+
+    def _step_torch(self, win, ln):
+        if win.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DDPMACTPolicy: the torch path decides on the host which lanes are due, groups them by window length and draws its Philox numbers there; "
+                               "it cannot be captured - the kernel can")
+        n, dev = win.shape[0], win.device
+        due = (self.counter >= self.Ta) | (self.counter < 0)
+        self.last_bad.zero_()
+        if self.record:
+            self.last_noise = torch.zeros(n, self.T + 1, self.Ta, self.A, dtype=torch.float32, device=dev)
+        if bool(due.any()):
+            noise = self._noise(n, dev, True)
+            for L in torch.unique(ln[due]).tolist():
+                rows = torch.nonzero(due & (ln == L)).reshape(-1)
+                Lc = min(max(int(L), 1), self.S)
+                y, bad, _ = self._chain_torch(win[rows, :Lc], noise[rows])
+                self.chunk[rows] = y
+                self.last_bad[rows] = bad.to(torch.int32)
+            if self.record:
+                drawn = noise.clone()
+                drawn[:, 0] = 0
+                self.last_noise.copy_(torch.where(due.reshape(-1, 1, 1, 1), drawn, self.last_noise))
+            self.counter.masked_fill_(due, 0)
+        y = self.chunk[torch.arange(n, device=dev), self.counter.long()]
+        self.counter.add_(1)
+        return y
+
+    def _step_kernel(self, win, ln):
+        from . import capi
+        n, dev, m = win.shape[0], win.device, self.model
+        w = self._packed.current(self._pack_params(), self._pack)
+        z = self._noise(n, dev, False)
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        noise_out = torch.zeros(n, self.T + 1, self.Ta, self.A, dtype=torch.float32, device=dev) if self.record else None
+        ptr = lambda v: None if v is None else v.data_ptr()
+        assert win.is_contiguous() and ln.is_contiguous() and ln.dtype == torch.int64 and self._t.device == dev and self.counter.device == dev
+        capi.check(capi.load().d3il_ddpm_act_chunk_f32(win.data_ptr(), ln.data_ptr(), w["w_in"].data_ptr(), w["tab"].data_ptr(), w["enc_w"].data_ptr(), w["enc_v"].data_ptr(),
+                                                       w["dec_w"].data_ptr(), w["dec_v"].data_ptr(), w["head_w"].data_ptr(), self.lo.data_ptr(), self.hi.data_ptr(),
+                                                       self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed, self.env_offset, self._t.data_ptr(), ptr(z), None,
+                                                       self.counter.data_ptr(), self.chunk.data_ptr(), y.data_ptr(), self.last_bad.data_ptr(), None, ptr(noise_out), n,
+                                                       self.obs_dim, self.A, self.S, self.Ta, m.embed_dim, m.n_heads, len(m.encoder.blocks), len(m.decoder.blocks), self.T, 1, -1, 0,
+                                                       torch.cuda.current_stream(dev).cuda_stream))
+        if self.record:
+            self.last_noise = noise_out
+        return y
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "DDPMACTPolicy: observation width %d, the state tokens take %d" % (s.shape[-1], self.obs_dim)
+        self._state(s.shape[0])
+        self.hist.append_(s)
+        win, ln = self.hist.padded()
+        if self.fused_ok(s):
+            y = self._step_kernel(win.contiguous(), ln.contiguous())
+        else:
+            if s.is_cuda and os.environ.get("D3IL_POLICY_DDPM_ACT_FUSED", "1") == "1" and not getattr(self, "_warned", False):
+                import warnings
+                self._warned = True      # (once per policy; forks copy the flag)
+                warnings.warn("DDPMACTPolicy: this network (width %d, %d heads, window %d, chunk %d, linear head %s) is not one the chain kernel is built for; every call "
+                              "runs the torch path with a device synchronisation per call and no graph capture"
+                              % (self.model.embed_dim, self.model.n_heads, self.S, self.Ta, self.model.linear_output))
+            y = self._step_torch(win, ln)
+        if self.record:
+            self.last_chunk = self.chunk.clone()
+        self._t.add_(1)
+        return y
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, obs_seq_len: int = 5, action_seq_len: int = 4, n_timesteps: int = 16, enc_layers: int = 2,
+               dec_layers: int = 4, embed_dim: int = 64, n_heads: int = 4, window_size: int = 8, action_scale: float = 0.002, bound: float = 1.5, policy_seed: int = 0,
+               linear_output: bool = True, **kw):
+        """A policy of the reference's shape (configs/agents/ddpm_encdec_agent.yaml: 2 encoder and 4 decoder layers, width 64, 4 heads, obs_seq_len 5, chunks of 4, 16
+        timesteps, masks of window_size + 1) with the fixed trained-like weights of ``ddpm_act_synthetic_state`` (there are no checkpoints offline), unit
+        observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
+        net = EncDecDenoiser(obs_dim, action_dim, embed_dim, n_heads, enc_layers, dec_layers, obs_seq_len, action_seq_len, max(window_size + 1, 1 + obs_seq_len, action_seq_len),
+                             linear_output=linear_output)
+        net.load_state_dict({k: torch.as_tensor(v) for k, v in ddpm_act_synthetic_state({k: v.shape for k, v in net.state_dict().items()}, seed).items()})
+        for p in net.parameters():
+            p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        return cls(net.to(device), sc, n_timesteps, seed=policy_seed, **kw)

@@ -277,6 +277,32 @@ int d3il_act_chunk_f32(const float* state, const float* w_in, const float* tab, 
                        const float* head_w, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset,
                        const uint32_t* t_device, const float* latent_in, int32_t* counter, float* chunk, float* actions, float* latent_out, long n_env, int obs_dim, int A,
                        int T, int width, int n_head, int latent, int n_enc, int n_dec, void* stream);
+/* One step of the batched DDPM-ACT policy (policies.DDPMACTPolicy; ddpm_encdec_agent.py:222-257 around diffusion_policy.py:117-217 and diffusion_models.py:844-905,
+ * no goals) in one launch, f32 throughout.  Persistent per-environment state on the device: counter i32 [n_env] and chunk [n_env][action_seq_len][A] (already clamped
+ * and inverse-scaled).  An environment with counter == action_seq_len (or outside 0 .. action_seq_len) is due and runs the whole reverse chain on its window
+ * (window [n_env][obs_seq_len][obs_dim], scaled, left-aligned, oldest first; len i64 [n_env] valid rows, 1 .. obs_seq_len): x = normals of chain index T =
+ * n_timesteps; for i = T - 1 .. 0: encoder on [temb[i], (W_tok s + b_tok) + pos[0 .. L-1]] (causal; LayerNorm with weight only, eps 1e-5; exact GELU), decoder on the
+ * action tokens (W_act x_t + b_act) + pos[L - 1 + t] (causal self-attention plus unmasked cross-attention over the 1 + L encoder rows in front of one projection),
+ * eps = head; x0 = clamp(sched[i][0] x - sched[i][1] eps, lo, hi), x = sched[i][2] x0 + sched[i][3] x + sched[i][4] normals_i (i = 0: nothing drawn or added); then
+ * chunk[n][t][a] = clamp(x, lo_a, hi_a) scale_a + shift_a and counter = 0.  Every environment then emits actions[n] = chunk[n][counter] and stores counter + 1.  A
+ * workgroup (16 environments) without a due environment runs no network; an environment's result never depends on which of its neighbours are due or on their
+ * window lengths.  Random numbers: Philox4x32-10, key = seed, counter = (env_offset + n, *t_device, 0x44410000 | k << 8 | t << 1 | q), k the chain index, t the action
+ * token, component 4 q + m, normals as d3il_ddpm_gpt_step_f32.  w_in, tab, enc_w, enc_v, dec_w, dec_v, head_w: policies.pack_ddpm_act_weights (fragment order as
+ * d3il_act_chunk_f32; w_in = tok_emb (32 columns) | action_emb (16 columns); layer arrays as d3il_act_chunk_f32; tab = pos [8][64] | encoder ln | decoder ln |
+ * tok_emb bias | action_emb bias | head bias [16] | temb [T][64] | sched [T][5]); lo / hi (scaled space) / scale / shift [A]; t_device: DEVICE u32, read only.
+ * Optional (NULL): noise_in [n_env][T + 1][action_seq_len][A] replaces the draws (index = chain index); x_in [n_env][action_seq_len][A] replaces the first
+ * iterate; k_start < 0 runs the whole chain, otherwise only chain steps k_start .. k_stop (0 <= k_stop <= k_start + 1 <= T; k_stop = k_start + 1: no step, the
+ * first iterate goes to the final clamp) - test hooks; x_out [n_env][action_seq_len][A] the iterate after the last step run (before the final clamp), noise_out
+ * (layout of noise_in) what was drawn - both written for due environments only; bad i32 [n_env] (may be NULL): 1 for a due
+ * environment with a NaN / Inf in a valid window row, a head output or an iterate - it gets NaN in its whole chunk and in the emitted action -, 0 for every other
+ * one.  No other environment changes; padding rows and the window of an environment that is not due are not read.  Built for width 64, 4 heads, obs_dim 1 .. 32,
+ * 1 <= A <= 8, obs_seq_len 1 .. 5, action_seq_len 1 .. 4, 1 .. 4 encoder and 1 .. 8 decoder layers, 1 .. 255 timesteps, linear_head = 1: D3IL_EUNSUPPORTED
+ * otherwise, answered before any launch.  Packed arrays 16-byte aligned. */
+int d3il_ddpm_act_chunk_f32(const float* window, const int64_t* len, const float* w_in, const float* tab, const float* enc_w, const float* enc_v, const float* dec_w,
+                            const float* dec_v, const float* head_w, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed,
+                            uint64_t env_offset, const uint32_t* t_device, const float* noise_in, const float* x_in, int32_t* counter, float* chunk, float* actions,
+                            int32_t* bad, float* x_out, float* noise_out, long n_env, int obs_dim, int A, int obs_seq_len, int action_seq_len, int width, int n_head,
+                            int n_enc, int n_dec, int n_timesteps, int linear_head, int k_start, int k_stop, void* stream);
 /* The whole inference of the batched conditional-VAE policy (policies.CVAEPolicy; cvae_agent.py:155-170 around cvae.py:55-62) in one launch, f32 throughout: per
  * environment z = clamp(z_in[n] or `latent` Box-Muller normals, -0.5, 0.5) (the reference clamps its prior sample: 61.7 % of the components sit on a bound), the
  * decoder (ResidualMLPNetwork, Mish) on the row [state | z], actions[n][a] = clamp(out_a, lo_a, hi_a) scale_a + shift_a (product and sum in f64, rounded once).
