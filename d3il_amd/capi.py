@@ -142,6 +142,12 @@ def has_group_options() -> bool:
     return hasattr(load(), "d3il_group_set_option")
 
 
+def is_unknown_group_option(err: Exception) -> bool:
+    """The error d3il_group_set_option gives for an option the loaded library does not have (the parent build loaded through D3IL_LIB_PATH knows
+    "quiet_streams" but not "dispatch_sets"): the caller keeps the path it had."""
+    return isinstance(err, D3ilError) and "d3il_group_set_option: unknown option" in str(err)
+
+
 def check(rc: int):
     if rc != 0:
         raise D3ilError("libd3il_rollout error %d: %s" % (rc, load().d3il_last_error().decode()))

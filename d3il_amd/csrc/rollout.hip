@@ -1114,24 +1114,33 @@ struct d3il_handle_s {
   // link-near guard of the generic engine (link_guard.h, d3il_set_link_guard): lg.n = 0 = off
   d3il_model_blob model;   // the blob the handle was made from (the body tree places the guard's capsules)
   LinkGuardConsts lg; LinkGuardConsts* d_lg; int64_t* lg_flagged;   // lg_flagged: caller-owned device counter, may be null
-  // step group (d3il_group_create): the group of this handle and its deferred d3il_random_rollout_step call of the current round
-  struct d3il_group_s* group; bool grp_pending; uint64_t grp_seed, grp_off; uint32_t grp_t; double* grp_actions; int64_t* grp_counts; hipStream_t grp_stream;
+  // step group (d3il_group_create): the group of this handle, its dispatch set there, and its deferred d3il_random_rollout_step call of the current round
+  struct d3il_group_s* group; int grp_set; bool grp_pending; uint64_t grp_seed, grp_off; uint32_t grp_t; double* grp_actions; int64_t* grp_counts; hipStream_t grp_stream;
   hipEvent_t ring_alt0[128], ring_alt1[128];      // ring slot of a merged launch: the group's shared event pair (null: the handle's own pair)
 };
-// A step group: Avoiding handles of one device whose d3il_random_rollout_step calls of one step go out as ONE dispatch.  The round's key
-// (t, n_substeps, max_steps, timing) is that of its first pending member.
-struct d3il_group_s {
-  int device, count; d3il_handle_s* m[AVOID_GROUP_MAX];
-  int n_pending; bool busy;      // busy: a flush or a merged launch is running (the library calls it makes must not flush again)
+// A step group: Avoiding handles of one device whose d3il_random_rollout_step calls of one step go out as ONE dispatch - or, with the
+// group option "dispatch_sets" = K, as K dispatches: the members, in group order, form K contiguous runs (d3il_dispatch_set), and every
+// set launches on its own when all ITS members are pending, on the stream of its first live member.  A set owns what a launch needs: the round's key
+// (t, n_substeps, max_steps, timing: that of its first pending member), the pending count, the device table, the ordering events, the timing ring, the
+// armed flag.  K = 1: one set with every member, the group of section 31.
+struct d3il_dispatch_set {
+  int count; d3il_handle_s* m[AVOID_GROUP_MAX];      // the live members of the set, in group order; m[0] leads (its stream takes the dispatch)
+  int n_pending;
   uint32_t t; int n_substeps, max_steps; bool timing;
   AvoidGroupTable* d_table; AvoidGroupTable table_host; bool table_valid;
   hipEvent_t ev_join[AVOID_GROUP_MAX], ev_done; bool ev_made;
   hipEvent_t ring0[128], ring1[128]; bool ring_created; long ring_head;      // the shared event pairs of the timed merged launches
   // option "quiet_streams" (DESIGN section 32): the pre-launch joins of the other members' streams are queued only in an ARMED round - the first one, and
-  // the first after anything but a merged round happened to the group (group_arm).  Off: every round joins.  Host counters: merged rounds, and those that joined
-  bool quiet, armed; int64_t n_merged, n_joined;
+  // the first after anything but a merged round happened to the group (group_arm).  Off: every round joins.
+  bool armed;
 };
-static inline void group_arm(d3il_group_s* g) { g->armed = true; }
+struct d3il_group_s {
+  int device, count; d3il_handle_s* m[AVOID_GROUP_MAX];
+  int n_sets; d3il_dispatch_set set[AVOID_GROUP_MAX];      // sets beyond n_sets keep the events and the table they once made until the group is destroyed
+  int n_pending; bool busy;      // n_pending: over all sets.  busy: a flush or a merged launch is running (the library calls it makes must not flush again)
+  bool quiet; int64_t n_merged, n_joined;      // host counters: merged dispatches (one per set and step), and those that joined
+};
+static inline void group_arm(d3il_group_s* g) { for (int k = 0; k < AVOID_GROUP_MAX; k++) g->set[k].armed = true; }
 // Creation flags of the library's own events: the ordering events of a step group (ev_join, ev_done) and the timing rings, the
 // group's and every handle's.  hipEventDisableSystemFence: the record carries no system-scope cache writeback and invalidation (measured: about 1.4 us less per
 // record on the launch queue, tools/probe/event_hops.hip).  Nothing reads results through these events: the host sees device memory only behind a stream or
@@ -2238,7 +2247,10 @@ static int rollout_step_single(d3il_handle h, uint64_t seed, uint64_t env_offset
 // the other although each fills a sixteenth of the chip.  A group sends the launches of one step as ONE dispatch on the first member's stream: a call on a
 // member only marks it pending, the call that completes the round launches.  Stream order is kept for the caller: the first member's stream waits for
 // an event on every other member's stream before the launch, and every other member's stream waits for the launch afterwards.  Group option "quiet_streams"
-// (DESIGN section 32): the caller queues nothing on those streams between rounds, and only an ARMED round waits before its launch.
+// (DESIGN section 32): the caller queues nothing on those streams between rounds, and only an ARMED round waits before its launch.  Group option
+// "dispatch_sets" (DESIGN section 34): K contiguous runs of members launch on their own, each as described here with "the set" for "the group"; a dispatch
+// lasts as long as its slowest workgroup, and a set pays for the slow workgroups of its own members only.  Ending a round stays on the side of joining: a
+// flush ends the pending rounds of ALL sets and arms all of them.
 static int group_flush(d3il_group_s* g) {
   if (g->busy) return D3IL_OK;
   group_arm(g);      // the members launch on their own streams now: the next merged round has to come behind them
@@ -2250,11 +2262,14 @@ static int group_flush(d3il_group_s* g) {
     h->grp_pending = false; g->n_pending--;
     if (!rc) rc = rollout_step_single(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, h->grp_counts, (void*)h->grp_stream);      // (after a failure the others are only un-marked)
   }
+  for (int k = 0; k < g->n_sets; k++) g->set[k].n_pending = 0;
   g->n_pending = 0; g->busy = false;
   return rc;
 }
-static int group_launch_locked(d3il_group_s* g) {
-  HIPCHK(hipSetDevice(g->device));
+// The merged dispatch of ONE dispatch set (with "dispatch_sets" 1: of the group).  Everything it records, waits for, reads and writes belongs to the set `g`
+// and its members: nothing is queued on a stream of another set, so the sets of a group run independently of each other.
+static int group_launch_locked(d3il_group_s* grp, d3il_dispatch_set* g) {
+  HIPCHK(hipSetDevice(grp->device));
   if (!g->ev_made) {
     for (int i = 0; i < AVOID_GROUP_MAX; i++) HIPCHK(hipEventCreateWithFlags(&g->ev_join[i], EV_ORDER_FLAGS));
     HIPCHK(hipEventCreateWithFlags(&g->ev_done, EV_ORDER_FLAGS));
@@ -2285,7 +2300,7 @@ static int group_launch_locked(d3il_group_s* g) {
   }
   // the join: s0 comes behind everything queued on the other members' streams.  A continuing round of a quiet group queues none: the other streams hold
   // only their waits for the earlier rounds, and the dispatch follows the previous one on its own queue
-  const bool join = !g->quiet || g->armed;
+  const bool join = !grp->quiet || g->armed;
   if (join) for (int i = 1; i < g->count; i++) {
     if (g->m[i]->grp_stream == s0) continue;
     HIPCHK(hipEventRecord(g->ev_join[i], g->m[i]->grp_stream));
@@ -2327,16 +2342,22 @@ static int group_launch_locked(d3il_group_s* g) {
   } else HIPCHK(hipEventRecord(done_ev, s0));
   for (int i = 1; i < g->count; i++) if (g->m[i]->grp_stream != s0) HIPCHK(hipStreamWaitEvent(g->m[i]->grp_stream, done_ev, 0));
   for (int i = 0; i < g->count; i++) { d3il_handle_s* h = g->m[i]; fused_step_end(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, (void*)h->grp_stream); }
-  g->n_merged++; g->n_joined += join ? 1 : 0;
-  g->armed = false;      // the next round continues this one, unless something else happens to the group first
+  grp->n_merged++; grp->n_joined += join ? 1 : 0;
+  g->armed = false;      // the set's next round continues this one, unless something else happens to the group first
   return D3IL_OK;
 }
-static int group_launch(d3il_group_s* g) {
+static int group_launch(d3il_group_s* g, d3il_dispatch_set* s) {
   g->busy = true;
-  const int rc = group_launch_locked(g);
-  if (rc) group_arm(g);      // a HIP failure: whatever the group does next starts from the joined form
-  for (int i = 0; i < g->count; i++) g->m[i]->grp_pending = false;
-  g->n_pending = 0; g->busy = false;
+  const int rc = group_launch_locked(g, s);
+  for (int i = 0; i < s->count; i++) s->m[i]->grp_pending = false;
+  g->n_pending -= s->n_pending; s->n_pending = 0;
+  if (rc) {      // a HIP failure: the pending rounds of the other sets are abandoned with this one, and whatever the group does next starts from the joined form
+    group_arm(g);
+    for (int i = 0; i < g->count; i++) g->m[i]->grp_pending = false;
+    for (int k = 0; k < g->n_sets; k++) g->set[k].n_pending = 0;
+    g->n_pending = 0;
+  }
+  g->busy = false;
   return rc;
 }
 // the call of a member: *handled = 1 when it was deferred or launched with its round, 0 when the caller runs it through the single path (the round, if any, has been flushed)
@@ -2350,14 +2371,16 @@ static int group_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset,
     group_arm(g);
     return g->n_pending ? group_flush(g) : D3IL_OK;
   }
-  if (g->n_pending && (h->grp_pending || g->t != t || g->n_substeps != h->hc.n_substeps || g->max_steps != h->hc.max_steps || g->timing != h->timing)) {
-    if (int rc = group_flush(g)) return rc;      // a second call of a member, or a call that does not fit the round: nothing is merged
+  // the round is that of the member's dispatch set: the sets of a group may be steps apart, so the key is compared inside the set only
+  d3il_dispatch_set* s = &g->set[h->grp_set];
+  if (s->n_pending && (h->grp_pending || s->t != t || s->n_substeps != h->hc.n_substeps || s->max_steps != h->hc.max_steps || s->timing != h->timing)) {
+    if (int rc = group_flush(g)) return rc;      // a second call of a member, or a call that does not fit the round: nothing is merged (the pending rounds of ALL sets end)
   }
-  if (!g->n_pending) { g->t = t; g->n_substeps = h->hc.n_substeps; g->max_steps = h->hc.max_steps; g->timing = h->timing; }
+  if (!s->n_pending) { s->t = t; s->n_substeps = h->hc.n_substeps; s->max_steps = h->hc.max_steps; s->timing = h->timing; }
   h->grp_pending = true; h->grp_seed = seed; h->grp_off = env_offset; h->grp_t = t; h->grp_actions = actions; h->grp_counts = episode_counts_device; h->grp_stream = (hipStream_t)stream;
-  g->n_pending++;
+  s->n_pending++; g->n_pending++;
   *handled = 1;
-  return g->n_pending == g->count ? group_launch(g) : D3IL_OK;
+  return s->n_pending == s->count ? group_launch(g, s) : D3IL_OK;
 }
 int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream) {
   if (h && h->group) {
@@ -2368,20 +2391,47 @@ int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, 
   return rollout_step_single(h, seed, env_offset, t, actions, episode_counts_device, stream);
 }
 static void timing_drain_all(d3il_handle_s* h) { while (h->ring_drained < h->ring_head) { if (timing_drain_one(h)) { h->ring_drained = h->ring_head; break; } } }
-// the member leaves its group: the round ends, the durations it still has to read from the group's shared event pairs are read now
+// nothing of the handle may name an event of its dispatch set any more (d3il_group_destroy destroys them; a set that lives on records them again, and after
+// the handle has left it, or moved to another set, no longer waits for the handle to read them first): the ring is drained, and a last timed launch that was
+// a merged one is no longer there for d3il_last_step_ms - its duration is in d3il_timing_stats
+static void group_forget_events(d3il_handle_s* h) {
+  timing_drain_all(h);
+  if (h->ring_head > 0 && h->ring_alt0[(h->ring_head - 1) % 128]) { h->ev_valid = false; h->ev0 = h->ev1 = nullptr; }
+  for (int i = 0; i < 128; i++) h->ring_alt0[i] = h->ring_alt1[i] = nullptr;
+}
+// the member leaves its group: the round ends, the durations it still has to read from its set's shared event pairs are read now
 static void group_leave(d3il_handle_s* h) {
   d3il_group_s* g = h->group;
   if (!g) return;
   (void)group_flush(g);
   group_arm(g);      // (also when a flush is running: the table and the first stream may change)
-  timing_drain_all(h);
-  // nothing of the handle may name an event of the group any more (d3il_group_destroy destroys them, a group that lives on records them again): the ring
-  // is drained, and a last timed launch that was a merged one is no longer there for d3il_last_step_ms - its duration is in d3il_timing_stats
-  if (h->ring_head > 0 && h->ring_alt0[(h->ring_head - 1) % 128]) { h->ev_valid = false; h->ev0 = h->ev1 = nullptr; }
-  for (int i = 0; i < 128; i++) h->ring_alt0[i] = h->ring_alt1[i] = nullptr;
+  group_forget_events(h);
+  // the member's set shrinks (its next live member leads it; an empty set is never pending and never launches), the other sets stay as they are
+  d3il_dispatch_set* s = &g->set[h->grp_set];
+  if (h->grp_pending) { s->n_pending--; g->n_pending--; }      // (only when a flush is running)
   int k = 0;
+  for (int i = 0; i < s->count; i++) if (s->m[i] != h) s->m[k++] = s->m[i];
+  s->count = k;
+  k = 0;
   for (int i = 0; i < g->count; i++) if (g->m[i] != h) g->m[k++] = g->m[i];
   g->count = k; h->group = nullptr; h->grp_pending = false;
+}
+// "dispatch_sets": the live members, in group order, as k contiguous runs of as equal a size as possible (the first count % k runs hold one more).
+// Called with nothing pending.  A member that moves to another set must not name the events of the old one (see group_forget_events).
+static void group_partition(d3il_group_s* g, int k) {
+  const int base = g->count / k, extra = g->count % k;
+  g->n_sets = k;
+  int i = 0;
+  for (int j = 0; j < AVOID_GROUP_MAX; j++) {
+    d3il_dispatch_set* s = &g->set[j];
+    s->count = j < k ? base + (j < extra ? 1 : 0) : 0;
+    s->n_pending = 0;
+    for (int q = 0; q < s->count; q++, i++) {
+      d3il_handle_s* h = g->m[i];
+      if (h->grp_set != j) group_forget_events(h);
+      s->m[q] = h; h->grp_set = j;
+    }
+  }
 }
 int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out) {
   if (!handles || !out) return fail(D3IL_EINVAL, "d3il_group_create: null argument");
@@ -2400,8 +2450,9 @@ int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out) {
   if (hipFuncSetAttribute((const void*)k_avoiding_step_split<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AVOID_LDS_SERVE) != hipSuccess) (void)hipGetLastError();
   d3il_group_s* g = new d3il_group_s();
   g->device = handles[0]->device; g->count = count;
-  g->armed = true;      // the first merged round comes behind the members' single launches
-  for (int i = 0; i < count; i++) { g->m[i] = handles[i]; handles[i]->group = g; handles[i]->grp_pending = false; }
+  group_arm(g);      // the first merged round comes behind the members' single launches
+  for (int i = 0; i < count; i++) { g->m[i] = handles[i]; handles[i]->group = g; handles[i]->grp_set = 0; handles[i]->grp_pending = false; }
+  group_partition(g, 1);
   *out = g;
   return D3IL_OK;
 }
@@ -2419,6 +2470,14 @@ int d3il_group_set_option(d3il_group g, const char* name, int value) {
     g->quiet = value != 0;
     return D3IL_OK;
   }
+  if (std::strcmp(name, "dispatch_sets") == 0) {
+    if (value < 1 || value > g->count) return fail(D3IL_EINVAL, "dispatch_sets must be 1 .. the number of members");
+    group_arm(g);
+    if (g->n_pending) { if (int rc = group_flush(g)) return rc; }      // rounds that have begun end through the single path
+    (void)hipSetDevice(g->device);
+    group_partition(g, value);
+    return D3IL_OK;
+  }
   return fail(D3IL_EINVAL, std::string("d3il_group_set_option: unknown option ") + name);
 }
 int d3il_group_stats(d3il_group g, int64_t* merged_rounds, int64_t* joined_rounds) {
@@ -2432,8 +2491,11 @@ int d3il_group_destroy(d3il_group g) {
   const int rc = group_flush(g);
   while (g->count > 0) group_leave(g->m[g->count - 1]);
   (void)hipDeviceSynchronize();      // the last merged launch reads the table
-  if (g->ev_made) { for (int i = 0; i < AVOID_GROUP_MAX; i++) (void)hipEventDestroy(g->ev_join[i]); (void)hipEventDestroy(g->ev_done); (void)hipFree(g->d_table); }
-  if (g->ring_created) for (int i = 0; i < 128; i++) { (void)hipEventDestroy(g->ring0[i]); (void)hipEventDestroy(g->ring1[i]); }
+  for (int k = 0; k < AVOID_GROUP_MAX; k++) {
+    d3il_dispatch_set* s = &g->set[k];
+    if (s->ev_made) { for (int i = 0; i < AVOID_GROUP_MAX; i++) (void)hipEventDestroy(s->ev_join[i]); (void)hipEventDestroy(s->ev_done); (void)hipFree(s->d_table); }
+    if (s->ring_created) for (int i = 0; i < 128; i++) { (void)hipEventDestroy(s->ring0[i]); (void)hipEventDestroy(s->ring1[i]); }
+  }
   delete g;
   return rc;
 }

@@ -41,11 +41,17 @@ class StepGroup:
     The rounds of a running sequence then follow each other on the first member's stream without the join through the other streams.  ``flush()`` (and
     every other library call on a member) re-arms the join for the next merged round: call it before a round that has to see a write queued on another
     member's stream, and before queueing a read there that the NEXT round must not overtake.  Work queued on a member's stream after a round still sees
-    that round."""
+    that round.
+
+    ``set_option("dispatch_sets", k)`` (default 1) cuts the members, in the order given, into k contiguous runs of as equal a size as
+    possible.  Every set is a group of its own as far as launching goes: it launches when all ITS members have called, on its first member's stream, and
+    may run steps ahead of the other sets; ``stats()`` then counts one merged dispatch per set and step.  Everything that ends a round (``flush()``, another
+    library call on a member, a call that does not fit) ends the pending rounds of all sets.  ``try_option`` is ``set_option`` for a library that may be
+    older than the option: it returns False and changes nothing when the library does not know the name."""
 
     MAX_MEMBERS = 8
 
-    def __init__(self, envs, quiet_streams: bool = False):
+    def __init__(self, envs, quiet_streams: bool = False, dispatch_sets: int = 1):
         envs = list(envs)
         if not capi.has_step_group():
             raise capi.D3ilError("the loaded libd3il_rollout has no step group (d3il_group_create)")
@@ -56,11 +62,27 @@ class StepGroup:
         self.g = g
         if quiet_streams:
             self.set_option("quiet_streams", 1)
+        self.dispatch_sets = 1
+        if dispatch_sets != 1:
+            self.set_option("dispatch_sets", dispatch_sets)
 
     def set_option(self, name: str, value: int):
         if not capi.has_group_options():
             raise capi.D3ilError("the loaded libd3il_rollout has no group options (d3il_group_set_option)")
         capi.check(self.L.d3il_group_set_option(self.g, name.encode(), int(value)))
+        if name == "dispatch_sets":
+            self.dispatch_sets = int(value)
+
+    def try_option(self, name: str, value: int) -> bool:
+        if not capi.has_group_options():
+            return False
+        try:
+            self.set_option(name, value)
+        except capi.D3ilError as e:
+            if capi.is_unknown_group_option(e):
+                return False
+            raise
+        return True
 
     def stats(self):
         """(merged rounds, merged rounds that joined the other members' streams before the launch) since the group was created; host counters."""

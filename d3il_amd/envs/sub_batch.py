@@ -88,7 +88,9 @@ class SubBatchSet:
 
     THE RULE when the set has formed a step group (``self.group``; Avoiding with fewer hardware queues than streams): the group runs with the library's
     ``quiet_streams`` option, so between two ``random_rollout_step`` rounds the caller queues nothing on the sub-batch streams that reads or writes what the
-    step touches (the environments' buffers, ``actions``, episode counters, tally) - except on the first sub-batch's stream, or after ``join()``.
+    step touches (the environments' buffers, ``actions``, episode counters, tally) - except on the first stream of each set, or after ``join()``.
+    (A group of four or more sub-batches is cut into two dispatch sets, ``_step_group``: the first stream of a set is that of its first sub-batch, and it
+    stays ordered for what the sub-batches of ITS set touch - the other set launches elsewhere, possibly steps ahead or behind.)
     ``join()`` flushes the group, which re-arms the library's join of the streams: torch work queued on any sub-batch stream before ``join()`` is ordered
     before the next round, work queued after a round sees that round.  Library calls on an environment (reset, get_state, options, timing) re-arm by
     themselves.  Without a group every stream is ordered as usual.
@@ -125,7 +127,12 @@ class SubBatchSet:
         """Avoiding: with fewer hardware queues than the S streams and the null stream need, two sub-batches share a queue and their step launches run one after
         the other; the library then sends the ``random_rollout_step`` calls of one step as ONE dispatch (a step group).  With a queue per
         stream nothing is grouped.  ``D3IL_STEP_GROUP=0|1`` overrides the choice (A/B runs).  The group runs with ``quiet_streams`` (the
-        rule is in the class docstring) where the library has the option."""
+        rule is in the class docstring) where the library has the option.
+
+        A group of four or more members, an even count, is cut into TWO dispatch sets (option ``dispatch_sets``) when the process has at
+        least three hardware queues: the first half launches on the first sub-batch's stream, the second half on the stream of its own first sub-batch, and
+        neither waits for the other's slowest workgroup.  With two queues (one of them the null stream's) both leaders would share one, and the halves would
+        run one after the other.  ``D3IL_STEP_GROUP_SETS=1|2`` overrides the choice (A/B runs); a library without the option keeps one set."""
         envs = [b.env for b in self.batches]
         want = hw_queues < len(envs) + 1
         if os.environ.get("D3IL_STEP_GROUP") in ("0", "1"):
@@ -136,7 +143,13 @@ class SubBatchSet:
         from .. import capi
         if len(envs) > StepGroup.MAX_MEMBERS or not capi.has_step_group():      # (an older library loaded through D3IL_LIB_PATH: today's path)
             return None
-        return StepGroup(envs, quiet_streams=capi.has_group_options())
+        group = StepGroup(envs, quiet_streams=capi.has_group_options())
+        sets = 2 if len(envs) >= 4 and len(envs) % 2 == 0 and hw_queues >= 3 else 1
+        if os.environ.get("D3IL_STEP_GROUP_SETS") in ("1", "2"):
+            sets = int(os.environ["D3IL_STEP_GROUP_SETS"])
+        if sets != 1 and sets <= len(envs):
+            group.try_option("dispatch_sets", sets)      # (False: the library has no dispatch sets - one dispatch per step, as before)
+        return group
 
     def __len__(self):
         return len(self.batches)

@@ -448,7 +448,25 @@ int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, 
  * and a read queued there after round N is ordered behind round N but NOT before round N+1, which may overwrite what it reads.  In both cases call d3il_group_flush
  * after queueing that work and before the next round (the armed round joins what the streams hold when it launches), or use the first member's stream.
  * d3il_group_stats: merged rounds and merged rounds that joined, since the group was created; plain host counters (no flush, no device access).  With the
- * option off the two are equal. */
+ * option off the two are equal.
+ *
+ * Group option "dispatch_sets" (d3il_group_set_option; default 1 = everything above holds as written).  With K the members, in the order given
+ * to d3il_group_create, form K contiguous runs of as equal a member count as possible (the first count % K runs hold one more): DISPATCH SETS.  K below 1 or above
+ * the number of live members is D3IL_EINVAL; setting the option flushes and arms, like "quiet_streams", and a handle that moves to another set answers
+ * d3il_last_step_ms as one that left a group (above).  A set launches on its own: when all ITS members are pending, as one dispatch of the set's workgroups on
+ * the stream of its first live member (the set's LEADER), without waiting for the other sets.  Read everything above with "the set" for "the group" and "the
+ * leader" for "the first member": a round and its key (t, n_substeps, max_steps, timing) are those of one set, so set A may be several steps ahead of set B;
+ * the pre-launch joins, "quiet_streams" with its armed flag, and the post-launch waits concern the set's other members' streams only; the third wave runs while
+ * the set's workgroups stay within the sum of ITS members' "serve_wave_max_workgroups"; the timing pair is the set's, entered into its members' rings (the
+ * members of one set report the same durations, members of different sets their own).  Nothing is recorded on, or waited for by, a stream of another set in a
+ * running sequence.  No ordering between the sets is needed, because everything a step touches is per handle: the members' buffers, `actions`, the episode
+ * counters and the tally belong to one member, hence to one set.  A caller that shares one of them between members of different sets (one tally table, one
+ * counter) gets the atomic adds of both dispatches in either order - sums are the same - but must not read them before both sets have run the step it asks for.
+ * Under "quiet_streams" the stream that stays fully ordered for a member's buffers is its own set's leader's.
+ * Ending a round stays on the side of joining: whatever ends a round above (a call that is not eligible or does not fit ITS set's round, a second call of a
+ * pending member, any other library call on a member, d3il_group_flush, a member leaving, a HIP failure) ends the pending rounds of ALL sets and arms all of
+ * them.  A member that leaves shrinks its set (the next live member leads it); a set without a live member is skipped; a set of one member still launches the
+ * group form.  d3il_group_stats counts merged DISPATCHES, and those that joined: K per step when every set merges. */
 typedef struct d3il_group_s* d3il_group;
 int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out);
 int d3il_group_flush(d3il_group g);
