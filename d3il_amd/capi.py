@@ -49,7 +49,7 @@ HXG_CLIPPED, HXG_NONFINITE, HXG_LAUNCHES, HXG_N = 0, 1, 2, 4      # the counters
 EXPORTS = ["d3il_create", "d3il_destroy", "d3il_start", "d3il_reset", "d3il_step", "d3il_get_buffers", "d3il_get_state",
            "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
            "d3il_rccl_available", "d3il_comm_unique_id", "d3il_comm_init", "d3il_comm_count", "d3il_comm_destroy", "d3il_reduce_metrics", "d3il_set_timing",
-           "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_group_create", "d3il_group_flush", "d3il_group_destroy", "d3il_group_set_option", "d3il_group_stats", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_debug_build_flags", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
+           "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_group_create", "d3il_group_flush", "d3il_group_destroy", "d3il_group_set_option", "d3il_group_stats", "d3il_group_pipeline_stats", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_debug_build_flags", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
 
 
 class D3ilError(RuntimeError):
@@ -126,6 +126,8 @@ def load():
         if hasattr(L, "d3il_group_set_option"):      # (the parent build has the group without its options and counters: has_group_options())
             L.d3il_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
             L.d3il_group_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(L, "d3il_group_pipeline_stats"):      # (the parent build has no "pipeline_depth": has_group_pipeline())
+            L.d3il_group_pipeline_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if L.d3il_blob_sizeof() != C.sizeof(ModelBlob):
             raise D3ilError("model blob layout mismatch between include/d3il_model_blob.h and d3il_amd/model/blob.py")
         _LIB = L
@@ -140,6 +142,11 @@ def has_step_group() -> bool:
 def has_group_options() -> bool:
     """The loaded library has the group's options and counters (d3il_group_set_option "quiet_streams", d3il_group_stats)."""
     return hasattr(load(), "d3il_group_set_option")
+
+
+def has_group_pipeline() -> bool:
+    """The loaded library has the group option "pipeline_depth" and its counters (d3il_group_pipeline_stats)."""
+    return hasattr(load(), "d3il_group_pipeline_stats")
 
 
 def is_unknown_group_option(err: Exception) -> bool:

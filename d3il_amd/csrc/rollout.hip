@@ -247,22 +247,88 @@ struct AvoidGroupMember {
   int n, stride;
   unsigned first_wg, pad_;      // first workgroup of the member in the merged dispatch; 0xFFFFFFFF in the unused rows
 };
-struct AvoidGroupTable { AvoidGroupMember m[AVOID_GROUP_MAX]; };
+struct AvoidGroupTable {
+  AvoidGroupMember m[AVOID_GROUP_MAX];
+  unsigned* pipe_fault; unsigned long long pipe_limit;      // the pipelined form only (below): the group's fault word, and the time limit of a wait in wall_clock64 ticks
+};
 typedef const __attribute__((address_space(4))) AvoidGroupTable CGroupTable4;
-template <bool FAST, bool SERVE, bool GROUP = false>
+
+// PIPED (group option "pipeline_depth"; only with GROUP and SERVE): consecutive rounds of a group run on different hardware queues with
+// nothing between them on the host side, and workgroup i of round r waits HERE for workgroup i of round r - 1 - the only workgroup whose stores it reads (a
+// lane's step reads what the same lane's previous step wrote; the tally and the episode counters are integer atomic adds).  One epoch word per workgroup
+// (`epoch`, PIPE_WORD_STRIDE words apart: two workgroups never share a 128-byte line), zeroed by the host when a sequence starts:
+//   consumer, before any load of state / flags / steps / actions: lane 0 of the physics wave polls its word, relaxed at agent scope with s_sleep between the
+//     polls, until it holds wait_epoch (0: the first round of a sequence, nothing to wait for); then ONE agent-scope acquire (this CU's L1 holds no line
+//     from before it), s_waitcnt vmcnt(0) (the invalidate has completed), the workgroup barrier, and then the loads of all three waves;
+//   producer, after the rollout epilogue: every storing wave drains its stores (the controller wave before the trailing barrier, which is the barrier
+//     between its stores and the signal; the physics wave, which stores everything else and signals, after the epilogue); lane 0 of the physics wave then
+//     does ONE agent-scope release (the XCD's L2 written back), s_waitcnt vmcnt(0) written as asm (the compiler drops the builtin's wait where it can prove
+//     the wave's counter empty, and the flag would overtake the write-back), and a relaxed agent-scope store of publish_epoch.
+// Everything handed over is addressed per lane (vector loads behind the acquire); what the scalar path reads - the table, the epilogue block, the reset
+// image - is not written during a sequence.
+// The wait is bounded (pipe_give_up): a workgroup that gives up ORs a code into the group's fault word, does NOT step, publishes its epoch all the same
+// and exits, so the rounds behind it see the fault word and drain in microseconds; the host reads the word wherever it waits for the device (D3IL_ESTATE).
+constexpr int PIPE_WORD_STRIDE = 32, PIPE_MAX_DEPTH = 4, PIPE_MAX_WG = 256;
+constexpr unsigned PIPE_FAULT_TIMEOUT = 1u, PIPE_FAULT_CHAINED = 2u;
+typedef __attribute__((address_space(1))) unsigned GU32;
+// THE give-up decision of a waiting workgroup, in one place (reviewed by reading - no test makes a workgroup wait in vain): a fault
+// word that is already non-zero (some workgroup of the sequence gave up: what this one waits for may never come, or is not worth having), or the time limit
+__device__ __forceinline__ bool pipe_give_up(unsigned fault_word, unsigned long long waited_ticks, unsigned long long limit_ticks) {
+  return fault_word != 0u || waited_ticks > limit_ticks;
+}
+// one lane: 0 when the word holds `want`, else the code of the give-up
+__device__ __forceinline__ unsigned pipe_wait(GU32* word, unsigned want, GU32* fault, unsigned long long limit_ticks) {
+  const unsigned long long t0 = wall_clock64();
+  while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
+    const unsigned f = __hip_atomic_load(fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (pipe_give_up(f, wall_clock64() - t0, limit_ticks)) return f != 0u ? PIPE_FAULT_CHAINED : PIPE_FAULT_TIMEOUT;
+    __builtin_amdgcn_s_sleep(16);
+  }
+  return 0u;
+}
+template <bool FAST, bool SERVE, bool GROUP = false, bool PIPED = false>
 __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(typename std::conditional<GROUP, const AvoidGroupTable*, const PandaConsts*>::type __restrict__ cp, double* __restrict__ state,
                                                                   unsigned* __restrict__ flags, int* __restrict__ steps,
                                                                   const double* __restrict__ actions, float* __restrict__ obs,
                                                                   unsigned char* __restrict__ done, unsigned char* __restrict__ success,
                                                                   unsigned short* __restrict__ mode, int n, int stride, int n_substeps, int max_steps,
-                                                                  const AvoidEpilogue* __restrict__ ep, unsigned t_next) {
+                                                                  const AvoidEpilogue* __restrict__ ep, unsigned t_next,
+                                                                  unsigned* epoch, unsigned wait_epoch, unsigned publish_epoch) {
+  static_assert(!PIPED || (GROUP && SERVE), "the pipelined form is a three-wave group form");
   __shared__ double xch[2][2 * NARM][WAVE];
   __shared__ double trg[2][2 * NARM + 1][WAVE];     // sin / cos of ikq (controller) and of the arm joints (physics) carried across the sub-steps: parked in LDS between them
   extern __shared__ double rx_smem[];             // SERVE: the rare-path exchange area
-  __shared__ unsigned long long ep_arg[3];        // the epilogue's two arguments and the workgroup index wait here for the end of the launch (written and read by the physics wave): nothing new is alive across the sub-step loop
+  __shared__ unsigned long long ep_arg[PIPED ? 5 : 3];      // the epilogue's two arguments and the workgroup index (PIPE: and the epoch word with its value) wait here for the end of the launch (written and read by the physics wave): nothing new is alive across the sub-step loop
   const int lane = threadIdx.x & (WAVE - 1);
   const int role = threadIdx.x / WAVE;          // wave-uniform: 0 controller, 1 physics, 2 (SERVE) the rare constraint paths
   RareXch rx; rx.buf = rx_smem; rx.ctl = (int*)(rx_smem + RX_ROWS * WAVE); rx.lane = lane; rx.seq = 0;
+  if constexpr (PIPED) {
+    // the consumer side of the hand-off (see above), first of all: nothing of it is alive behind its barrier.  pipe_code: what lane 0 of the physics wave
+    // got, for all three waves
+    __shared__ unsigned pipe_code;
+    if (role == 1) {
+      CGroupTable4* gt = (CGroupTable4*)(unsigned long long)cp;
+      unsigned* const word_p = epoch + (size_t)blockIdx.x * PIPE_WORD_STRIDE;
+      GU32* word = (GU32*)(unsigned long long)word_p;
+      unsigned code = 0u;
+      if (wait_epoch != 0u) {
+        if (lane == 0) {
+          GU32* fault = (GU32*)(unsigned long long)gt->pipe_fault;
+          code = pipe_wait(word, wait_epoch, fault, gt->pipe_limit);
+          if (code != 0u) {      // the give-up: the fault word, and the epoch all the same - nothing is handed over, so no release
+            __hip_atomic_fetch_or(fault, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(word, publish_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      if (lane == 0) pipe_code = code;
+      ep_arg[3] = (unsigned long long)word_p; ep_arg[4] = publish_epoch;      // parked for the producer side (every lane stores the same words, as below)
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(pipe_code) != 0u) return;      // workgroup-uniform: nobody steps
+  }
   unsigned wg_index = blockIdx.x;               // the workgroup's index inside its handle
   if constexpr (GROUP) {
     CGroupTable4* gt = (CGroupTable4*)(unsigned long long)cp;
@@ -337,6 +403,7 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
 #pragma unroll
       for (int i = 0; i < NARM; i++) { so[(D3IL_STATE_IK_Q + i) * (size_t)stride] = ikq[i]; so[(D3IL_STATE_IK_QD + i) * (size_t)stride] = ikqd[i]; }
     }
+    if constexpr (PIPED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's stores are out before the barrier behind which the physics wave signals
     __syncthreads();      // the trailing barrier (see the physics wave)
   } else if (SERVE && role == 2) {
     double warm[6];
@@ -435,6 +502,17 @@ __global__ __launch_bounds__((SERVE ? 3 : 2) * WAVE) void k_avoiding_step_split(
     if (ep_bits != 0ull) {
       const unsigned wg = __builtin_amdgcn_readfirstlane((unsigned)ep_arg[2]);
       avoiding_tail_lane(*(CEpilogue4*)ep_bits, __builtin_amdgcn_readfirstlane((unsigned)ep_arg[1]), (int)(wg * WAVE + lane_now));
+    }
+    if constexpr (PIPED) {
+      // the producer side of the hand-off (see above): this wave's stores drained, then one lane releases and publishes
+      const unsigned w_lo = __builtin_amdgcn_readfirstlane((unsigned)ep_arg[3]), w_hi = __builtin_amdgcn_readfirstlane((unsigned)(ep_arg[3] >> 32));
+      const unsigned pub = __builtin_amdgcn_readfirstlane((unsigned)ep_arg[4]);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane_now == 0u) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store((GU32*)((unsigned long long)w_lo | ((unsigned long long)w_hi << 32)), pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
 }
@@ -1065,6 +1143,10 @@ static inline bool gen_task(int task_id) {      // the tasks of the generic engi
 }
 
 constexpr int RG_SLOTS = 2, RG_SAMPLE = 8;
+// Group option "pipeline_timeout_ms", default: a workgroup waits at most from the start of its round to the end of the round before - 1.17 ms at the longest
+// in the trace of the default bench command at depth 3 (profiles/r12, tools/round_overlap.py "lead"), about (depth - 1) steps - and a foreign kernel that
+// holds the chip adds its own length; 2 s is some 1700 times that.
+constexpr int PIPE_TIMEOUT_MS_DEFAULT = 2000;
 struct d3il_handle_s {
   int task_id, n, stride, device;
   PandaConsts hc;          // host copy
@@ -1139,8 +1221,32 @@ struct d3il_group_s {
   int n_sets; d3il_dispatch_set set[AVOID_GROUP_MAX];      // sets beyond n_sets keep the events and the table they once made until the group is destroyed
   int n_pending; bool busy;      // n_pending: over all sets.  busy: a flush or a merged launch is running (the library calls it makes must not flush again)
   bool quiet; int64_t n_merged, n_joined;      // host counters: merged dispatches (one per set and step), and those that joined
+  // option "pipeline_depth" = D: round r of a running sequence launches on the stream of the (r mod D)-th launch stream with no event
+  // between the rounds; the workgroups order themselves on the device (k_avoiding_step_split<.., PIPED>).  pipe_active: a sequence is running - pipe_d launch
+  // streams, pipe_r rounds so far.  d_epoch: one word per workgroup, PIPE_WORD_STRIDE apart, an allocation of its own (zeroed when a sequence starts);
+  // d_fault: the fault word (an allocation of its own: it outlives the sequences until the host has read it).  pipe_unread: pipelined rounds went out since
+  // the fault word was last read.
+  int pipe_depth, pipe_timeout_ms, cu_count, cu_device, wall_khz;      // cu_count: what the residency rule counts on (option "pipeline_cu_budget"; default cu_device, the device's)
+  unsigned* d_epoch; unsigned* d_fault;
+  bool pipe_made, pipe_active, pipe_unread; int pipe_d; uint32_t pipe_r;
+  hipStream_t pipe_stream[PIPE_MAX_DEPTH]; hipEvent_t ev_pipe[PIPE_MAX_DEPTH], ev_pipe_start;
+  int64_t n_pipelined, n_pipe_faults;
 };
-static inline void group_arm(d3il_group_s* g) { for (int k = 0; k < AVOID_GROUP_MAX; k++) g->set[k].armed = true; }
+// The end of a pipelined sequence: between its rounds no member stream is ordered with respect to the step's memory, so whatever ends it puts every member
+// stream behind the last round of every launch stream (one event per launch stream; the launch streams are member streams).  Called through group_arm:
+// everything that arms the next merged round ends the sequence first.  A failure here leaves the device synchronised instead.
+static void pipe_end(d3il_group_s* g) {
+  if (!g->pipe_active) return;
+  g->pipe_active = false;
+  bool ok = hipSetDevice(g->device) == hipSuccess;
+  for (int k = 0; k < g->pipe_d && ok; k++) ok = hipEventRecord(g->ev_pipe[k], g->pipe_stream[k]) == hipSuccess;
+  for (int i = 0; i < g->count && ok; i++) {
+    hipStream_t s = g->m[i]->grp_stream;
+    for (int k = 0; k < g->pipe_d && ok; k++) if (g->pipe_stream[k] != s) ok = hipStreamWaitEvent(s, g->ev_pipe[k], 0) == hipSuccess;
+  }
+  if (!ok) { (void)hipGetLastError(); (void)hipDeviceSynchronize(); }
+}
+static inline void group_arm(d3il_group_s* g) { pipe_end(g); for (int k = 0; k < AVOID_GROUP_MAX; k++) g->set[k].armed = true; }
 // Creation flags of the library's own events: the ordering events of a step group (ev_join, ev_done) and the timing rings, the
 // group's and every handle's.  hipEventDisableSystemFence: the record carries no system-scope cache writeback and invalidation (measured: about 1.4 us less per
 // record on the launch queue, tools/probe/event_hops.hip).  Nothing reads results through these events: the host sees device memory only behind a stream or
@@ -1179,6 +1285,7 @@ extern "C" {
 // single-handle path, in group order - so that no call sees buffers a deferred step has not advanced yet.  Such a call may queue work on the member's stream
 // or change what a step launches: the next merged round joins the members' streams again (group_arm), pending round or not.
 static int group_flush(d3il_group_s* g);
+static int pipe_check_fault(d3il_group_s* g, const char* who);
 static inline int group_settle(d3il_handle_s* h) {
   if (!h || !h->group || h->group->busy) return D3IL_OK;
   group_arm(h->group);
@@ -1358,10 +1465,12 @@ int d3il_create(int task_id, int n_envs, int device_id, const void* model_blob, 
 int d3il_destroy(d3il_handle h) {
   if (!h) return fail(D3IL_EINVAL, "d3il_destroy: null handle");
   (void)hipSetDevice(h->device);
+  d3il_group_s* was_in = h->group;
   group_leave(h);      // a member of a step group: the round is flushed, the others go on without it
   (void)hipDeviceSynchronize();
+  const int rc_f = pipe_check_fault(was_in, "d3il_destroy");      // leaving a group whose pipelined rounds gave up is reported, the handle is freed all the same
   free_handle(h);
-  return D3IL_OK;
+  return rc_f;
 }
 
 int d3il_start(d3il_handle h, const double* init_qpos7) {
@@ -1601,10 +1710,10 @@ static int step_launch(d3il_handle h, const double* actions, void* stream, const
   // the third wave (rare constraint paths) while a CU hosts one workgroup anyway; at saturation the two-wave form keeps two workgroups per CU
   if (split && nwg <= h->serve_max_wg)
     hipLaunchKernelGGL((k_avoiding_step_split<true, true>), dim3(nwg), dim3(3 * WAVE), AVOID_LDS_SERVE, s, h->dc, b.state, b.flags, b.step_count, actions, b.obs, b.done,
-                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, ep, t_next);
+                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, ep, t_next, (unsigned*)nullptr, 0u, 0u);
   else if (split)
     hipLaunchKernelGGL((k_avoiding_step_split<true, false>), dim3(nwg), dim3(2 * WAVE), 0, s, h->dc, b.state, b.flags, b.step_count, actions, b.obs, b.done,
-                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, ep, t_next);
+                       b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, ep, t_next, (unsigned*)nullptr, 0u, 0u);
   else if (h->fast)
     hipLaunchKernelGGL((k_avoiding_step<true, true>), dim3(nwg), dim3(WAVE), lds, s, h->dc, b.state, b.flags, b.step_count, actions, b.obs, b.done,
                        b.success, b.mode, h->n, h->stride, h->hc.n_substeps, h->hc.max_steps, h->lanes);
@@ -1634,6 +1743,7 @@ int d3il_get_state(d3il_handle h, double* state, int32_t state_rows, uint32_t* f
   if (int rc_ = check_state_rows(h, state, state_rows, "d3il_get_state")) return rc_;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipDeviceSynchronize());
+  if (int rc_ = pipe_check_fault(h->group, "d3il_get_state")) return rc_;
   if (state) HIPCHK(hipMemcpy2D(state, (size_t)h->n * 8, h->buf.state, (size_t)h->stride * 8, (size_t)h->n * 8, h->state_rows, hipMemcpyDeviceToHost));
   if (flags) HIPCHK(hipMemcpy(flags, h->buf.flags, (size_t)h->n * 4, hipMemcpyDeviceToHost));
   if (steps) HIPCHK(hipMemcpy(steps, h->buf.step_count, (size_t)h->n * 4, hipMemcpyDeviceToHost));
@@ -2092,6 +2202,7 @@ int d3il_timing_stats(d3il_handle h, double* out4) {
   if (!h || !out4) return fail(D3IL_EINVAL, "d3il_timing_stats: null argument");
   HIPCHK(hipSetDevice(h->device));
   while (h->ring_drained < h->ring_head) { if (int rc = timing_drain_one(h)) return rc; }
+  if (int rc_ = pipe_check_fault(h->group, "d3il_timing_stats")) return rc_;
   out4[0] = h->t_sum; out4[1] = h->t_n ? h->t_min : 0.0; out4[2] = h->t_max; out4[3] = (double)h->t_n;
   return D3IL_OK;
 }
@@ -2250,7 +2361,9 @@ static int rollout_step_single(d3il_handle h, uint64_t seed, uint64_t env_offset
 // (DESIGN section 32): the caller queues nothing on those streams between rounds, and only an ARMED round waits before its launch.  Group option
 // "dispatch_sets" (DESIGN section 34): K contiguous runs of members launch on their own, each as described here with "the set" for "the group"; a dispatch
 // lasts as long as its slowest workgroup, and a set pays for the slow workgroups of its own members only.  Ending a round stays on the side of joining: a
-// flush ends the pending rounds of ALL sets and arms all of them.
+// flush ends the pending rounds of ALL sets and arms all of them.  Group option "pipeline_depth" (DESIGN section 35): consecutive rounds of a one-set quiet
+// group launch on D member streams in turn with nothing between them, and each workgroup waits on the device for its own predecessor of the round before;
+// whatever arms a round ends the running sequence first (pipe_end).
 static int group_flush(d3il_group_s* g) {
   if (g->busy) return D3IL_OK;
   group_arm(g);      // the members launch on their own streams now: the next merged round has to come behind them
@@ -2265,6 +2378,51 @@ static int group_flush(d3il_group_s* g) {
   for (int k = 0; k < g->n_sets; k++) g->set[k].n_pending = 0;
   g->n_pending = 0; g->busy = false;
   return rc;
+}
+// "pipeline_depth": what a pipelined round needs besides the set's own events - the epoch block and the fault word (allocations of their own; the epoch
+// block is what the memset of an arming round zeroes, whole and from its start), one event per launch stream and the start event.
+constexpr size_t PIPE_EPOCH_BYTES = (size_t)PIPE_MAX_WG * PIPE_WORD_STRIDE * sizeof(unsigned);
+static int pipe_prepare(d3il_group_s* g) {
+  if (g->pipe_made) return D3IL_OK;
+  if (!g->d_epoch) HIPCHK(hipMalloc(&g->d_epoch, PIPE_EPOCH_BYTES));
+  if (!g->d_fault) { HIPCHK(hipMalloc(&g->d_fault, 16)); HIPCHK(hipMemset(g->d_fault, 0, 16)); }
+  for (int k = 0; k < PIPE_MAX_DEPTH; k++) if (!g->ev_pipe[k]) HIPCHK(hipEventCreateWithFlags(&g->ev_pipe[k], EV_ORDER_FLAGS));
+  if (!g->ev_pipe_start) HIPCHK(hipEventCreateWithFlags(&g->ev_pipe_start, EV_ORDER_FLAGS));
+  g->pipe_made = true;
+  return D3IL_OK;
+}
+// The depth of the round about to launch, and its launch streams.  The option asks; the round gets it only while a waiting workgroup can never keep its
+// predecessor off the chip: the three-wave form (one workgroup per CU: each of its waves takes the registers of a whole SIMD), and
+// depth x workgroups within the device's CU count, so that every round that can be in flight is resident together with the ones it waits for.  One dispatch
+// set and quiet streams (checked when the option is set); as many distinct member streams as the depth, otherwise the depth shrinks to what there is.
+static int pipe_round_depth(const d3il_group_s* grp, const d3il_dispatch_set* g, unsigned total, bool serve, hipStream_t* ls) {
+  if (grp->pipe_depth < 2 || !grp->quiet || grp->n_sets != 1 || !serve || total > (unsigned)PIPE_MAX_WG) return 1;
+  if ((long)grp->pipe_depth * (long)total > (long)grp->cu_count || grp->wall_khz <= 0) return 1;
+  int n = 0;
+  for (int i = 0; i < g->count && n < grp->pipe_depth; i++) {
+    bool seen = false;
+    for (int k = 0; k < n; k++) seen = seen || ls[k] == g->m[i]->grp_stream;
+    if (!seen) ls[n++] = g->m[i]->grp_stream;
+  }
+  return n >= 2 ? n : 1;
+}
+// Wherever the library waits for the device on behalf of a member it reads the group's fault word (the caller has ended the sequence: group_settle): a
+// workgroup that gave up waiting (k_avoiding_step_split<.., PIPED>) and every workgroup behind it did not step, so what the members hold is not the state
+// after the steps the caller counted.  D3IL_ESTATE, once per fault: the word is cleared, and the next sequence runs again.
+static int pipe_check_fault(d3il_group_s* g, const char* who) {
+  if (!g || !g->pipe_unread || !g->d_fault) return D3IL_OK;
+  HIPCHK(hipSetDevice(g->device));
+  HIPCHK(hipDeviceSynchronize());
+  unsigned w = 0;
+  HIPCHK(hipMemcpy(&w, g->d_fault, sizeof w, hipMemcpyDeviceToHost));
+  g->pipe_unread = false;
+  if (w == 0u) return D3IL_OK;
+  g->n_pipe_faults++;
+  const unsigned zero = 0u;
+  HIPCHK(hipMemcpy(g->d_fault, &zero, sizeof zero, hipMemcpyHostToDevice));
+  return fail(D3IL_ESTATE, std::string(who) + ": a workgroup of a pipelined step round gave up waiting for its predecessor (fault word " + std::to_string(w) +
+                               ((w & PIPE_FAULT_TIMEOUT) ? ": the time limit \"pipeline_timeout_ms\" ran out" : ": behind an earlier give-up") +
+                               "); it and the rounds behind it did not step - the members do not hold the state after the steps that were called");
 }
 // The merged dispatch of ONE dispatch set (with "dispatch_sets" 1: of the group).  Everything it records, waits for, reads and writes belongs to the set `g`
 // and its members: nothing is queued on a stream of another set, so the sets of a group run independently of each other.
@@ -2292,19 +2450,48 @@ static int group_launch_locked(d3il_group_s* grp, d3il_dispatch_set* g) {
     total += (unsigned)((h->n + WAVE - 1) / WAVE); serve_budget += h->serve_max_wg;
   }
   hipStream_t s0 = g->m[0]->grp_stream;
+  const bool serve = (long)total <= (long)serve_budget;      // three waves while the merged dispatch stays inside what the members' thresholds allow together (one workgroup per CU), otherwise two
+  // "pipeline_depth" (DESIGN section 35): the depth this round runs with, and its launch streams - the first `depth` distinct member streams, in group
+  // order (ls[0] == s0).  Depth 1 is the path below as it was.
+  hipStream_t ls[PIPE_MAX_DEPTH];
+  const int depth = pipe_round_depth(grp, g, total, serve, ls);
+  if (depth >= 2) {
+    if (int rc = pipe_prepare(grp)) return rc;
+    tab.pipe_fault = grp->d_fault; tab.pipe_limit = (unsigned long long)grp->pipe_timeout_ms * (unsigned long long)grp->wall_khz;
+  } else pipe_end(grp);
   // the table follows its fields like the epilogue block: rewritten only when one changed, and then behind everything that may still read the old one
   if (!g->table_valid || std::memcmp(&g->table_host, &tab, sizeof tab) != 0) {
     if (g->table_valid) HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(g->d_table, &tab, sizeof tab, hipMemcpyHostToDevice));
     g->table_host = tab; g->table_valid = true;
+    if (grp->pipe_active) { pipe_end(grp); g->armed = true; }      // (another workgroup count, other buffers: the epochs start again)
+  }
+  // a pipelined round is ARMING when it starts a sequence: the first round, the first after anything that armed the set, another depth or other launch streams
+  bool pipe_arming = false;
+  if (depth >= 2) {
+    bool same = grp->pipe_active && grp->pipe_d == depth && grp->pipe_r < 0xFFFFFFF0u;
+    for (int k = 0; k < depth && same; k++) same = grp->pipe_stream[k] == ls[k];
+    pipe_arming = g->armed || !same;
+    if (pipe_arming) pipe_end(grp);
   }
   // the join: s0 comes behind everything queued on the other members' streams.  A continuing round of a quiet group queues none: the other streams hold
   // only their waits for the earlier rounds, and the dispatch follows the previous one on its own queue
-  const bool join = !grp->quiet || g->armed;
+  const bool join = depth >= 2 ? pipe_arming : (!grp->quiet || g->armed);
   if (join) for (int i = 1; i < g->count; i++) {
     if (g->m[i]->grp_stream == s0) continue;
     HIPCHK(hipEventRecord(g->ev_join[i], g->m[i]->grp_stream));
     HIPCHK(hipStreamWaitEvent(s0, g->ev_join[i], 0));
+  }
+  hipStream_t sl = s0;      // the stream of this round's launch
+  if (depth >= 2) {
+    if (pipe_arming) {      // behind the join: the epoch words zeroed, then the other launch streams let go
+      HIPCHK(hipMemsetAsync(grp->d_epoch, 0, PIPE_EPOCH_BYTES, s0));
+      HIPCHK(hipEventRecord(grp->ev_pipe_start, s0));
+      for (int k = 1; k < depth; k++) HIPCHK(hipStreamWaitEvent(ls[k], grp->ev_pipe_start, 0));
+      grp->pipe_active = true; grp->pipe_d = depth; grp->pipe_r = 0;
+      for (int k = 0; k < depth; k++) grp->pipe_stream[k] = ls[k];
+    }
+    sl = ls[grp->pipe_r % (unsigned)depth];
   }
   hipEvent_t t0 = nullptr, t1 = nullptr;
   if (g->timing) {
@@ -2315,23 +2502,26 @@ static int group_launch_locked(d3il_group_s* grp, d3il_dispatch_set* g) {
     // a member reads the pair of a slot before the group records it again: a slot comes round after 128 merged launches, and each was a launch of every member
     for (int i = 0; i < g->count; i++) { d3il_handle_s* h = g->m[i]; if (h->ring_head - h->ring_drained >= 128) { if (int rc = timing_drain_one(h)) return rc; } }
     t0 = g->ring0[g->ring_head % 128]; t1 = g->ring1[g->ring_head % 128];
-    HIPCHK(hipEventRecord(t0, s0));
+    HIPCHK(hipEventRecord(t0, sl));
   }
   const d3il_handle_s* h0 = g->m[0];
   const unsigned t_next = g->t + 1u;
-  // three waves while the merged dispatch stays inside what the members' thresholds allow together (one workgroup per CU), otherwise two
-  if ((long)total <= (long)serve_budget)
+  if (depth >= 2)      // round r of the sequence waits for epoch r (0: nothing) and publishes r + 1
+    hipLaunchKernelGGL((k_avoiding_step_split<true, true, true, true>), dim3(total), dim3(3 * WAVE), AVOID_LDS_SERVE, sl, (const AvoidGroupTable*)g->d_table, (double*)nullptr, (unsigned*)nullptr,
+                       (int*)nullptr, (const double*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, (unsigned short*)nullptr, 0, 0, h0->hc.n_substeps,
+                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next, grp->d_epoch, (unsigned)grp->pipe_r, (unsigned)grp->pipe_r + 1u);
+  else if (serve)
     hipLaunchKernelGGL((k_avoiding_step_split<true, true, true>), dim3(total), dim3(3 * WAVE), AVOID_LDS_SERVE, s0, (const AvoidGroupTable*)g->d_table, (double*)nullptr, (unsigned*)nullptr,
                        (int*)nullptr, (const double*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, (unsigned short*)nullptr, 0, 0, h0->hc.n_substeps,
-                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next);
+                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next, (unsigned*)nullptr, 0u, 0u);
   else
     hipLaunchKernelGGL((k_avoiding_step_split<true, false, true>), dim3(total), dim3(2 * WAVE), 0, s0, (const AvoidGroupTable*)g->d_table, (double*)nullptr, (unsigned*)nullptr,
                        (int*)nullptr, (const double*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, (unsigned short*)nullptr, 0, 0, h0->hc.n_substeps,
-                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next);
+                       h0->hc.max_steps, (const AvoidEpilogue*)nullptr, t_next, (unsigned*)nullptr, 0u, 0u);
   HIPCHK(hipGetLastError());
   hipEvent_t done_ev = g->ev_done;
   if (g->timing) {
-    HIPCHK(hipEventRecord(t1, s0));
+    HIPCHK(hipEventRecord(t1, sl));
     done_ev = t1;      // the end of the timed pair is the event the other streams wait for
     for (int i = 0; i < g->count; i++) {
       d3il_handle_s* h = g->m[i];
@@ -2339,9 +2529,11 @@ static int group_launch_locked(d3il_group_s* grp, d3il_dispatch_set* g) {
       h->ring_alt0[slot] = t0; h->ring_alt1[slot] = t1; h->ev0 = t0; h->ev1 = t1; h->ev_valid = true; h->ring_head++;
     }
     g->ring_head++;
-  } else HIPCHK(hipEventRecord(done_ev, s0));
-  for (int i = 1; i < g->count; i++) if (g->m[i]->grp_stream != s0) HIPCHK(hipStreamWaitEvent(g->m[i]->grp_stream, done_ev, 0));
+  } else if (depth < 2) HIPCHK(hipEventRecord(done_ev, s0));
+  // (a pipelined round records no ev_done and queues no wait: the member streams come behind the sequence when it ends, pipe_end)
+  if (depth < 2) for (int i = 1; i < g->count; i++) if (g->m[i]->grp_stream != s0) HIPCHK(hipStreamWaitEvent(g->m[i]->grp_stream, done_ev, 0));
   for (int i = 0; i < g->count; i++) { d3il_handle_s* h = g->m[i]; fused_step_end(h, h->grp_seed, h->grp_off, h->grp_t, h->grp_actions, (void*)h->grp_stream); }
+  if (depth >= 2) { grp->pipe_r++; grp->n_pipelined++; grp->pipe_unread = true; }
   grp->n_merged++; grp->n_joined += join ? 1 : 0;
   g->armed = false;      // the set's next round continues this one, unless something else happens to the group first
   return D3IL_OK;
@@ -2450,6 +2642,12 @@ int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out) {
   if (hipFuncSetAttribute((const void*)k_avoiding_step_split<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AVOID_LDS_SERVE) != hipSuccess) (void)hipGetLastError();
   d3il_group_s* g = new d3il_group_s();
   g->device = handles[0]->device; g->count = count;
+  g->pipe_depth = 1; g->pipe_timeout_ms = PIPE_TIMEOUT_MS_DEFAULT;
+  // what "pipeline_depth" is checked against: the CU count, and the rate of the clock the waiting workgroups read (wall_clock64; 0 = unknown: no pipelining)
+  if (hipDeviceGetAttribute(&g->cu_count, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) { g->cu_count = 0; (void)hipGetLastError(); }
+  g->cu_device = g->cu_count;
+  if (hipDeviceGetAttribute(&g->wall_khz, hipDeviceAttributeWallClockRate, g->device) != hipSuccess) { g->wall_khz = 0; (void)hipGetLastError(); }
+  if (hipFuncSetAttribute((const void*)k_avoiding_step_split<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AVOID_LDS_SERVE) != hipSuccess) (void)hipGetLastError();
   group_arm(g);      // the first merged round comes behind the members' single launches
   for (int i = 0; i < count; i++) { g->m[i] = handles[i]; handles[i]->group = g; handles[i]->grp_set = 0; handles[i]->grp_pending = false; }
   group_partition(g, 1);
@@ -2465,6 +2663,7 @@ int d3il_group_set_option(d3il_group g, const char* name, int value) {
   if (!g || !name) return fail(D3IL_EINVAL, "d3il_group_set_option: null argument");
   if (std::strcmp(name, "quiet_streams") == 0) {
     if (value != 0 && value != 1) return fail(D3IL_EINVAL, "quiet_streams must be 0 or 1");
+    if (value == 0 && g->pipe_depth >= 2) return fail(D3IL_EINVAL, "quiet_streams 0: pipeline_depth >= 2 needs quiet_streams 1");
     group_arm(g);
     if (g->n_pending) { if (int rc = group_flush(g)) return rc; }      // a round that has begun ends under the setting it began with
     g->quiet = value != 0;
@@ -2472,10 +2671,33 @@ int d3il_group_set_option(d3il_group g, const char* name, int value) {
   }
   if (std::strcmp(name, "dispatch_sets") == 0) {
     if (value < 1 || value > g->count) return fail(D3IL_EINVAL, "dispatch_sets must be 1 .. the number of members");
+    if (value != 1 && g->pipe_depth >= 2) return fail(D3IL_EINVAL, "dispatch_sets: pipeline_depth >= 2 needs one dispatch set");
     group_arm(g);
     if (g->n_pending) { if (int rc = group_flush(g)) return rc; }      // rounds that have begun end through the single path
     (void)hipSetDevice(g->device);
     group_partition(g, value);
+    return D3IL_OK;
+  }
+  if (std::strcmp(name, "pipeline_depth") == 0) {
+    if (value < 1 || value > PIPE_MAX_DEPTH) return fail(D3IL_EINVAL, "pipeline_depth must be 1 .. 4");
+    if (value >= 2 && (!g->quiet || g->n_sets != 1)) return fail(D3IL_EINVAL, "pipeline_depth >= 2 needs quiet_streams 1 and dispatch_sets 1");
+    group_arm(g);      // ends a running sequence: the next merged round starts from the joined form under the new depth
+    if (g->n_pending) { if (int rc = group_flush(g)) return rc; }
+    g->pipe_depth = value;
+    return D3IL_OK;
+  }
+  if (std::strcmp(name, "pipeline_cu_budget") == 0) {      // the CUs the residency rule may count on: the device's (default), or fewer
+    if (value < 1 || value > g->cu_device) return fail(D3IL_EINVAL, "pipeline_cu_budget must be 1 .. the device's CU count");
+    group_arm(g);
+    if (g->n_pending) { if (int rc = group_flush(g)) return rc; }
+    g->cu_count = value;
+    return D3IL_OK;
+  }
+  if (std::strcmp(name, "pipeline_timeout_ms") == 0) {
+    if (value < 1 || value > 600000) return fail(D3IL_EINVAL, "pipeline_timeout_ms must be 1 .. 600000");
+    group_arm(g);      // (the limit travels in the group's table: the next round rewrites it behind a device synchronisation)
+    if (g->n_pending) { if (int rc = group_flush(g)) return rc; }
+    g->pipe_timeout_ms = value;
     return D3IL_OK;
   }
   return fail(D3IL_EINVAL, std::string("d3il_group_set_option: unknown option ") + name);
@@ -2485,12 +2707,22 @@ int d3il_group_stats(d3il_group g, int64_t* merged_rounds, int64_t* joined_round
   *merged_rounds = g->n_merged; *joined_rounds = g->n_joined;      // host counters: no flush, no device access
   return D3IL_OK;
 }
+int d3il_group_pipeline_stats(d3il_group g, int64_t* pipelined_rounds, int64_t* pipeline_faults) {
+  if (!g || !pipelined_rounds || !pipeline_faults) return fail(D3IL_EINVAL, "d3il_group_pipeline_stats: null argument");
+  *pipelined_rounds = g->n_pipelined; *pipeline_faults = g->n_pipe_faults;      // host counters: no flush, no device access
+  return D3IL_OK;
+}
 int d3il_group_destroy(d3il_group g) {
   if (!g) return fail(D3IL_EINVAL, "d3il_group_destroy: null group");
   (void)hipSetDevice(g->device);
-  const int rc = group_flush(g);
+  int rc = group_flush(g);
   while (g->count > 0) group_leave(g->m[g->count - 1]);
   (void)hipDeviceSynchronize();      // the last merged launch reads the table
+  if (int rc_f = pipe_check_fault(g, "d3il_group_destroy")) { if (!rc) rc = rc_f; }
+  for (int k = 0; k < PIPE_MAX_DEPTH; k++) if (g->ev_pipe[k]) (void)hipEventDestroy(g->ev_pipe[k]);
+  if (g->ev_pipe_start) (void)hipEventDestroy(g->ev_pipe_start);
+  if (g->d_epoch) (void)hipFree(g->d_epoch);
+  if (g->d_fault) (void)hipFree(g->d_fault);
   for (int k = 0; k < AVOID_GROUP_MAX; k++) {
     d3il_dispatch_set* s = &g->set[k];
     if (s->ev_made) { for (int i = 0; i < AVOID_GROUP_MAX; i++) (void)hipEventDestroy(s->ev_join[i]); (void)hipEventDestroy(s->ev_done); (void)hipFree(s->d_table); }

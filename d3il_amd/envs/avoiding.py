@@ -47,7 +47,15 @@ class StepGroup:
     possible.  Every set is a group of its own as far as launching goes: it launches when all ITS members have called, on its first member's stream, and
     may run steps ahead of the other sets; ``stats()`` then counts one merged dispatch per set and step.  Everything that ends a round (``flush()``, another
     library call on a member, a call that does not fit) ends the pending rounds of all sets.  ``try_option`` is ``set_option`` for a library that may be
-    older than the option: it returns False and changes nothing when the library does not know the name."""
+    older than the option: it returns False and changes nothing when the library does not know the name.
+
+    ``set_option("pipeline_depth", d)`` (default 1; needs ``quiet_streams`` and one dispatch set) lets d consecutive rounds overlap:
+    round r launches on the r mod d-th of the first d member streams with no event between the rounds, and every workgroup waits on the device for its own
+    predecessor of the round before.  THE CONTRACT of a pipelined sequence: between two rounds NO member stream is ordered with respect to what the step
+    touches - read or write it only behind ``flush()`` (or another library call on a member), which ends the sequence and puts every member stream behind
+    its last round, or behind a device synchronisation.  A group that cannot keep all d rounds resident (the two-wave form, d x workgroups above the CU
+    count) runs with depth 1 by itself; ``pipeline_stats()`` says how many rounds were pipelined.  A workgroup that gives up waiting (option
+    ``pipeline_timeout_ms``) makes the next ``get_state`` / ``timing_stats`` / ``close`` of a member raise ``D3ilError``."""
 
     MAX_MEMBERS = 8
 
@@ -90,6 +98,14 @@ class StepGroup:
         capi.check(self.L.d3il_group_stats(self.g, C.byref(merged), C.byref(joined)))
         return merged.value, joined.value
 
+    def pipeline_stats(self):
+        """(merged rounds that ran pipelined, give-ups reported) since the group was created; host counters.  (0, 0) for a library without the option."""
+        if not capi.has_group_pipeline():
+            return 0, 0
+        rounds, faults = C.c_int64(), C.c_int64()
+        capi.check(self.L.d3il_group_pipeline_stats(self.g, C.byref(rounds), C.byref(faults)))
+        return rounds.value, faults.value
+
     def flush(self):
         """Ends a round early; with ``quiet_streams`` also the caller's re-arming point: the next merged round joins the members' streams again."""
         if self.g:
@@ -98,8 +114,9 @@ class StepGroup:
     def close(self):
         """Ends the round and returns the members to the single-handle path (before the members themselves are closed, or after: a closed member has left)."""
         if getattr(self, "g", None):
-            self.L.d3il_group_destroy(self.g)
-            self.g = None
+            g, self.g = self.g, None
+            if self.L.d3il_group_destroy(g) == -6:      # D3IL_ESTATE: a pipelined round gave up (the group is gone all the same)
+                capi.check(-6)
 
     def __del__(self):
         try:

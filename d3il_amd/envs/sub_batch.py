@@ -94,6 +94,12 @@ class SubBatchSet:
     ``join()`` flushes the group, which re-arms the library's join of the streams: torch work queued on any sub-batch stream before ``join()`` is ordered
     before the next round, work queued after a round sees that round.  Library calls on an environment (reset, get_state, options, timing) re-arm by
     themselves.  Without a group every stream is ordered as usual.
+
+    A group whose rounds are PIPELINED (``_step_group``: the library's ``pipeline_depth`` option; ``group.pipeline_stats()`` says whether
+    rounds were) has no exception: consecutive rounds are in flight on several sub-batch streams at once, and between two rounds of a running sequence NO
+    sub-batch stream - the first included - is ordered with respect to what the step touches.  ``join()`` (the flush ends the sequence and puts every
+    sub-batch stream behind its last round), any other library call on an environment, or a device synchronisation (``torch.cuda.synchronize()``)
+    restores the order; read results behind one of them.
     """
 
     def __init__(self, n: int, n_sub_batches: int, device, make_env, min_envs: int = MIN_ENVS):
@@ -132,7 +138,10 @@ class SubBatchSet:
         A group of four or more members, an even count, is cut into TWO dispatch sets (option ``dispatch_sets``) when the process has at
         least three hardware queues: the first half launches on the first sub-batch's stream, the second half on the stream of its own first sub-batch, and
         neither waits for the other's slowest workgroup.  With two queues (one of them the null stream's) both leaders would share one, and the halves would
-        run one after the other.  ``D3IL_STEP_GROUP_SETS=1|2`` overrides the choice (A/B runs); a library without the option keeps one set."""
+        run one after the other.  ``D3IL_STEP_GROUP_SETS=1|2`` overrides the choice (A/B runs); a library without the option keeps one set.
+
+        Where the library can pipeline the rounds (below), that comes first and the group keeps one set; the two sets are what is left for a library
+        without ``pipeline_depth`` (it answers "unknown option"), for fewer than three hardware queues and for a group too large to stay resident."""
         envs = [b.env for b in self.batches]
         want = hw_queues < len(envs) + 1
         if os.environ.get("D3IL_STEP_GROUP") in ("0", "1"):
@@ -144,6 +153,18 @@ class SubBatchSet:
         if len(envs) > StepGroup.MAX_MEMBERS or not capi.has_step_group():      # (an older library loaded through D3IL_LIB_PATH: today's path)
             return None
         group = StepGroup(envs, quiet_streams=capi.has_group_options())
+        # Pipelined rounds (option ``pipeline_depth``) where the library has them and the whole group, D rounds deep, stays resident
+        # with one workgroup per CU: D = min(3, members, hardware queues - 1 (the null stream's), CUs // workgroups of the group).  The group then keeps ONE
+        # dispatch set - depth and two sets together need more queues than there are.  ``D3IL_STEP_GROUP_PIPE=0|2|3`` overrides the choice (A/B runs).
+        wgs = sum((b.n + MIN_ENVS - 1) // MIN_ENVS for b in self.batches)
+        depth = min(3, len(envs), hw_queues - 1, CUS // max(1, wgs))
+        # An explicit ``D3IL_STEP_GROUP_SETS`` without it asks for that form of dispatch sets, unpipelined.
+        if os.environ.get("D3IL_STEP_GROUP_PIPE") in ("0", "2", "3"):
+            depth = int(os.environ["D3IL_STEP_GROUP_PIPE"])
+        elif os.environ.get("D3IL_STEP_GROUP_SETS") in ("1", "2"):
+            depth = 1
+        if depth >= 2 and capi.has_group_pipeline() and group.try_option("pipeline_depth", depth):
+            return group
         sets = 2 if len(envs) >= 4 and len(envs) % 2 == 0 and hw_queues >= 3 else 1
         if os.environ.get("D3IL_STEP_GROUP_SETS") in ("1", "2"):
             sets = int(os.environ["D3IL_STEP_GROUP_SETS"])

@@ -466,12 +466,36 @@ int d3il_random_rollout_step(d3il_handle h, uint64_t seed, uint64_t env_offset, 
  * Ending a round stays on the side of joining: whatever ends a round above (a call that is not eligible or does not fit ITS set's round, a second call of a
  * pending member, any other library call on a member, d3il_group_flush, a member leaving, a HIP failure) ends the pending rounds of ALL sets and arms all of
  * them.  A member that leaves shrinks its set (the next live member leads it); a set without a live member is skipped; a set of one member still launches the
- * group form.  d3il_group_stats counts merged DISPATCHES, and those that joined: K per step when every set merges. */
+ * group form.  d3il_group_stats counts merged DISPATCHES, and those that joined: K per step when every set merges.
+ *
+ * Group option "pipeline_depth" (d3il_group_set_option; default 1 = everything above holds as written).  With D = 2 .. 4 consecutive merged
+ * rounds of the group overlap: round r of a running sequence launches on the r mod D-th of the group's LAUNCH STREAMS (the first D distinct member streams, in
+ * group order) with no event between the rounds, and on the device every workgroup of round r waits for its own predecessor of round r - 1 - the only
+ * workgroup whose stores it reads - so a workgroup no longer waits for the slowest workgroup of the previous dispatch.  Results are bit for bit those of depth 1.
+ * D >= 2 needs "quiet_streams" 1 and "dispatch_sets" 1 (D3IL_EINVAL otherwise, also when one of those two is changed while D >= 2).  A round is pipelined
+ * only while a waiting workgroup can never keep its predecessor off the chip: the three-wave form (one workgroup per CU) and D x (workgroups of the dispatch) <=
+ * the device's CU count (group option "pipeline_cu_budget", 1 .. the device's count, lowers what is counted on - for a process that shares the chip with
+ * other resident work); a group that does not meet this, or whose members share streams so that fewer than two launch streams exist, silently runs with depth 1.
+ * CONTRACT of a pipelined sequence, on top of "quiet_streams": between two rounds NO member stream - the first member's included - is ordered with respect to
+ * the memory the step touches; rounds are in flight on several of them.  Whatever arms a round under "quiet_streams" (above: d3il_group_flush, any other
+ * library call on a member, a call that is not eligible, a member leaving, an option switch, a HIP failure) also ENDS the sequence: every member stream then
+ * waits for the last round of every launch stream, so work queued on a member's stream after that point sees every round, and the next merged round starts a
+ * new sequence behind what the member streams hold (the join of an armed round, then the epoch words are zeroed and the other launch streams let go).  A
+ * device or stream synchronisation by the caller orders the host as usual.  So: read or write the step's memory only behind d3il_group_flush (or another
+ * library call on a member) or behind a device synchronisation.
+ * Timing: the event pair of a pipelined round lies around its launch on its launch stream; the duration includes the time its workgroups waited for their
+ * predecessors, so it is no longer the time the step's arithmetic takes.
+ * The wait of a workgroup is bounded by the group option "pipeline_timeout_ms" (default 2000, 1 .. 600000).  A workgroup that gives up - the limit ran out, or
+ * the group's fault word is already set - sets the fault word, does NOT step, and lets its successors go, which give up at once: a faulted sequence drains in
+ * microseconds.  The library reads the fault word wherever it waits for the device on behalf of a member - d3il_get_state, d3il_timing_stats, d3il_destroy of a
+ * member, d3il_group_destroy - and answers D3IL_ESTATE once per fault (the word is then cleared): the members do not hold the state after the steps called.
+ * d3il_group_pipeline_stats: merged rounds that were pipelined, and faults reported, since the group was created; host counters. */
 typedef struct d3il_group_s* d3il_group;
 int d3il_group_create(const d3il_handle* handles, int count, d3il_group* out);
 int d3il_group_flush(d3il_group g);
 int d3il_group_set_option(d3il_group g, const char* name, int value);
 int d3il_group_stats(d3il_group g, int64_t* merged_rounds, int64_t* joined_rounds);
+int d3il_group_pipeline_stats(d3il_group g, int64_t* pipelined_rounds, int64_t* pipeline_faults);
 int d3il_group_destroy(d3il_group g);
 /* Option "graph_rollout": captures the graphs the next d3il_random_rollout_step calls with these arguments will launch, without launching anything (outside a timed region). */
 int d3il_random_rollout_prepare(d3il_handle h, uint64_t seed, uint64_t env_offset, uint32_t t, double* actions, int64_t* episode_counts_device, void* stream);
