@@ -5,6 +5,7 @@ GPU box (it is git-ignored, not gpurun-ignored).
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -13,11 +14,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libd3il_rollout.so")
 SOURCES = [os.path.join(PKG, "csrc", "rollout.hip")]
-DEPS = SOURCES + [os.path.join(PKG, "csrc", "panda_step.h"), os.path.join(PKG, "csrc", "panda_consts.h"),
-                  os.path.join(PKG, "csrc", "rigid_common.h"), os.path.join(PKG, "csrc", "policy_f16x3.h"), os.path.join(PKG, "csrc", "policy_bet.h"), os.path.join(PKG, "csrc", "policy_ddpm_gpt.h"), os.path.join(PKG, "csrc", "policy_ibc.h"), os.path.join(PKG, "csrc", "policy_act.h"), os.path.join(PKG, "csrc", "policy_ddpm_act.h"), os.path.join(PKG, "csrc", "policy_cvae.h"), os.path.join(PKG, "csrc", "gen_step.h"), os.path.join(PKG, "csrc", "gen_tree.h"), os.path.join(PKG, "csrc", "gen_kernels.h"), os.path.join(PKG, "csrc", "link_guard.h"),
-                  os.path.join(PKG, "csrc", "stack_step.h"), os.path.join(PKG, "csrc", "stack_kernels.h"), os.path.join(PKG, "csrc", "align_step.h"), os.path.join(PKG, "model", "blobs", "stacking.json"),
-                  os.path.join(PKG, "csrc", "gen_consts.cpp"), os.path.join(PKG, "model", "blobs", "avoiding.json"),
-                  os.path.join(ROOT, "include", "d3il_rollout.h"), os.path.join(ROOT, "include", "d3il_model_blob.h")]
+# every header of csrc/ by pattern (a new one cannot be forgotten), the generator source, the task models the constant blocks are derived from, the public headers
+DEPS = SOURCES + sorted(glob.glob(os.path.join(PKG, "csrc", "*.h"))) + [os.path.join(PKG, "csrc", "gen_consts.cpp"),
+                                                                        os.path.join(PKG, "model", "blobs", "stacking.json"), os.path.join(PKG, "model", "blobs", "avoiding.json"),
+                                                                        os.path.join(ROOT, "include", "d3il_rollout.h"), os.path.join(ROOT, "include", "d3il_model_blob.h")]
 # -disable-machine-licm / -disable-machine-sink: with the model constants baked in as literals, MachineLICM hoists
 # their materialisation (s_mov pairs) out of the sub-step loop and then spills ~350 SGPRs through VGPR lanes;
 # keeping them next to their use costs nothing (they are re-materialisable) and removes the spills.

@@ -29,8 +29,6 @@
 
 namespace d3il {
 
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
-
 constexpr unsigned ACT_TAG = 0x41430000u;      // fourth counter word = TAG | q (q < 8): never 0, never BET_TAG, never a DDPM_GPT_TAG or IBC_TAG word
 constexpr int ACT_C = 64, ACT_NH = 4, ACT_LAT = 32, ACT_OBSMAX = 32, ACT_TMAX = 8, ACT_AMAX = 8, ACT_MAXENC = 4, ACT_MAXDEC = 8;
 // packed layer arrays (policies.pack_act_weights), in floats: matrices [q k v proj fc1 fc2] / [q k v cq ck cv proj fc1 fc2], vectors [ln1 ln2 b.. b1 b2]
@@ -39,11 +37,6 @@ constexpr int ACT_ENC_W = 4 * 4096 + 2 * 16384, ACT_ENC_V = 704, ACT_DEC_W = 7 *
 constexpr int ACT_TAB_QE = 128, ACT_TAB_LNE = 640, ACT_TAB_LND = 704, ACT_TAB_HB = 768, ACT_TAB = 784;
 typedef float act_f4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ bool act_nonfinite(float x) {
-  unsigned b = __float_as_uint(x);
-  asm("" : "+v"(b));
-  return (b & 0x7F800000u) == 0x7F800000u;
-}
 __device__ __forceinline__ act_f4 act_ld4(const float* p) { return *(const act_f4*)p; }
 // output tile To of a packed layer with NT input tiles on one token's 16 rows (xin: LDS, B-operand order), added to init
 template <int NT>
@@ -166,9 +159,9 @@ __global__ __launch_bounds__(256) void k_act_chunk(ActArgs a) {
           for (int r = 0; r < 4; r++) {
             const int f = 16 * t + 4 * g + r;
             const float v = f < OBS ? a.state[n * OBS + f] : 0.f;
-            badl |= act_nonfinite(v) ? 1 : 0;
+            badl |= policy_nonfinite(v) ? 1 : 0;
             s[r] = v;
-            z[r] = a.latent_in ? a.latent_in[n * ACT_LAT + f] : (float)(rr[r] >> 8) * (1.0f / 16777216.0f);
+            z[r] = a.latent_in ? a.latent_in[n * ACT_LAT + f] : policy_uniform24(rr[r]);
             if (a.latent_out) a.latent_out[n * ACT_LAT + f] = z[r];
           }
         }
@@ -264,7 +257,7 @@ __global__ __launch_bounds__(256) void k_act_chunk(ActArgs a) {
         if (t < T) {
           oo[t] = act_lin<4>((const act_f4*)a.head_w, 0, hb + t * 256, act_ld4(a.tab + ACT_TAB_HB + 4 * g), lane);
 #pragma unroll
-          for (int r = 0; r < 4; r++) badh |= (4 * g + r < A && act_nonfinite(oo[t][r])) ? 1 : 0;
+          for (int r = 0; r < 4; r++) badh |= (4 * g + r < A && policy_nonfinite(oo[t][r])) ? 1 : 0;
         }
       }
       if (badh && due) sbad[j] = 1;

@@ -28,27 +28,14 @@
 
 namespace d3il {
 
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
-
 constexpr unsigned BET_TAG = 0x42655448u;      // fourth counter word of the head's Philox stream (k_policy_action uses 0: the streams never coincide)
 constexpr int BET_V = 64, BET_NW = 4, BET_CMAX = 128, BET_AMAX = 8;
 typedef float bet_f4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float bet_wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 __device__ __forceinline__ float bet_wave_max(float v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
   return v;
-}
-// exponent field all ones (NaN or +-Inf), on the bits
-__device__ __forceinline__ bool bet_nonfinite(float x) {
-  unsigned b = __float_as_uint(x);
-  asm("" : "+v"(b));
-  return (b & 0x7F800000u) == 0x7F800000u;
 }
 
 struct BetHeadArgs {
@@ -88,11 +75,11 @@ __global__ __launch_bounds__(64 * BET_NW) void k_bet_head(BetHeadArgs a) {
     const long rr = live ? row : a.rows - 1;
     // ---- 1. LayerNorm of the row
     const float h0 = lane < C ? a.h[rr * C + lane] : 0.f, h1 = 64 + lane < C ? a.h[rr * C + 64 + lane] : 0.f;
-    const float mean = bet_wave_sum(h0 + h1) * inv_c;
+    const float mean = policy_wave_sum(h0 + h1) * inv_c;
     const float d0 = lane < C ? h0 - mean : 0.f, d1 = 64 + lane < C ? h1 - mean : 0.f;
-    const float rstd = 1.0f / sqrtf(bet_wave_sum(d0 * d0 + d1 * d1) * inv_c + a.eps);
+    const float rstd = 1.0f / sqrtf(policy_wave_sum(d0 * d0 + d1 * d1) * inv_c + a.eps);
     const float x0 = d0 * rstd * lw0 + lb0, x1 = d1 * rstd * lw1 + lb1;
-    const bool bad = __ballot(bet_nonfinite(h0) || bet_nonfinite(h1) || bet_nonfinite(x0) || bet_nonfinite(x1)) != 0ull;
+    const bool bad = __ballot(policy_nonfinite(h0) || policy_nonfinite(h1) || policy_nonfinite(x0) || policy_nonfinite(x1)) != 0ull;
     if (lane < C) xrow[lane] = x0;      // (this wave's own slice: its reads of the previous pass were issued before these writes)
     if (64 + lane < C) xrow[64 + lane] = x1;
     __syncthreads();
@@ -120,7 +107,7 @@ __global__ __launch_bounds__(64 * BET_NW) void k_bet_head(BetHeadArgs a) {
       const unsigned long long ge = a.env_offset + (unsigned long long)rr;
       unsigned r[4];
       philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, BET_TAG, r);
-      u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+      u = policy_uniform24(r[0]);
     }
     const int cnt = __popcll(__ballot(c <= u * S));
     const int bin = cnt < BET_V - 1 ? cnt : BET_V - 1;

@@ -1,6 +1,6 @@
 // policy_cvae.h - the whole inference of the batched conditional-VAE policy (policies.CVAEPolicy; agents/cvae_agent.py:155-170 around
-// agents/models/vae/cvae.py:55-62 over common/mlp.py ResidualMLPNetwork) as ONE kernel.  Included by rollout.hip INSIDE namespace d3il, right after
-// k_resmlp_f32, whose operand scheme, rm_layer, dd_mish and dd_nonfinite it reuses (dg_box_muller: policy_ddpm_gpt.h).
+// agents/models/vae/cvae.py:55-62 over common/mlp.py ResidualMLPNetwork) as ONE kernel.  Included by rollout.hip behind policy_f32.h: it reuses
+// k_resmlp_f32's operand scheme with mlp_f4, rm_layer and dd_mish (the random stream and the bit test: policy_common.h).
 //
 // For environment n (s = the scaled state row, L = latent width, the decoder a Mish ResidualMLPNetwork on [s | z], f32 throughout):
 //   1. z_a = clamp(z_in[n, a] or Box-Muller on philox4x32_10(seed, (env_offset + n, step word, CVAE_TAG | q)), -0.5, 0.5), component a = 4 q + m takes word m.
@@ -17,13 +17,13 @@
 // different calls): 4096 Philox calls per workgroup instead of 128, for the price of one barrier; (b) the input layer is 64 columns wide, 16 matrix-core steps on two accumulators; (c) the tail
 // is fused: output bias, clamp, inverse scaling, bit tests; (d) the step word comes from device memory.
 //
-// LDS: xb 2 x NT x 64 float4 (16 / 32 KB), zs 16 x 36 words.  Vector stores only, no inline assembly beyond the empty register barrier of dd_nonfinite; every branch
+// LDS: xb 2 x NT x 64 float4 (16 / 32 KB), zs 16 x 36 words.  Vector stores only, no inline assembly beyond the empty register barrier of policy_nonfinite; every branch
 // in front of a barrier depends on the wave index or on kernel arguments only.  NaN / Inf: the device pass is built with -ffinite-math-only, so the state row, the
 // latent before its clamp and the outputs before theirs are tested on their bit patterns (exponent field all ones); a hit gives 0x7FC00000 in every action
 // component of that environment (and in the z_out components that were hit).  Rows never mix: column j of every matrix-core product is row j.
 #pragma once
 
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
+namespace d3il {
 
 constexpr unsigned CVAE_TAG = 0x43560000u;      // fourth counter word = TAG | q (q < 8): never 0, never BET_TAG, never a DDPM_GPT_TAG, IBC_TAG or ACT_TAG word
 constexpr int CVAE_LMAX = 32, CVAE_INMAX = 64, CVAE_AMAX = 16, CVAE_ZSTRIDE = 36;
@@ -72,11 +72,11 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
         const unsigned long long ge = a.env_offset + (unsigned long long)rz;
         unsigned r[4];
         philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), *a.t_dev, CVAE_TAG | (unsigned)q, r);
-        dg_box_muller(r[0], r[1], z[0], z[1]); dg_box_muller(r[2], r[3], z[2], z[3]);
+        policy_box_muller(r[0], r[1], z[0], z[1]); policy_box_muller(r[2], r[3], z[2], z[3]);
       }
 #pragma unroll
       for (int m = 0; m < 4; m++) {
-        const unsigned zb = dd_nonfinite(z[m]) ? 0x7FC00000u : __float_as_uint(fminf(fmaxf(z[m], -0.5f), 0.5f));
+        const unsigned zb = policy_nonfinite(z[m]) ? 0x7FC00000u : __float_as_uint(fminf(fmaxf(z[m], -0.5f), 0.5f));
         zs[jz * CVAE_ZSTRIDE + 4 * q + m] = zb;
         if (a.z_out && livez && 4 * q + m < L) ((unsigned*)a.z_out)[rowz * L + 4 * q + m] = zb;
       }
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
   }
   unsigned bad = 0u;      // this lane's quarter of the input row, tested here: in_k is dead after the input layer
 #pragma unroll
-  for (int s2 = 0; s2 < 16; s2++) bad |= dd_nonfinite(in_k[s2]);
+  for (int s2 = 0; s2 < 16; s2++) bad |= (unsigned)policy_nonfinite(in_k[s2]);
   const mlp_f4* w_in4 = (const mlp_f4*)a.w_in;
   const mlp_f4* w_out4 = (const mlp_f4*)a.w_out;
   mlp_f4 xo[TPW];
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     v[r] = acc[r] + a.b_out[4 * g + r];      // (b_out is padded to 16)
-    bad |= 4 * g + r < A ? dd_nonfinite(v[r]) : 0u;
+    bad |= 4 * g + r < A ? (unsigned)policy_nonfinite(v[r]) : 0u;
   }
   bad |= __shfl_xor(bad, 16);
   bad |= __shfl_xor(bad, 32);
@@ -161,3 +161,5 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
     }
   }
 }
+
+}  // namespace d3il

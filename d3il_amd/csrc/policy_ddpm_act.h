@@ -1,6 +1,6 @@
 // policy_ddpm_act.h - the whole reverse-diffusion chain and the per-lane chunk bookkeeping of the batched DDPM-ACT policy (policies.DDPMACTPolicy;
 // agents/ddpm_encdec_agent.py:222-257 around diffusion_policy.py:117-217 Diffusion.sample and diffusion_models.py:844-905 DiffusionEncDec.forward, no goals) as ONE
-// kernel (included by rollout.hip after policy_ddpm_gpt.h and policy_act.h, whose building blocks it uses).
+// kernel (included by rollout.hip after policy_act.h, whose building blocks it uses; the random stream and the bit test: policy_common.h).
 //
 // Per environment n (persistent device state: counter[n], chunk[n][Ta][A], the chunk already clamped and inverse-scaled; the window win[n][S][obs] left-aligned with
 // len[n] valid rows, policies._History.padded):
@@ -25,14 +25,14 @@
 // chain and layer loops are runtime loops.  Every branch in front of a barrier or shuffle depends on kernel arguments or the workgroup-wide vote only.
 //
 // Random numbers: Philox4x32-10, key = seed, counter = (lo32, hi32 of env_offset + n, step word, DDPM_ACT_TAG | k << 8 | t << 1 | q), k = T for the first iterate
-// and i for reverse step i (0 is never drawn), t the action token, component 4 q + m; Box-Muller as policy_ddpm_gpt.h.  The head output sits on wave 0, lane (g, j)
+// and i for reverse step i (0 is never drawn), t the action token, component 4 q + m; Box-Muller of policy_common.h.  The head output sits on wave 0, lane (g, j)
 // = components 4 g .. 4 g + 3 of environment j: that lane draws call q = g and does the x0 / posterior arithmetic.
 //
 // No atomics, no workspace, vector stores only, no inline assembly beyond the empty register barrier of the bit test.  NaN / Inf (-ffinite-math-only: bit tests): a
 // due environment with one in a valid window row, a head output or an iterate gets 0x7FC00000 in its whole chunk and emitted action and bad[n] = 1; padding rows
 // and the window of an environment that is not due are not read; no other environment changes.
 #pragma once
-#include "policy_ddpm_gpt.h"
+#include "policy_common.h"
 #include "policy_act.h"
 
 namespace d3il {
@@ -65,8 +65,8 @@ __device__ __forceinline__ act_f4 da_noise(const DdpmActArgs& a, long n, unsigne
     unsigned rr[4];
     philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t_word, DDPM_ACT_TAG | ((unsigned)k << 8) | ((unsigned)t << 1) | (unsigned)g, rr);
     float n0, n1, n2, n3;
-    dg_box_muller(rr[0], rr[1], n0, n1);
-    dg_box_muller(rr[2], rr[3], n2, n3);
+    policy_box_muller(rr[0], rr[1], n0, n1);
+    policy_box_muller(rr[2], rr[3], n2, n3);
     z = act_f4{n0, n1, n2, n3};
 #pragma unroll
     for (int r = 0; r < 4; r++)
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_ddpm_act_chunk(DdpmActArgs a) {
               for (int r = 0; r < 4; r++) {
                 const int f = 16 * t + 4 * g + r;
                 const float x = f < OBS ? a.win[(n * S + s) * OBS + f] : 0.f;
-                badl |= act_nonfinite(x) ? 1 : 0;
+                badl |= policy_nonfinite(x) ? 1 : 0;
                 v[r] = x;
               }
             }
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_ddpm_act_chunk(DdpmActArgs a) {
           xx[t] = da_noise(a, n, ge, t_word, T, t, g);
         }
 #pragma unroll
-        for (int r = 0; r < 4; r++) badl |= act_nonfinite(xx[t][r]) ? 1 : 0;
+        for (int r = 0; r < 4; r++) badl |= policy_nonfinite(xx[t][r]) ? 1 : 0;
       }
     }
     // ---- 3. the chain
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_ddpm_act_chunk(DdpmActArgs a) {
                 const float pn = s4 * nz[r];
                 const float xn = i > 0 ? mean + pn : mean;
                 const bool in = 4 * g + r < A;
-                badl |= (in && (act_nonfinite(eps[r]) || act_nonfinite(xn))) ? 1 : 0;
+                badl |= (in && (policy_nonfinite(eps[r]) || policy_nonfinite(xn))) ? 1 : 0;
                 xx[t][r] = in ? xn : 0.f;
               }
             }

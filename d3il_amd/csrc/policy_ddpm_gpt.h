@@ -27,30 +27,9 @@
 
 namespace d3il {
 
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
-
 constexpr unsigned DDPM_GPT_TAG = 0x44470000u;      // fourth counter word = TAG | k << 8 | j << 1 | q: never 0 (k_policy_action) and never BET_TAG
 constexpr int DG_NW = 4, DG_CMAX = 128, DG_AMAX = 8, DG_WMAX = 16, DG_TMAX = 255;
 
-__device__ __forceinline__ float dg_wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-// exponent field all ones (NaN or +-Inf), on the bits
-__device__ __forceinline__ bool dg_nonfinite(float x) {
-  unsigned b = __float_as_uint(x);
-  asm("" : "+v"(b));
-  return (b & 0x7F800000u) == 0x7F800000u;
-}
-// two standard normals from two Philox words: u1 in (0, 1], u2 in [0, 1), the precise library functions
-__device__ __forceinline__ void dg_box_muller(unsigned ra, unsigned rb, float& n0, float& n1) {
-  const float u1 = (float)((ra >> 8) + 1u) * (1.0f / 16777216.0f), u2 = (float)(rb >> 8) * (1.0f / 16777216.0f);
-  const float rad = sqrtf(-2.0f * logf(u1));
-  float s, c;
-  sincosf(6.28318530717958647692f * u2, &s, &c);
-  n0 = rad * c; n1 = rad * s;
-}
 
 struct DdpmGptArgs {
   const float* hk; const float* ln_w; const float* ln_b; const float* w_pred; const float* b_pred; const float* w_aemb; const float* bias_pos; const float* temb;
@@ -117,10 +96,10 @@ __global__ __launch_bounds__(64 * DG_NW) void k_ddpm_gpt_step(DdpmGptArgs a) {
         const unsigned tag = DDPM_GPT_TAG | ((unsigned)k << 8) | ((unsigned)j << 1);
         unsigned r[4];
         philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, tag, r);
-        dg_box_muller(r[0], r[1], nz[0], nz[1]); dg_box_muller(r[2], r[3], nz[2], nz[3]);
+        policy_box_muller(r[0], r[1], nz[0], nz[1]); policy_box_muller(r[2], r[3], nz[2], nz[3]);
         if (A > 4) {
           philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, tag | 1u, r);
-          dg_box_muller(r[0], r[1], nz[4], nz[5]); dg_box_muller(r[2], r[3], nz[6], nz[7]);
+          policy_box_muller(r[0], r[1], nz[4], nz[5]); policy_box_muller(r[2], r[3], nz[6], nz[7]);
         } else {
           nz[4] = nz[5] = nz[6] = nz[7] = 0.f;
         }
@@ -135,25 +114,25 @@ __global__ __launch_bounds__(64 * DG_NW) void k_ddpm_gpt_step(DdpmGptArgs a) {
       } else {
         // ---- 1. LayerNorm of the hidden row
         const float h0 = c0 ? a.hk[row * C + lane] : 0.f, h1 = c1 ? a.hk[row * C + 64 + lane] : 0.f;
-        const float mean = dg_wave_sum(h0 + h1) * inv_c;
+        const float mean = policy_wave_sum(h0 + h1) * inv_c;
         const float d0 = c0 ? h0 - mean : 0.f, d1 = c1 ? h1 - mean : 0.f;
-        const float rstd = 1.0f / sqrtf(dg_wave_sum(d0 * d0 + d1 * d1) * inv_c + a.eps);
+        const float rstd = 1.0f / sqrtf(policy_wave_sum(d0 * d0 + d1 * d1) * inv_c + a.eps);
         const float z0 = d0 * rstd * lw0 + lb0, z1 = d1 * rstd * lw1 + lb1;
-        hit = __ballot(dg_nonfinite(h0) || dg_nonfinite(h1) || dg_nonfinite(z0) || dg_nonfinite(z1)) != 0ull;
+        hit = __ballot(policy_nonfinite(h0) || policy_nonfinite(h1) || policy_nonfinite(z0) || policy_nonfinite(z1)) != 0ull;
         // ---- 2. the head, 3. clipped x0, 4. posterior mean, 6. the next iterate
 #pragma unroll
         for (int q = 0; q < DG_AMAX; q++) {
-          const float e = dg_wave_sum(fmaf(wp1[q], z1, wp0[q] * z0)) + bp[q];
+          const float e = policy_wave_sum(fmaf(wp1[q], z1, wp0[q] * z0)) + bp[q];
           const float xq = q < A ? a.x[row * A + q] : 0.f;
           const float x0 = fminf(fmaxf(s0 * xq - s1 * e, lo[q]), hi[q]);
           const float m = s2 * x0 + s3 * xq;
           xp[q] = k == 0 ? m : m + s4 * nz[q];
-          hit = hit || dg_nonfinite(xq);
+          hit = hit || policy_nonfinite(xq);
         }
       }
 #pragma unroll
       for (int q = 0; q < DG_AMAX; q++) {
-        hit = hit || (q < A && dg_nonfinite(xp[q]));
+        hit = hit || (q < A && policy_nonfinite(xp[q]));
         unsigned b = __float_as_uint(xp[q]);
         b = valid ? b : 0u;      // padded positions: x' = 0, the token is bias_pos[j]
         xp[q] = __uint_as_float(b);

@@ -12,7 +12,7 @@
 // f64 reference in tests/test_policies_f16x3.py).  Range: |operand| <= 65504 (saturating) - LayerNorm outputs, GELU outputs and weights are O(1).
 // The saturation is silent in the default instantiations (GUARD = false), and it is expected to swallow a NaN / Inf operand too (the clamp returns its bound; not asserted by a test).  The
 // GUARD = true instantiations (d3il_f16x3_set_guard; "range / NaN guard" below) count the rows it touched and let a non-finite operand through as NaN.
-// The kernels keep the structure of k_mlp_gelu_residual_f32 / k_linear120_f32 (rollout.hip): one wave owns 16 token rows, the transposed product D[feature][row]
+// The kernels keep the structure of k_mlp_gelu_residual_f32 / k_linear120_f32 (policy_f32.h): one wave owns 16 token rows, the transposed product D[feature][row]
 // makes the D registers of the first MLP product the B operand of the second, four waves share the weight stream through a double-buffered LDS stage.
 #pragma once
 

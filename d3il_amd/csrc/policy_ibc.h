@@ -31,8 +31,6 @@
 
 namespace d3il {
 
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
-
 constexpr unsigned IBC_TAG = 0x49420000u;      // fourth counter word = TAG | kind << 14 | k << 8 | s << 2 | q: never 0, never BET_TAG, never a DDPM_GPT_TAG word
 constexpr int IBC_S = 64, IBC_AMAX = 8, IBC_KMAX = 63, IBC_MAXB = 4, IBC_NW = 8;
 typedef float ibc_f4 __attribute__((ext_vector_type(4)));
@@ -56,11 +54,6 @@ __device__ __forceinline__ float ibc_start(float lo, float hi, float u) {
   const float span = hi - lo;
   const float prod = u * span;
   return lo + prod;
-}
-__device__ __forceinline__ bool ibc_nonfinite(float x) {
-  unsigned b = __float_as_uint(x);
-  asm("" : "+v"(b));
-  return (b & 0x7F800000u) == 0x7F800000u;
 }
 // y[q] = (RES ? y[q] : 0) + (bias) + W m for the wave's output tiles TPW w + q of one packed HID x HID layer (xin: the 16 rows in LDS, B-operand order).
 // Feature step t outside, the wave's tiles inside: one activation fragment is live at a time and the weight fragments stream through (few registers next to
@@ -145,7 +138,7 @@ __global__ __launch_bounds__(64 * IBC_NW) void k_ibc_langevin(IbcArgs a) {
   for (int s2 = 0; s2 < 7; s2++) {
     const int f = 4 * s2 + g;
     st_k[s2] = f < OBS ? a.state[n * OBS + f] : 0.f;
-    bad |= ibc_nonfinite(st_k[s2]) ? 1 : 0;
+    bad |= policy_nonfinite(st_k[s2]) ? 1 : 0;
   }
   // Wave 0 keeps the samples: lane (g, j) owns components g and 4 + g of row j (start point, noise, update); the other waves read them from LDS.
   const int qa = g, qb = 4 + g;
@@ -170,10 +163,10 @@ __global__ __launch_bounds__(64 * IBC_NW) void k_ibc_langevin(IbcArgs a) {
         unsigned ra = r[0], rb = r2[0];
 #pragma unroll
         for (int m = 1; m < 4; m++) { ra = g == m ? r[m] : ra; rb = g == m ? r2[m] : rb; }
-        xa = ina ? ibc_start(lo_a, hi_a, (float)(ra >> 8) * (1.0f / 16777216.0f)) : 0.f;
-        xc = inb ? ibc_start(lo_b, hi_b, (float)(rb >> 8) * (1.0f / 16777216.0f)) : 0.f;
+        xa = ina ? ibc_start(lo_a, hi_a, policy_uniform24(ra)) : 0.f;
+        xc = inb ? ibc_start(lo_b, hi_b, policy_uniform24(rb)) : 0.f;
       }
-      bad |= (ibc_nonfinite(xa) || ibc_nonfinite(xc)) ? 1 : 0;
+      bad |= (policy_nonfinite(xa) || policy_nonfinite(xc)) ? 1 : 0;
       sx[s * IBC_AMAX + qa] = (double)xa; sx[s * IBC_AMAX + qb] = (double)xc;
       if (a.x0_out) {
         if (ina) a.x0_out[row * A + qa] = xa;
@@ -267,7 +260,7 @@ __global__ __launch_bounds__(64 * IBC_NW) void k_ibc_langevin(IbcArgs a) {
         if (last) {
           const float e = acc[0] + a.b_out[0];      // (lanes (0, j))
           if (g == 0) {
-            bad |= ibc_nonfinite(e) ? 1 : 0;
+            bad |= policy_nonfinite(e) ? 1 : 0;
             se[s] = e;
             if (a.energies) a.energies[row] = e;
           }
@@ -294,10 +287,10 @@ __global__ __launch_bounds__(64 * IBC_NW) void k_ibc_langevin(IbcArgs a) {
             unsigned r[4];
             float nz[8];
             philox4x32_10(k0, k1, c0, c1, t_word, tag, r);
-            dg_box_muller(r[0], r[1], nz[0], nz[1]); dg_box_muller(r[2], r[3], nz[2], nz[3]);
+            policy_box_muller(r[0], r[1], nz[0], nz[1]); policy_box_muller(r[2], r[3], nz[2], nz[3]);
             if (A > 4) {
               philox4x32_10(k0, k1, c0, c1, t_word, tag | 1u, r);
-              dg_box_muller(r[0], r[1], nz[4], nz[5]); dg_box_muller(r[2], r[3], nz[6], nz[7]);
+              policy_box_muller(r[0], r[1], nz[4], nz[5]); policy_box_muller(r[2], r[3], nz[6], nz[7]);
             } else {
               nz[4] = nz[5] = nz[6] = nz[7] = 0.f;
             }
@@ -316,8 +309,8 @@ __global__ __launch_bounds__(64 * IBC_NW) void k_ibc_langevin(IbcArgs a) {
           const double raw_a = hs * (double)ga + st * ((double)za * ns), raw_b = hs * (double)gb + st * ((double)zb * ns);
           const double xn_a = fmin(fmax(sx[s * IBC_AMAX + qa] - fmin(fmax(raw_a, -(double)cl_a), (double)cl_a), (double)lo_a), (double)hi_a);
           const double xn_b = fmin(fmax(sx[s * IBC_AMAX + qb] - fmin(fmax(raw_b, -(double)cl_b), (double)cl_b), (double)lo_b), (double)hi_b);
-          bad |= (ina && (ibc_nonfinite(ga) || ibc_nonfinite((float)raw_a) || ibc_nonfinite((float)xn_a))) ? 1 : 0;
-          bad |= (inb && (ibc_nonfinite(gb) || ibc_nonfinite((float)raw_b) || ibc_nonfinite((float)xn_b))) ? 1 : 0;
+          bad |= (ina && (policy_nonfinite(ga) || policy_nonfinite((float)raw_a) || policy_nonfinite((float)xn_a))) ? 1 : 0;
+          bad |= (inb && (policy_nonfinite(gb) || policy_nonfinite((float)raw_b) || policy_nonfinite((float)xn_b))) ? 1 : 0;
           if (ina) sx[s * IBC_AMAX + qa] = xn_a;
           if (inb) sx[s * IBC_AMAX + qb] = xn_b;
         }
@@ -342,7 +335,7 @@ __global__ __launch_bounds__(64 * IBC_NW) void k_ibc_langevin(IbcArgs a) {
   else {
     unsigned r[4];
     philox4x32_10(k0, k1, c0, c1, t_word, IBC_TAG | (2u << 14), r);
-    u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+    u = policy_uniform24(r[0]);
   }
   const int cnt = __popcll(__ballot(c <= u * S));
   const int pick = cnt < IBC_S - 1 ? cnt : IBC_S - 1;

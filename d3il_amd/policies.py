@@ -19,9 +19,12 @@ batch == the reference's batch-1 ``predict`` of environment i).
 """
 from __future__ import annotations
 
+import copy
 import math
 import os
+import warnings
 
+import numpy as np
 import torch
 from torch import nn
 from torch.nn import functional as F
@@ -302,6 +305,16 @@ def weights_out_of_range(w: torch.Tensor) -> torch.Tensor:
     return (~torch.isfinite(w) | (w.abs() > 65504.0)).sum()
 
 
+_capturing = torch.cuda.is_current_stream_capturing      # is the current stream being captured into a HIP graph?  For code that already runs on the device.
+
+
+def swap_in_ema(module: nn.Module, shadow_params):
+    """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``module.parameters()`` order."""
+    with torch.no_grad():
+        for p, sh in zip(module.parameters(), shadow_params):
+            p.copy_(torch.as_tensor(sh, dtype=p.dtype, device=p.device))
+
+
 class PackedWeights:
     """Packed device copies of a module's weights that follow its parameters: ``buf`` is a dict of PERSISTENT buffers, refreshed in place whenever a parameter has
     changed (tensor version counters: no device synchronisation).  The addresses never change while names, shapes, dtypes and devices stay, so a captured HIP graph
@@ -338,7 +351,7 @@ class PackedWeights:
 
     def current(self, params, pack):
         """The buffers for a launch: refreshed here, except inside a graph capture, where packing kernels must not be recorded - they have to be packed already."""
-        if torch.cuda.is_current_stream_capturing():
+        if _capturing():
             assert self.key is not None, "a captured graph replays the packed weight buffers: call ensure_packed() before capturing"
         else:
             self.ensure(params, pack)
@@ -411,7 +424,7 @@ def guard_epoch() -> int:
 def _env_range_guard(device):
     """D3IL_POLICY_RANGE_GUARD=1: create and enable a guard at the first f16x3 call of the process (outside a graph capture)."""
     global _ENV_GUARD_TRIED
-    if _ENV_GUARD_TRIED or torch.cuda.is_current_stream_capturing():
+    if _ENV_GUARD_TRIED or _capturing():
         return
     _ENV_GUARD_TRIED = True
     if os.environ.get("D3IL_POLICY_RANGE_GUARD", "0") == "1" and _RANGE_GUARD is None:
@@ -623,6 +636,19 @@ class _History:
         self.len.masked_fill_(mask.to(self.len.device).bool().reshape(-1), 0)
         self.lockstep = -1
 
+    def snapshot(self):
+        return self.buf.clone(), self.len.clone(), self.lockstep
+
+    def restore(self, snap):
+        """Put a snapshot back INTO the buffers (a captured graph holds their addresses)."""
+        buf, ln, self.lockstep = snap
+        self.buf.copy_(buf); self.len.copy_(ln)
+
+    def copy(self):
+        c = copy.copy(self)
+        c.buf, c.len = self.buf.clone(), self.len.clone()
+        return c
+
     def padded(self):
         """Lanes with different history lengths in ONE batch: (window [N, W, dim], lengths [N]) with every lane's entries left-aligned, oldest first, and zeros on
         the right up to the window size.  A causal network whose position embedding counts from the first token never lets a lane's tokens see the padding behind
@@ -694,7 +720,7 @@ def pack_resmlp_weights(lin_in, blocks, lin_out, in_cols: int = 32) -> dict:
 
 
 class FusedResMLP:
-    """The device path of a ResidualMLPNetwork (csrc/rollout.hip k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
+    """The device path of a ResidualMLPNetwork (csrc/policy_f32.h k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
     ``parts`` = (lin_in, [(l1, l2), ..], lin_out) of the module it serves (no reference to the module is kept).  Non-finite input: a row of x with a NaN / Inf comes
     out NaN in every column, as from torch's layers, and no other row changes (tests/test_gpu_policy_f32_edges.py)."""
 
@@ -808,7 +834,6 @@ class CapturedPolicy:
 
 
 def cosine_beta_schedule(timesteps, s=0.008):     # agents/models/diffusion/utils.py:31-42 (float64 numpy -> float32)
-    import numpy as np
     steps = timesteps + 1
     x = np.linspace(0, steps, steps)
     ac = np.cos(((x / steps) + s) / (1 + s) * np.pi * 0.5) ** 2
@@ -851,7 +876,7 @@ class DDPMPolicy:
         self.n_envs = n_envs
         self._packed = PackedWeights()
 
-    # ---- the whole chain in one kernel of the rollout library (csrc/rollout.hip k_ddpm_mlp_f32)
+    # ---- the whole chain in one kernel of the rollout library (csrc/policy_f32.h k_ddpm_mlp_f32)
     def fused_ok(self):
         m = self.model
         L = m.layers.layers
@@ -898,7 +923,6 @@ class DDPMPolicy:
     def fork(self):
         """A clone for another sub-batch (envs/sub_batch.fork_agent): network, scaler and schedule shared, observation history and the packed buffers of the
         fused chain its own (packed again at its first call)."""
-        import copy
         c = copy.copy(self)
         c.hist = copy.deepcopy(self.hist)
         c._packed = PackedWeights()
@@ -915,10 +939,7 @@ class DDPMPolicy:
         self.model.load_state_dict({k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")})
 
     def use_ema(self, shadow_params):
-        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order."""
-        with torch.no_grad():
-            for p, s in zip(self.model.parameters(), shadow_params):
-                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
+        swap_in_ema(self.model, shadow_params)
 
     def reset(self):
         if self.hist is not None:
@@ -989,9 +1010,7 @@ class BESOPolicy:
         self.inner.load_state_dict({k[len("inner_model."):]: v for k, v in sd.items() if k.startswith("inner_model.") and k[len("inner_model."):] in own})
 
     def use_ema(self, shadow_params):
-        with torch.no_grad():
-            for p, s in zip(self.inner.parameters(), shadow_params):
-                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
+        swap_in_ema(self.inner, shadow_params)
 
     f16x3_blocks = True      # the DiffusionGPT blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)
 
@@ -1117,13 +1136,9 @@ class BESOPolicy:
         return self.scaler.inverse_scale_output(x0_all)
 
 
-# ------------------------------------------------------------------------------------------------ Behaviour Transformer
-BET_TAG = 0x42655448          # fourth Philox counter word of the sampling head (csrc/policy_bet.h BET_TAG; the random-policy harness uses 0)
-
-
+# ------------------------------------------------------------------------------------------------ the Philox stream of the native policies, on the host
 def philox4x32_10(k0, k1, c0, c1, c2, c3):
-    """Philox4x32-10 on numpy arrays / ints (broadcast): the four output words as uint32 arrays - the host form of csrc/rollout.hip philox4x32_10."""
-    import numpy as np
+    """Philox4x32-10 on numpy arrays / ints (broadcast): the four output words as uint32 arrays - the host form of csrc/policy_common.h philox4x32_10."""
     m32 = np.uint64(0xFFFFFFFF)
     u = lambda v: np.asarray(v, dtype=np.uint64) & m32
     k0, k1, c0, c1, c2, c3 = np.broadcast_arrays(u(k0), u(k1), u(c0), u(c1), u(c2), u(c3))
@@ -1136,13 +1151,129 @@ def philox4x32_10(k0, k1, c0, c1, c2, c3):
     return tuple(x.astype(np.uint32) for x in (c0, c1, c2, c3))
 
 
+def philox_words(seed: int, env_offset: int, n: int, t: int, tag):
+    """THE stream of every native policy: uint32 [n, ..., 4] = Philox4x32-10(key = (lo32, hi32 of seed), counter = (lo32, hi32 of env_offset + row, t, tag)) for rows
+    0 .. n-1.  ``tag`` - the policy's *_TAG or-ed with its layout bits - is a uint64 scalar or an array [1, ...] that broadcasts against the row axis."""
+    tag = np.asarray(tag, dtype=np.uint64)
+    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape((n,) + (1,) * (tag.ndim - 1))
+    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+
+
+def uniform24(r):
+    """The upper 24 bits of Philox words as float32 uniforms in [0, 1 - 2^-24] (csrc/policy_common.h policy_uniform24)."""
+    return ((r >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+
+
+def box_muller_f64(r):
+    """Standard normals from Philox words [..., 4], float64 [..., 4]: exact on the words and f64 from there on (csrc/policy_common.h policy_box_muller in f32):
+    u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24, (n0, n1) = sqrt(-2 ln u1) (cos, sin)(2 pi u2); (n2, n3) likewise from r2, r3."""
+    out = np.zeros(r.shape)
+    for p in range(2):
+        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+        rad = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
+    return out
+
+
+def _tag_axes(*sizes):
+    """uint64 index arrays [1, s0, 1, ..], [1, 1, s1, ..], .. for the layout bits of a tag: one axis per size behind the row axis."""
+    return [np.arange(s, dtype=np.uint64).reshape((1,) * (i + 1) + (s,) + (1,) * (len(sizes) - 1 - i)) for i, s in enumerate(sizes)]
+
+
+class NativePolicy:
+    """What the Sims, SubBatchSet and CapturedPolicy call on a policy that draws from the Philox stream above, written once.  A subclass has ``model`` (the
+    network), ``device``, calls ``_init_stream(seed)`` in its constructor and states
+      SWITCH   the D3IL_POLICY_* variable that turns its kernel off ("0": the torch path, which the tests compare the kernel against);
+      STATE    the names of its per-lane device tensors (None until ``_state(n)`` has sized them);  ``hist``, a _History or None, is per-lane state too;
+      LAST     the names of the ``last_*`` records a fork starts without;
+      _state(n)                 make the per-lane state fit n lanes (default: there is none);
+      _pack_params() / _pack()  the parameters its packed tables follow and the packer, for PackedWeights; _kernel_shape() where only some networks are packed.
+    The step word ``_t`` lives on the device (the kernels read it as u32); a captured graph advances it at every replay."""
+
+    SWITCH, STATE, LAST = None, (), ()
+    hist = None
+
+    def _init_stream(self, seed):
+        self.seed, self.env_offset = int(seed), 0
+        self._t = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._packed = PackedWeights()
+
+    def _state(self, n):
+        pass
+
+    def _kernel_shape(self) -> bool:
+        return True
+
+    def _switch_on(self) -> bool:
+        return os.environ.get(self.SWITCH, "1") == "1"
+
+    def set_rollout_range(self, offset, count):
+        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
+        self.env_offset = int(offset)
+        self._state(int(count))
+
+    def fork(self):
+        """A clone for another sub-batch: network, scaler and tables shared; per-lane state, step word and packed buffers its own."""
+        c = copy.copy(self)
+        c._t, c._packed = self._t.clone(), PackedWeights()
+        for k in self.STATE:
+            setattr(c, k, None if getattr(self, k) is None else getattr(self, k).clone())
+        c.hist = None if self.hist is None else self.hist.copy()
+        for k in self.LAST:
+            setattr(c, k, None)
+        return c
+
+    def captured(self):
+        """This policy as one captured HIP graph per batch shape (the kernel path is a fixed chain that ends with the add on the step word)."""
+        return CapturedPolicy(self)
+
+    def use_ema(self, shadow_params):
+        swap_in_ema(self.model, shadow_params)
+
+    def invalidate_packed(self):
+        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
+        self._packed.invalidate()
+
+    def ensure_packed(self):
+        if next(self.model.parameters()).is_cuda and self._kernel_shape():
+            self._packed.ensure(self._pack_params(), self._pack)
+
+    # ---- CapturedPolicy's hooks
+    def capture_snapshot(self, obs):
+        """Before the warm-up calls of a capture: the per-lane state and the step word, which capture_restore puts back - warm-up and capture do not count as steps."""
+        self._state(int(obs.shape[0]))
+        return [getattr(self, k).clone() for k in ("_t",) + self.STATE], None if self.hist is None else self.hist.snapshot()
+
+    def capture_restore(self, snap):
+        tensors, hist = snap
+        for k, src in zip(("_t",) + self.STATE, tensors):
+            getattr(self, k).copy_(src)
+        if hist is not None:
+            self.hist.restore(hist)
+
+    # ---- the torch paths
+    def _host_step_word(self) -> int:
+        """The step word for a draw on the host (a device synchronisation) - which a graph capture cannot record."""
+        if torch.cuda.is_initialized() and _capturing():
+            raise RuntimeError("%s: the torch path draws its Philox numbers on the host and cannot be captured; the kernel draws on the device" % type(self).__name__)
+        return int(self._t.item()) & 0xFFFFFFFF
+
+    def _warn_fallback(self, s, text):
+        """Once per policy (forks copy the flag): the kernel is switched on, the input is on the device, and this network is not one it is built for."""
+        if s.is_cuda and self._switch_on() and not getattr(self, "_warned", False):
+            self._warned = True
+            warnings.warn("%s: %s" % (type(self).__name__, text()))
+
+
+# ------------------------------------------------------------------------------------------------ Behaviour Transformer
+BET_TAG = 0x42655448          # fourth Philox counter word of the sampling head (csrc/policy_bet.h BET_TAG; the random-policy harness uses 0)
+
+
 def bet_uniforms(seed: int, env_offset: int, n: int, t: int):
     """The head kernel's uniforms of rows 0 .. n-1 at step word t, on the host: 24 bits of Philox4x32-10(key = seed, counter = (env_offset + row, t, BET_TAG)),
     float32 in [0, 1 - 2^-24]."""
-    import numpy as np
-    ge = np.uint64(env_offset) + np.arange(n, dtype=np.uint64)
-    r0 = philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, BET_TAG)[0]
-    return ((r0 >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+    return uniform24(philox_words(seed, env_offset, n, t, BET_TAG)[:, 0])
 
 
 class MinGPTTrunk(nn.Module):
@@ -1175,7 +1306,7 @@ class MinGPTTrunk(nn.Module):
         return self.head(self.ln_f(self.hidden(x)))
 
 
-class BeTPolicy:
+class BeTPolicy(NativePolicy):
     """BeT_Agent.predict (agents/bet_agent.py:328-384) on a batch: scaled observation window (deque maxlen W; the window GROWS at episode start - sequence length
     1, 2, .. W with pos_emb[:L]), the minGPT trunk, and at every lane's last token the sampling tail - ln_f, the bias-free head of V (1 + A) outputs, softmax over the
     first V, ONE categorical draw, the offsets of the drawn bin in the layout "(V A)" (latent_generators/mingpt.py:155-186), bin_centers[bin] + offset (k_means.py:111-138),
@@ -1203,8 +1334,8 @@ class BeTPolicy:
         assert trunk.head.weight.shape[0] == self.V * (1 + self.A), "the head has V (1 + A) outputs"
         self.min_action, self.max_action = f(min_action), f(max_action)
         self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
-        self.seed, self.env_offset, self.uniform_fn = int(seed), 0, uniform_fn
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self._init_stream(seed)
+        self.uniform_fn = uniform_fn
         self.hist = None
         self._static = False          # fixed-shape chain with device-only state (set by capture_snapshot)
         self.record = False           # also keep the head's probabilities (last_probs) / the torch tail's logits (last_logits)
@@ -1241,11 +1372,19 @@ class BeTPolicy:
         except AttributeError:
             return False
 
-    # ---- the policy protocol of the Sims and SubBatchSet
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
+    SWITCH, LAST = "D3IL_POLICY_BET_HEAD", ("last_bins", "last_u", "last_probs", "last_logits")
+    model = property(lambda self: self.trunk)
+
     @property
     def f16x3_blocks(self) -> bool:
         """The trunk runs the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
         return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.trunk.blocks)
+
+    def _state(self, n):
+        """The observation window for n lanes; a new size starts empty."""
+        if self.hist is None or self.hist.buf.shape[0] != n:
+            self.hist = _History(n, self.W, self.trunk.tok_emb.in_features, self.device)
 
     def reset(self):
         if self.hist is not None:
@@ -1255,22 +1394,18 @@ class BeTPolicy:
         if self.hist is not None:
             self.hist.reset_(mask)
 
-    def set_rollout_range(self, offset, count):
-        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
-        self.env_offset = int(offset)
-        if self.hist is not None and self.hist.buf.shape[0] != count:
-            self.hist = None
-
     def fork(self):
-        """A clone for another sub-batch: trunk, head, centres and scaler shared; history, step word and capture mode its own."""
-        import copy
-        c = copy.copy(self)
+        """A clone for another sub-batch: trunk, head, centres and scaler shared; step word its own, an empty history, not in capture mode."""
+        c = super().fork()
         c.hist, c._static = None, False
-        c._t = self._t.clone()
-        c.last_bins = c.last_u = c.last_probs = c.last_logits = None
         return c
 
+    def invalidate_packed(self):
+        for blk in self.trunk.blocks:
+            blk.invalidate_packed()
+
     def ensure_packed(self):
+        """The packed weights are the blocks' own."""
         ensure_blocks_packed(self.trunk.blocks)
 
     def load_reference_state_dict(self, sd):
@@ -1279,30 +1414,20 @@ class BeTPolicy:
 
     # ---- CapturedPolicy's hooks
     def capture_snapshot(self, obs):
-        """Before the warm-up calls of a capture: switch to the fixed-shape chain (right-padded windows, lengths on the device, in-place history) and return the
-        per-episode state, which capture_restore puts back - warm-up and capture do not count as steps."""
+        """Also switches to the fixed-shape chain (right-padded windows, lengths on the device, in-place history)."""
         self._static = True
-        if self.hist is None or self.hist.buf.shape[0] != obs.shape[0]:
-            self.hist = _History(obs.shape[0], self.W, obs.shape[1], self.device)
-        return (self.hist.buf.clone(), self.hist.len.clone(), self.hist.lockstep, self._t.clone())
-
-    def capture_restore(self, snap):
-        buf, ln, lock, t = snap
-        self.hist.buf.copy_(buf); self.hist.len.copy_(ln); self._t.copy_(t)
-        self.hist.lockstep = lock
+        return super().capture_snapshot(obs)
 
     # ---- the sampling tail
     def head_kernel_ok(self, h) -> bool:
         C = h.shape[-1]
         return (h.is_cuda and h.dtype == torch.float32 and self.V == 64 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 8 and self.trunk.head.weight.dtype == torch.float32
-                and os.environ.get("D3IL_POLICY_BET_HEAD", "1") == "1")
+                and self._switch_on())
 
     def _uniforms(self, n, dev):
         if self.uniform_fn is not None:
             return torch.as_tensor(self.uniform_fn(n), dtype=torch.float32).to(dev).reshape(n).contiguous()
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("BeTPolicy: the torch tail draws its Philox numbers on the host and cannot be captured; the head kernel draws on the device")
-        return torch.as_tensor(bet_uniforms(self.seed, self.env_offset, n, int(self._t.item()) & 0xFFFFFFFF)).to(dev)
+        return torch.as_tensor(bet_uniforms(self.seed, self.env_offset, n, self._host_step_word())).to(dev)
 
     def _tail_torch(self, h):
         """Steps 1 - 7 of csrc/policy_bet.h as torch ops, in the kernel's order of operations where the order is defined (S is the last prefix sum)."""
@@ -1366,10 +1491,9 @@ class BeTPolicy:
         s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32))
         if s.is_cuda and not _ENV_GUARD_TRIED and self.f16x3_blocks:
             _env_range_guard(s.device)
-        if s.is_cuda and not torch.cuda.is_current_stream_capturing():
+        if s.is_cuda and not _capturing():
             self.ensure_packed()
-        if self.hist is None or self.hist.buf.shape[0] != s.shape[0]:
-            self.hist = _History(s.shape[0], self.W, s.shape[1], self.device)
+        self._state(s.shape[0])
         self.hist.append_(s)
         return self.tail(self._last_hidden().contiguous())
 
@@ -1400,29 +1524,16 @@ DDPM_GPT_TAG = 0x44470000     # fourth Philox counter word of the step kernel, o
 def ddpm_gpt_words(seed: int, env_offset: int, n: int, t: int, k: int, W: int):
     """The Philox words behind ``ddpm_gpt_normals``: uint32 [n, W, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
     DDPM_GPT_TAG | k << 8 | j << 1 | q))."""
-    import numpy as np
     assert 1 <= k <= 255 and 1 <= W <= 16, "the counter layout holds k <= 255 and j <= 15; chain index 0 is never drawn"
-    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1, 1)
-    j = np.arange(W, dtype=np.uint64).reshape(1, W, 1)
-    q = np.arange(2, dtype=np.uint64).reshape(1, 1, 2)
-    tag = np.uint64(DDPM_GPT_TAG | (k << 8)) | (j << np.uint64(1)) | q
-    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+    j, q = _tag_axes(W, 2)
+    return philox_words(seed, env_offset, n, t, np.uint64(DDPM_GPT_TAG | (k << 8)) | (j << np.uint64(1)) | q)
 
 
 def ddpm_gpt_normals(seed: int, env_offset: int, n: int, t: int, k: int, W: int, A: int):
     """The step kernel's normals of environments 0 .. n-1 at step word t and chain index k, on the host: float64 [n, W, A].  Exact on the 32-bit words
-    (``ddpm_gpt_words``: two calls q per (row, j)) and f64 from there on: Box-Muller with u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24,
-    (n0, n1) = sqrt(-2 ln u1) (cos, sin)(2 pi u2), (n2, n3) likewise from r2, r3; component a = 4 q + m."""
-    import numpy as np
+    (``ddpm_gpt_words``: two calls q per (row, j)) and f64 from there on (``box_muller_f64``); component a = 4 q + m."""
     assert 1 <= A <= 8
-    r = ddpm_gpt_words(seed, env_offset, n, t, k, W)
-    out = np.zeros((n, W, 2, 4))
-    for p in range(2):
-        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
-        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
-        rad = np.sqrt(-2.0 * np.log(u1))
-        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
-    return out.reshape(n, W, 8)[:, :, :A]
+    return box_muller_f64(ddpm_gpt_words(seed, env_offset, n, t, k, W)).reshape(n, W, 8)[:, :, :A]
 
 
 class DiffusionGPTDenoiser(nn.Module):
@@ -1463,7 +1574,7 @@ class DiffusionGPTDenoiser(nn.Module):
         return self.action_pred(_layer_norm(self.ln_f, self.hidden(x, keep).contiguous()))
 
 
-class DDPMGPTPolicy:
+class DDPMGPTPolicy(NativePolicy):
     """DiffusionAgent.predict with window_size > 1 (agents/ddpm_agent.py:213-274) around Diffusion.sample (gc_diffusion.py:117-216) with the transformer denoiser, on
     a batch: scaled observation window (deque maxlen W; the window GROWS at episode start), ALL L action positions of the window start from noise (no action history,
     unlike BESO), T reverse steps - epsilon prediction, x0 clipped to the data bounds in scaled space, posterior mean, posterior noise except at step 0 -, final clamp,
@@ -1495,10 +1606,9 @@ class DDPMGPTPolicy:
         f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
         self.min_action, self.max_action = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
         self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
-        self.seed, self.env_offset, self.noise_in = int(seed), 0, noise_in
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
+        self._init_stream(seed)
+        self.noise_in = noise_in
         self.hist = None
-        self._packed = PackedWeights()
         self.record = False           # also keep what every launch drew (last_noise: {k: [n, W, A]})
         self.last_bad = self.last_noise = None
 
@@ -1548,11 +1658,18 @@ class DDPMGPTPolicy:
         except (AttributeError, TypeError, ValueError):
             return False
 
-    # ---- the policy protocol of the Sims and SubBatchSet
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
+    SWITCH, LAST = "D3IL_POLICY_DDPM_GPT_STEP", ("last_bad", "last_noise")
+
     @property
     def f16x3_blocks(self) -> bool:
         """The blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
         return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.model.blocks)
+
+    def _state(self, n):
+        """The observation window for n lanes; a new size starts empty."""
+        if self.hist is None or self.hist.buf.shape[0] != n:
+            self.hist = _History(n, self.W, self.model.state_dim, self.device)
 
     def reset(self):
         if self.hist is not None:
@@ -1562,31 +1679,15 @@ class DDPMGPTPolicy:
         if self.hist is not None:
             self.hist.reset_(mask)
 
-    def set_rollout_range(self, offset, count):
-        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
-        self.env_offset = int(offset)
-        if self.hist is not None and self.hist.buf.shape[0] != count:
-            self.hist = None
-
     def fork(self):
-        """A clone for another sub-batch: denoiser, scaler and schedule shared; history, step word and packed tables its own."""
-        import copy
-        c = copy.copy(self)
+        """A clone for another sub-batch: denoiser, scaler and schedule shared; step word and packed tables its own, an empty history."""
+        c = super().fork()
         c.hist = None
-        c._t = self._t.clone()
-        c._packed = PackedWeights()
-        c.last_bad = c.last_noise = None
         return c
 
     def load_reference_state_dict(self, sd):
         """``Diffusion.state_dict()`` of the reference: the denoiser sits under ``model.``."""
         self.model.load_state_dict({k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")})
-
-    def use_ema(self, shadow_params):
-        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order."""
-        with torch.no_grad():
-            for p, s in zip(self.model.parameters(), shadow_params):
-                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
 
     # ---- packed tables
     def _pack_params(self):
@@ -1601,44 +1702,28 @@ class DDPMGPTPolicy:
                 "bias_pos": (m.action_emb.bias + m.pos_emb[0, :self.W]).to(torch.float32).contiguous()}
 
     def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
-        self._packed.invalidate()
+        super().invalidate_packed()
         for blk in self.model.blocks:
             blk.invalidate_packed()
 
     def ensure_packed(self):
-        """The packed tables and the blocks' packed weights follow the parameters (outside any capture) - e.g. after the EMA swap of a rollout."""
+        """The packed tables (on the CPU too: the torch path reads them) and the blocks' packed weights follow the parameters (outside any capture)."""
         self._packed.ensure(self._pack_params(), self._pack)
         if self.model.pos_emb.is_cuda:
             ensure_blocks_packed(self.model.blocks)
-
-    # ---- CapturedPolicy's hooks
-    def capture_snapshot(self, obs):
-        """Before the warm-up calls of a capture: the per-episode state (history, lengths, step word), which capture_restore puts back - warm-up and capture do not
-        count as steps.  (The chain has one form only: nothing to switch.)"""
-        if self.hist is None or self.hist.buf.shape[0] != obs.shape[0]:
-            self.hist = _History(obs.shape[0], self.W, obs.shape[1], self.device)
-        return (self.hist.buf.clone(), self.hist.len.clone(), self.hist.lockstep, self._t.clone())
-
-    def capture_restore(self, snap):
-        buf, ln, lock, t = snap
-        self.hist.buf.copy_(buf); self.hist.len.copy_(ln); self._t.copy_(t)
-        self.hist.lockstep = lock
 
     # ---- one step of the chain
     def step_kernel_ok(self, dev) -> bool:
         m = self.model
         C = m.embed_dim
         return (dev.type == "cuda" and m.linear_output and m.pos_emb.dtype == torch.float32 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 8 and 1 <= self.W <= 16 and 1 <= self.T <= 255
-                and os.environ.get("D3IL_POLICY_DDPM_GPT_STEP", "1") == "1")
+                and self._switch_on())
 
     def _noise(self, k, n, dev):
         """The normals of chain index k as the torch path takes them: ``noise_in(k, n)`` or the host form of the kernel's Philox draw."""
         if self.noise_in is not None:
             return torch.as_tensor(self.noise_in(k, n), dtype=torch.float32).to(dev).reshape(n, self.W, self.A).contiguous()
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("DDPMGPTPolicy: the torch path draws its Philox normals on the host and cannot be captured; the step kernel draws on the device")
-        return torch.as_tensor(ddpm_gpt_normals(self.seed, self.env_offset, n, int(self._t.item()) & 0xFFFFFFFF, k, self.W, self.A), dtype=torch.float32).to(dev)
+        return torch.as_tensor(ddpm_gpt_normals(self.seed, self.env_offset, n, self._host_step_word(), k, self.W, self.A), dtype=torch.float32).to(dev)
 
     def _step_torch(self, st, k, hk):
         """Steps 1 - 8 of csrc/policy_ddpm_gpt.h as torch ops, in the kernel's order of operations, on the chain state ``st`` (x, xbuf, bad, lengths, packed tables)."""
@@ -1694,15 +1779,13 @@ class DDPMGPTPolicy:
         s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32))
         m, W, T = self.model, self.W, self.T
         n, dev = s.shape[0], s.device
-        capturing = s.is_cuda and torch.cuda.is_current_stream_capturing()
         if s.is_cuda and not _ENV_GUARD_TRIED and self.f16x3_blocks:
             _env_range_guard(dev)
-        if not capturing:
+        if not (s.is_cuda and _capturing()):
             self.ensure_packed()
         assert self._packed.key is not None, "a captured graph replays the packed tables: call ensure_packed() before capturing"
         w = self._packed.buf
-        if self.hist is None or self.hist.buf.shape[0] != n:
-            self.hist = _History(n, W, s.shape[1], self.device)
+        self._state(n)
         self.hist.append_(s)
         states, ln = self.hist.padded()
         C = m.embed_dim
@@ -1750,43 +1833,27 @@ IBC_EDGE = 1e-4               # a draw this close to an edge of the normalised C
 def ibc_words(seed: int, env_offset: int, n: int, t: int, kind: int, k: int, S: int = 64):
     """The Philox words of the chain kernel: uint32 [n, S, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
     IBC_TAG | kind << 14 | k << 8 | s << 2 | q)); kind 0 = start point, 1 = noise of iteration k, 2 = the draw (s = q = 0 is the word that is used)."""
-    import numpy as np
     assert 0 <= kind <= 2 and 0 <= k <= 63 and 1 <= S <= 64, "the counter layout holds k <= 63 and s <= 63"
-    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1, 1)
-    s = np.arange(S, dtype=np.uint64).reshape(1, S, 1)
-    q = np.arange(2, dtype=np.uint64).reshape(1, 1, 2)
-    tag = np.uint64(IBC_TAG | (kind << 14) | (k << 8)) | (s << np.uint64(2)) | q
-    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+    s, q = _tag_axes(S, 2)
+    return philox_words(seed, env_offset, n, t, np.uint64(IBC_TAG | (kind << 14) | (k << 8)) | (s << np.uint64(2)) | q)
 
 
 def ibc_start_uniforms(seed: int, env_offset: int, n: int, t: int, A: int, S: int = 64):
     """The kernel's start-point uniforms of environments 0 .. n-1 at step word t: float32 [n, S, A] in [0, 1 - 2^-24], component a = 4 q + m takes word m of
     call q.  The start point is lo + u (hi - lo), every operation rounded to f32."""
-    import numpy as np
     assert 1 <= A <= 8
-    r = ibc_words(seed, env_offset, n, t, 0, 0, S).reshape(n, S, 8)[:, :, :A]
-    return ((r >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+    return uniform24(ibc_words(seed, env_offset, n, t, 0, 0, S).reshape(n, S, 8)[:, :, :A])
 
 
 def ibc_normals(seed: int, env_offset: int, n: int, t: int, k: int, A: int, S: int = 64):
-    """The kernel's normals of iteration k: float64 [n, S, A].  Exact on the words and f64 from there on, Box-Muller as ``ddpm_gpt_normals``."""
-    import numpy as np
+    """The kernel's normals of iteration k: float64 [n, S, A].  Exact on the words and f64 from there on (``box_muller_f64``)."""
     assert 1 <= A <= 8
-    r = ibc_words(seed, env_offset, n, t, 1, k, S)
-    out = np.zeros((n, S, 2, 4))
-    for p in range(2):
-        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
-        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
-        rad = np.sqrt(-2.0 * np.log(u1))
-        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
-    return out.reshape(n, S, 8)[:, :, :A]
+    return box_muller_f64(ibc_words(seed, env_offset, n, t, 1, k, S)).reshape(n, S, 8)[:, :, :A]
 
 
 def ibc_pick_uniforms(seed: int, env_offset: int, n: int, t: int):
     """The kernel's uniform of the categorical draw, one per environment: float32 [n]."""
-    import numpy as np
-    r0 = ibc_words(seed, env_offset, n, t, 2, 0, 1)[:, 0, 0, 0]
-    return ((r0 >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+    return uniform24(ibc_words(seed, env_offset, n, t, 2, 0, 1)[:, 0, 0, 0])
 
 
 def ibc_step_sizes(iterations: int, init_infer: float, init: float, final: float, power: float, second_init: float, second: bool = True):
@@ -1828,7 +1895,7 @@ def resmlp_energy_and_grad(model: ResidualMLP, rows, obs_dim: int, grad: bool = 
     return e, g @ lin_in.weight[:, obs_dim:]
 
 
-class IBCPolicy:
+class IBCPolicy(NativePolicy):
     """IBCAgent.predict without goals (agents/ibc_agent.py:248-286) around LangevinMCMCSampler.infer (samplers/langevin_mcmc.py:129-163, 236-286) on the energy
     network EBMMLP (ebms.py:21-51: a ResidualMLPNetwork on [state | action] with one output), on a batch: scale the observation, S uniform start points per
     environment inside the data bounds (scaled space), K Langevin iterations x <- clamp(x - clamp(step / 2 dE/dx + step noise_scale z, +-clip), lo, hi) with
@@ -1863,10 +1930,8 @@ class IBCPolicy:
         self.lo, self.hi, self.clip = f(b[0]), f(b[1]), f(self.delta_action_clip * 0.5 * (b[1] - b[0]))      # (the clip in f64 from the f64 bounds, as the reference)
         self.coef = f(torch.tensor([[v * 0.5, v] for v in self.steps], dtype=torch.float64).reshape(self.K, 2))
         self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
-        self.seed, self.env_offset, self.n_envs = int(seed), 0, n_envs
-        self.x0_in, self.noise_in, self.u_in = x0_in, noise_in, u_in
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
-        self._packed = PackedWeights()
+        self._init_stream(seed)
+        self.n_envs, self.x0_in, self.noise_in, self.u_in = n_envs, x0_in, noise_in, u_in
         self.record = False           # also keep the chain's start points, noise, final samples and energies (last_x0, last_noise, last_x, last_energies)
         self.last_picks = self.last_u = self.last_x0 = self.last_noise = self.last_x = self.last_energies = None
 
@@ -1917,36 +1982,15 @@ class IBCPolicy:
         except (AttributeError, TypeError, ValueError, IndexError):
             return False
 
-    # ---- the policy protocol of the Sims and SubBatchSet
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
+    SWITCH, LAST = "D3IL_POLICY_IBC_FUSED", ("last_picks", "last_u", "last_x0", "last_noise", "last_x", "last_energies")
+
     def reset(self):
         pass
-
-    def set_rollout_range(self, offset, count):
-        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
-        self.env_offset = int(offset)
-
-    def fork(self):
-        """A clone for another sub-batch: network, scaler and tables shared; step word and packed buffers its own."""
-        import copy
-        c = copy.copy(self)
-        c._t = self._t.clone()
-        c._packed = PackedWeights()
-        c.last_picks = c.last_u = c.last_x0 = c.last_noise = c.last_x = c.last_energies = None
-        return c
-
-    def captured(self):
-        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: one kernel and the add on the step word)."""
-        return CapturedPolicy(self)
 
     def load_reference_state_dict(self, sd):
         """``EBMMLP.state_dict()`` of the reference: the network sits under ``mlp.``."""
         self.model.load_state_dict({k[len("mlp."):]: v for k, v in sd.items() if k.startswith("mlp.")})
-
-    def use_ema(self, shadow_params):
-        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order."""
-        with torch.no_grad():
-            for p, s in zip(self.model.parameters(), shadow_params):
-                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
 
     # ---- packed tables
     def _pack_params(self):
@@ -1964,28 +2008,12 @@ class IBCPolicy:
         out["wT_act"] = pack_resmlp_weights(lin_in, [], act)["w_out"]
         return out
 
-    def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
-        self._packed.invalidate()
-
-    def ensure_packed(self):
-        if next(self.model.parameters()).is_cuda:
-            self._packed.ensure(self._pack_params(), self._pack)
-
-    # ---- CapturedPolicy's hooks
-    def capture_snapshot(self, obs):
-        """Warm-up and capture do not count as steps: the step word is put back."""
-        return self._t.clone()
-
-    def capture_restore(self, snap):
-        self._t.copy_(snap)
-
     # ---- the chain
     def fused_ok(self, s) -> bool:
         lin_in, blocks, _ = self.model._parts()
         w = lin_in.weight
         return (s.is_cuda and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and len(blocks) <= 4 and lin_in.in_features <= 28
-                and self.S == 64 and os.environ.get("D3IL_POLICY_IBC_FUSED", "1") == "1")
+                and self.S == 64 and self._switch_on())
 
     def _banks(self, n, dev, need_host: bool):
         """(x0, noise, u) as the torch path takes them / as the kernel is handed them: the given banks, or (``need_host``) the host form of the kernel's draws."""
@@ -1994,10 +2022,7 @@ class IBCPolicy:
         nz = f(self.noise_in(n), (self.K, n, self.S, self.A)) if self.noise_in is not None else None
         u = f(self.u_in(n), (n,)) if self.u_in is not None else None
         if need_host and (x0 is None or nz is None or u is None):
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("IBCPolicy: the torch chain draws its Philox numbers on the host and cannot be captured; the kernel draws on the device")
-            import numpy as np
-            t = int(self._t.item()) & 0xFFFFFFFF
+            t = self._host_step_word()
             if x0 is None:
                 uu = torch.as_tensor(ibc_start_uniforms(self.seed, self.env_offset, n, t, self.A, self.S)).to(dev)
                 x0 = self.lo + uu * (self.hi - self.lo)
@@ -2062,12 +2087,9 @@ class IBCPolicy:
         if self.fused_ok(s):
             y = self._chain_kernel(s)
         else:
-            if s.is_cuda and os.environ.get("D3IL_POLICY_IBC_FUSED", "1") == "1" and not getattr(self, "_warned", False):
-                import warnings
-                self._warned = True      # (once per policy; forks copy the flag)
-                warnings.warn("IBCPolicy: this network (hidden %d, %d blocks, %d inputs, %d samples) is not one the chain kernel is built for; every call runs the torch chain "
-                              "with its Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
-                              % (self.model._parts()[0].out_features, len(self.model._parts()[1]), self.model._parts()[0].in_features, self.S))
+            self._warn_fallback(s, lambda: "this network (hidden %d, %d blocks, %d inputs, %d samples) is not one the chain kernel is built for; every call runs the torch chain "
+                                "with its Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                                % (self.model._parts()[0].out_features, len(self.model._parts()[1]), self.model._parts()[0].in_features, self.S))
             x0, nz, u = self._banks(s.shape[0], s.device, True)
             y, self.last_picks, self.last_x, self.last_energies = self._chain_torch(s, x0, nz, u)
             self.last_u, self.last_x0, self.last_noise = u, x0, nz
@@ -2097,18 +2119,13 @@ ACT_TAG = 0x41430000          # fourth Philox counter word of the chunk kernel, 
 
 def act_latent_words(seed: int, env_offset: int, n: int, t: int):
     """The Philox words of the chunk kernel: uint32 [n, 8 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t, ACT_TAG | q))."""
-    import numpy as np
-    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1)
-    q = np.arange(8, dtype=np.uint64).reshape(1, 8)
-    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, np.uint64(ACT_TAG) | q), axis=-1)
+    return philox_words(seed, env_offset, n, t, np.uint64(ACT_TAG) | _tag_axes(8)[0])
 
 
 def act_latent_uniforms(seed: int, env_offset: int, n: int, t: int):
     """The kernel's latent of environments 0 .. n-1 at step word t: float32 [n, 32] in [0, 1 - 2^-24], component 4 q + m = 24 bits of word m of call q
     (the reference draws torch.rand: uniform, not normal)."""
-    import numpy as np
-    r = act_latent_words(seed, env_offset, n, t).reshape(n, 32)
-    return ((r >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+    return uniform24(act_latent_words(seed, env_offset, n, t).reshape(n, 32))
 
 
 def act_reference_shapes(obs_dim: int, action_dim: int, T: int, C: int = 64, enc_layers: int = 2, dec_layers: int = 4, latent_dim: int = 32, action_enc_layers: int = 2) -> dict:
@@ -2132,7 +2149,6 @@ def act_synthetic_state(shapes: dict, seed: int) -> dict:
     """Fixed-seed weights of trained-like magnitudes for an ActVAE-shaped state dict (there are no checkpoints offline; the reference's initialisation, std 0.02
     and zero biases, makes the network nearly linear): one np.random.RandomState(seed), drawn in sorted key order - matrices N(0, 1) 1.2 / sqrt(fan-in) (the action head 2.4: scaled actions of order 2), LayerNorm
     weights 1 + 0.15 N, biases 0.2 N, embeddings and position tables 0.4 N, all rounded to f32.  The golden generator and the tests rebuild the same arrays."""
-    import numpy as np
     rs = np.random.RandomState(seed)
     out = {}
     for k in sorted(shapes):
@@ -2273,7 +2289,7 @@ def pack_act_weights(net: ActNet) -> dict:
             "enc_w": torch.stack(enc_w), "enc_v": torch.stack(enc_v), "dec_w": torch.stack(dec_w), "dec_v": torch.stack(dec_v), "head_w": flat(pack_tiles(net.action_head.weight))}
 
 
-class ACTPolicy:
+class ACTPolicy(NativePolicy):
     """ActAgent.predict without goals (agents/act_agent.py:207-239) around ActVAE.forward without actions (act_vae.py:389-445), on a batch: scale the observation;
     a lane whose ``counter`` equals the chunk length T is due and computes a new chunk of T actions from its CURRENT observation and a fresh uniform latent -
     clamped to the scaler's bounds in the scaled space, inverse-scaled, stored -; every lane then emits chunk[counter] and counts on.  ``reset()`` makes all lanes
@@ -2295,10 +2311,8 @@ class ACTPolicy:
         f = lambda a: a.detach().to(device=dev, dtype=torch.float32).contiguous()
         self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
         self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
-        self.seed, self.env_offset, self.n_envs = int(seed), 0, n_envs
-        self.latent_in = latent_in
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
-        self._packed = PackedWeights()
+        self._init_stream(seed)
+        self.n_envs, self.latent_in = n_envs, latent_in
         self.counter = self.chunk = self.last_latent = None          # per-lane state: i32 [N], f32 [N, T, A] (clamped, inverse-scaled), the latent of the lane's chunk [N, 32]
         self.record = False           # also keep a copy of the chunk table after every call (last_chunk)
         self.last_chunk = None
@@ -2359,7 +2373,9 @@ class ACTPolicy:
         except (AttributeError, TypeError, ValueError, IndexError):
             return False
 
-    # ---- the policy protocol of the Sims and SubBatchSet
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
+    SWITCH, STATE, LAST = "D3IL_POLICY_ACT_FUSED", ("counter", "chunk", "last_latent"), ("last_chunk",)
+
     def _state(self, n):
         """counter / chunk / last_latent for n lanes; a new size starts with every lane due."""
         if self.counter is None or self.counter.shape[0] != n:
@@ -2378,26 +2394,6 @@ class ACTPolicy:
         self._state(int(mask.shape[0]))
         self.counter.masked_fill_(mask.to(device=self.device, dtype=torch.bool), self.T)
 
-    def set_rollout_range(self, offset, count):
-        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
-        self.env_offset = int(offset)
-        self._state(int(count))
-
-    def fork(self):
-        """A clone for another sub-batch: network, scaler and tables shared; per-lane state, step word and packed buffers its own."""
-        import copy
-        c = copy.copy(self)
-        c._t = self._t.clone()
-        c._packed = PackedWeights()
-        if self.counter is not None:
-            c.counter, c.chunk, c.last_latent = self.counter.clone(), self.chunk.clone(), self.last_latent.clone()
-        c.last_chunk = None
-        return c
-
-    def captured(self):
-        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: one kernel and the add on the step word)."""
-        return CapturedPolicy(self)
-
     def load_reference_state_dict(self, sd):
         """``ActVAE.state_dict()`` of the reference: a plain load of the keys the inference path has (masks and the training-only modules are ignored)."""
         own = self.model.state_dict()
@@ -2412,24 +2408,6 @@ class ACTPolicy:
     def _pack(self):
         return pack_act_weights(self.model)
 
-    def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
-        self._packed.invalidate()
-
-    def ensure_packed(self):
-        if next(self.model.parameters()).is_cuda and self._kernel_shape():
-            self._packed.ensure(self._pack_params(), self._pack)
-
-    # ---- CapturedPolicy's hooks
-    def capture_snapshot(self, obs):
-        """Warm-up and capture consume neither a step nor a chunk position: step word, counters and chunks are put back."""
-        self._state(int(obs.shape[0]))
-        return self._t.clone(), self.counter.clone(), self.chunk.clone(), self.last_latent.clone()
-
-    def capture_restore(self, snap):
-        for dst, src in zip((self._t, self.counter, self.chunk, self.last_latent), snap):
-            dst.copy_(src)
-
     # ---- the step
     def _kernel_shape(self) -> bool:
         m = self.model
@@ -2438,7 +2416,7 @@ class ACTPolicy:
 
     def fused_ok(self, s) -> bool:
         w = self.model.state_encoder.weight
-        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and os.environ.get("D3IL_POLICY_ACT_FUSED", "1") == "1"
+        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
 
     def _latent(self, n, dev, need_host: bool):
         """The latent as the torch path takes it / as the kernel is handed it: the given bank, or (``need_host``) the host form of the kernel's draw."""
@@ -2446,7 +2424,7 @@ class ACTPolicy:
             return torch.as_tensor(self.latent_in(n), dtype=torch.float32).to(dev).reshape(n, self.model.latent_dim).contiguous()
         if not need_host:
             return None
-        return torch.as_tensor(act_latent_uniforms(self.seed, self.env_offset, n, int(self._t.item()) & 0xFFFFFFFF)).to(dev)
+        return torch.as_tensor(act_latent_uniforms(self.seed, self.env_offset, n, self._host_step_word())).to(dev)
 
     def _chunk_torch(self, s, z):
         """A new chunk for every row, in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too): network, clamp to the bounds in the
@@ -2459,7 +2437,7 @@ class ACTPolicy:
         return torch.where(bad.reshape(-1, 1, 1), torch.full_like(y, float("nan")), y)
 
     def _step_torch(self, s):
-        if s.is_cuda and torch.cuda.is_current_stream_capturing():
+        if s.is_cuda and _capturing():
             raise RuntimeError("ACTPolicy: the torch path decides on the host which lanes are due and draws its Philox numbers there; it cannot be captured - the kernel can")
         n = s.shape[0]
         due = (self.counter >= self.T) | (self.counter < 0)
@@ -2495,11 +2473,8 @@ class ACTPolicy:
         if self.fused_ok(s):
             y = self._step_kernel(s)
         else:
-            if s.is_cuda and os.environ.get("D3IL_POLICY_ACT_FUSED", "1") == "1" and not getattr(self, "_warned", False):
-                import warnings
-                self._warned = True      # (once per policy; forks copy the flag)
-                warnings.warn("ACTPolicy: this network (width %d, %d heads, latent %d, T %d) is not one the chunk kernel is built for; every call runs the torch path "
-                              "with a device synchronisation per call and no graph capture" % (self.model.C, self.model.n_head, self.model.latent_dim, self.T))
+            self._warn_fallback(s, lambda: "this network (width %d, %d heads, latent %d, T %d) is not one the chunk kernel is built for; every call runs the torch path "
+                                "with a device synchronisation per call and no graph capture" % (self.model.C, self.model.n_head, self.model.latent_dim, self.T))
             y = self._step_torch(s)
         if self.record:
             self.last_chunk = self.chunk.clone()
@@ -2527,28 +2502,17 @@ CVAE_Z_BOUND = 0.5            # VariationalAE.predict clamps its prior sample to
 
 def cvae_words(seed: int, env_offset: int, n: int, t: int):
     """The Philox words of the decode kernel: uint32 [n, 8 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t, CVAE_TAG | q))."""
-    import numpy as np
-    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1)
-    q = np.arange(8, dtype=np.uint64).reshape(1, 8)
-    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, np.uint64(CVAE_TAG) | q), axis=-1)
+    return philox_words(seed, env_offset, n, t, np.uint64(CVAE_TAG) | _tag_axes(8)[0])
 
 
 def cvae_latent_normals(seed: int, env_offset: int, n: int, t: int, L: int):
     """The kernel's UNCLAMPED standard normals of environments 0 .. n-1 at step word t: float64 [n, L], component a = 4 q + m from word m of call q.  Exact on the
-    words and f64 from there on, Box-Muller as ``ddpm_gpt_normals`` (words 0, 1 -> components 0, 1; words 2, 3 -> components 2, 3)."""
-    import numpy as np
+    words and f64 from there on (``box_muller_f64``: words 0, 1 -> components 0, 1; words 2, 3 -> components 2, 3)."""
     assert 1 <= L <= 32, "the counter layout holds eight calls of four components"
-    r = cvae_words(seed, env_offset, n, t)
-    out = np.zeros((n, 8, 4))
-    for p in range(2):
-        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
-        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
-        rad = np.sqrt(-2.0 * np.log(u1))
-        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
-    return out.reshape(n, 32)[:, :L]
+    return box_muller_f64(cvae_words(seed, env_offset, n, t)).reshape(n, 32)[:, :L]
 
 
-class CVAEPolicy:
+class CVAEPolicy(NativePolicy):
     """CVAEAgent.predict (agents/cvae_agent.py:155-170) around VariationalAE.predict (agents/models/vae/cvae.py:55-62) on a batch: scale the observation, draw a
     standard-normal latent per environment and CLAMP IT TO +-0.5 - the reference clamps its prior sample, so 2 (1 - Phi(0.5)) = 61.7 % of all latent components sit
     exactly on a bound; kept as it is -, run the decoder (a Mish ResidualMLPNetwork) on [state | z] (state first), clamp to the data bounds (scaled space),
@@ -2575,10 +2539,8 @@ class CVAEPolicy:
         f = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous()
         self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
         self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
-        self.seed, self.env_offset, self.n_envs = int(seed), 0, n_envs
-        self.z_in = z_in
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
-        self._packed = PackedWeights()
+        self._init_stream(seed)
+        self.n_envs, self.z_in = n_envs, z_in
         self.last_z = None
 
     # ---- construction from the reference's objects
@@ -2625,26 +2587,11 @@ class CVAEPolicy:
         except (AttributeError, TypeError, ValueError, IndexError):
             return False
 
-    # ---- the policy protocol of the Sims and SubBatchSet
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
+    SWITCH, LAST = "D3IL_POLICY_CVAE_FUSED", ("last_z",)
+
     def reset(self):
         pass
-
-    def set_rollout_range(self, offset, count):
-        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
-        self.env_offset = int(offset)
-
-    def fork(self):
-        """A clone for another sub-batch: network, scaler and tables shared; step word and packed buffers its own."""
-        import copy
-        c = copy.copy(self)
-        c._t = self._t.clone()
-        c._packed = PackedWeights()
-        c.last_z = None
-        return c
-
-    def captured(self):
-        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: the scaling, one kernel and the add on the step word)."""
-        return CapturedPolicy(self)
 
     def load_reference_state_dict(self, sd):
         """``VariationalAE.state_dict()`` of the reference: the decoder sits under ``decoder.``; the encoder's entries are ignored."""
@@ -2658,28 +2605,12 @@ class CVAEPolicy:
         """pack_resmlp_weights of the decoder with the input layer packed to 64 columns."""
         return pack_resmlp_weights(*self.model._parts(), in_cols=64)
 
-    def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
-        self._packed.invalidate()
-
-    def ensure_packed(self):
-        if next(self.model.parameters()).is_cuda:
-            self._packed.ensure(self._pack_params(), self._pack)
-
-    # ---- CapturedPolicy's hooks
-    def capture_snapshot(self, obs):
-        """Warm-up and capture do not count as steps: the step word is put back."""
-        return self._t.clone()
-
-    def capture_restore(self, snap):
-        self._t.copy_(snap)
-
     # ---- the decode
     def fused_ok(self, s) -> bool:
         lin_in, _, lin_out = self.model._parts()
         w = lin_in.weight
         return (s.is_cuda and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and lin_in.in_features <= 64 and self.L <= 32
-                and lin_out.out_features <= 16 and os.environ.get("D3IL_POLICY_CVAE_FUSED", "1") == "1")
+                and lin_out.out_features <= 16 and self._switch_on())
 
     def _bank(self, n, dev, need_host: bool):
         """The unclamped latent as the torch path takes it / as the kernel is handed it: ``z_in``, or (``need_host``) the host form of the kernel's draw, or None."""
@@ -2687,10 +2618,7 @@ class CVAEPolicy:
             return torch.as_tensor(self.z_in(n), dtype=torch.float32).to(dev).reshape(n, self.L).contiguous()
         if not need_host:
             return None
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("CVAEPolicy: the torch path draws its Philox numbers on the host and cannot be captured; the kernel draws on the device")
-        t = int(self._t.item()) & 0xFFFFFFFF
-        return torch.as_tensor(cvae_latent_normals(self.seed, self.env_offset, n, t, self.L), dtype=torch.float32).to(dev)
+        return torch.as_tensor(cvae_latent_normals(self.seed, self.env_offset, n, self._host_step_word(), self.L), dtype=torch.float32).to(dev)
 
     def _decode_torch(self, s, z):
         """Steps 1 - 3 of csrc/policy_cvae.h as torch ops in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too) on the unclamped
@@ -2730,12 +2658,9 @@ class CVAEPolicy:
         if self.fused_ok(s):
             y = self._decode_kernel(s)
         else:
-            if s.is_cuda and os.environ.get("D3IL_POLICY_CVAE_FUSED", "1") == "1" and not getattr(self, "_warned", False):
-                import warnings
-                self._warned = True      # (once per policy; forks copy the flag)
-                warnings.warn("CVAEPolicy: this decoder (hidden %d, %d inputs, %d outputs) is not one the decode kernel is built for; every call runs torch's layers "
-                              "with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
-                              % (self.model._parts()[0].out_features, self.model._parts()[0].in_features, self.A))
+            self._warn_fallback(s, lambda: "this decoder (hidden %d, %d inputs, %d outputs) is not one the decode kernel is built for; every call runs torch's layers "
+                                "with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                                % (self.model._parts()[0].out_features, self.model._parts()[0].in_features, self.A))
             y, self.last_z = self._decode_torch(s, self._bank(s.shape[0], s.device, True))
         self._t.add_(1)
         return y
@@ -2764,28 +2689,16 @@ DDPM_ACT_TAG = 0x44410000     # fourth Philox counter word of the chain kernel, 
 def ddpm_act_words(seed: int, env_offset: int, n: int, t: int, k: int, Ta: int):
     """The Philox words behind ``ddpm_act_normals``: uint32 [n, Ta, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
     DDPM_ACT_TAG | k << 8 | j << 1 | q)), j the action token."""
-    import numpy as np
     assert 1 <= k <= 255 and 1 <= Ta <= 4, "the counter layout holds k <= 255; chain index 0 is never drawn; chunks of at most 4"
-    ge = (np.uint64(env_offset) + np.arange(n, dtype=np.uint64)).reshape(n, 1, 1)
-    j = np.arange(Ta, dtype=np.uint64).reshape(1, Ta, 1)
-    q = np.arange(2, dtype=np.uint64).reshape(1, 1, 2)
-    tag = np.uint64(DDPM_ACT_TAG | (k << 8)) | (j << np.uint64(1)) | q
-    return np.stack(philox4x32_10(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, ge & np.uint64(0xFFFFFFFF), ge >> np.uint64(32), t & 0xFFFFFFFF, tag), axis=-1)
+    j, q = _tag_axes(Ta, 2)
+    return philox_words(seed, env_offset, n, t, np.uint64(DDPM_ACT_TAG | (k << 8)) | (j << np.uint64(1)) | q)
 
 
 def ddpm_act_normals(seed: int, env_offset: int, n: int, t: int, k: int, Ta: int, A: int):
     """The chain kernel's normals of environments 0 .. n-1 at step word t and chain index k (T = the first iterate, i = reverse step i), on the host: float64
-    [n, Ta, A].  Exact on the 32-bit words and f64 from there on, Box-Muller as ``ddpm_gpt_normals``; component a = 4 q + m."""
-    import numpy as np
+    [n, Ta, A].  Exact on the 32-bit words and f64 from there on (``box_muller_f64``); component a = 4 q + m."""
     assert 1 <= A <= 8
-    r = ddpm_act_words(seed, env_offset, n, t, k, Ta)
-    out = np.zeros((n, Ta, 2, 4))
-    for p in range(2):
-        u1 = ((r[..., 2 * p] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
-        u2 = (r[..., 2 * p + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
-        rad = np.sqrt(-2.0 * np.log(u1))
-        out[..., 2 * p], out[..., 2 * p + 1] = rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
-    return out.reshape(n, Ta, 8)[:, :, :A]
+    return box_muller_f64(ddpm_act_words(seed, env_offset, n, t, k, Ta)).reshape(n, Ta, 8)[:, :, :A]
 
 
 def ddpm_act_reference_shapes(obs_dim: int, action_dim: int, obs_seq_len: int, action_seq_len: int, C: int = 64, enc_layers: int = 2, dec_layers: int = 4) -> dict:
@@ -2816,7 +2729,6 @@ def ddpm_act_synthetic_state(shapes: dict, seed: int) -> dict:
     into the residual stream (column a over its squared norm), so that the noise estimate follows the iterate.  A head that ignores the iterate makes
     x0 = sqrt(1 / ac) x - sqrt(1 / ac - 1) eps grow from step to step and EVERY chain ends on the clamp bounds; with it some final entries sit on a bound and most
     do not."""
-    import numpy as np
     rs = np.random.RandomState(seed)
     out = {}
     for k in sorted(shapes):
@@ -2915,7 +2827,7 @@ def pack_ddpm_act_weights(net: EncDecDenoiser, n_timesteps: int) -> dict:
             "enc_w": torch.stack(enc_w), "enc_v": torch.stack(enc_v), "dec_w": torch.stack(dec_w), "dec_v": torch.stack(dec_v), "head_w": flat(pack_tiles(net.action_pred.weight))}
 
 
-class DDPMACTPolicy:
+class DDPMACTPolicy(NativePolicy):
     """DiffusionAgent.predict of the encoder-decoder agent without goals (agents/ddpm_encdec_agent.py:222-257) around Diffusion.sample (diffusion_policy.py:117-217)
     and DiffusionEncDec.forward (diffusion_models.py:844-905), on a batch: the scaled observation enters the lane's window (deque maxlen obs_seq_len S) on EVERY
     step; a lane whose ``counter`` equals the chunk length Ta is due and samples a new chunk of Ta actions from its window as it stands (L entries, 1 <= L <= S; the
@@ -2946,9 +2858,8 @@ class DDPMACTPolicy:
         f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
         self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
         self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
-        self.seed, self.env_offset, self.n_envs, self.noise_in = int(seed), 0, n_envs, noise_in
-        self._t = torch.zeros(1, dtype=torch.int32, device=dev)      # the step word (the kernel reads it as u32)
-        self._packed = PackedWeights()
+        self._init_stream(seed)
+        self.n_envs, self.noise_in = n_envs, noise_in
         self.counter = self.chunk = self.hist = self.last_bad = None      # per-lane state: i32 [N], f32 [N, Ta, A] (clamped, inverse-scaled), the window, i32 [N]
         self.record = False           # also keep the chunk table and what was drawn after every call (last_chunk, last_noise [N, T + 1, Ta, A]: zero where nothing was drawn)
         self.last_chunk = self.last_noise = None
@@ -3031,7 +2942,9 @@ class DDPMACTPolicy:
         except (AttributeError, TypeError, ValueError, IndexError):
             return False
 
-    # ---- the policy protocol of the Sims and SubBatchSet
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; a fork and a capture keep the window, ``hist``, with the rest)
+    SWITCH, STATE, LAST = "D3IL_POLICY_DDPM_ACT_FUSED", ("counter", "chunk", "last_bad"), ("last_chunk", "last_noise")
+
     def _state(self, n):
         """counter / chunk / window / last_bad for n lanes; a new size starts with every lane due on an empty window."""
         if self.counter is None or self.counter.shape[0] != n:
@@ -3054,29 +2967,6 @@ class DDPMACTPolicy:
         self.counter.masked_fill_(m, self.Ta)
         self.hist.reset_(m)
 
-    def set_rollout_range(self, offset, count):
-        """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
-        self.env_offset = int(offset)
-        self._state(int(count))
-
-    def fork(self):
-        """A clone for another sub-batch: denoiser, scaler and schedule shared; per-lane state, step word and packed buffers its own."""
-        import copy
-        c = copy.copy(self)
-        c._t = self._t.clone()
-        c._packed = PackedWeights()
-        if self.counter is not None:
-            c.counter, c.chunk, c.last_bad = self.counter.clone(), self.chunk.clone(), self.last_bad.clone()
-            c.hist = _History(self.counter.shape[0], self.S, self.obs_dim, self.device)
-            c.hist.buf.copy_(self.hist.buf); c.hist.len.copy_(self.hist.len)
-            c.hist.lockstep = self.hist.lockstep
-        c.last_chunk = c.last_noise = None
-        return c
-
-    def captured(self):
-        """This policy as one captured HIP graph per batch shape (the fused path is a fixed chain: scaling, the window shift, one kernel, the add on the step word)."""
-        return CapturedPolicy(self)
-
     def load_reference_state_dict(self, sd):
         """``Diffusion.state_dict()`` of the reference: the denoiser sits under ``model.`` (a bare DiffusionEncDec state dict is taken as it is); masks are ignored."""
         if any(k.startswith("model.") for k in sd):
@@ -3086,38 +2976,12 @@ class DDPMACTPolicy:
         for p in self.model.parameters():
             p.requires_grad_(False)
 
-    def use_ema(self, shadow_params):
-        """One EMA swap per rollout (the reference swaps per predict call): shadow parameters in ``model.parameters()`` order, which is the reference's."""
-        with torch.no_grad():
-            for p, s in zip(self.model.parameters(), shadow_params):
-                p.copy_(torch.as_tensor(s, dtype=p.dtype, device=p.device))
-
     # ---- packed tables
     def _pack_params(self):
         return list(self.model.parameters())
 
     def _pack(self):
         return pack_ddpm_act_weights(self.model, self.T)
-
-    def invalidate_packed(self):
-        """After ``param.data`` writes (invisible to the version counters): the next call / ensure_packed() repacks."""
-        self._packed.invalidate()
-
-    def ensure_packed(self):
-        if next(self.model.parameters()).is_cuda and self._kernel_shape():
-            self._packed.ensure(self._pack_params(), self._pack)
-
-    # ---- CapturedPolicy's hooks
-    def capture_snapshot(self, obs):
-        """Warm-up and capture consume neither a step, a window entry nor a chunk position: step word, counters, chunks, window, lengths and last_bad are put back."""
-        self._state(int(obs.shape[0]))
-        return (self._t.clone(), self.counter.clone(), self.chunk.clone(), self.hist.buf.clone(), self.hist.len.clone(), self.last_bad.clone()), self.hist.lockstep
-
-    def capture_restore(self, snap):
-        tensors, lock = snap
-        for dst, src in zip((self._t, self.counter, self.chunk, self.hist.buf, self.hist.len, self.last_bad), tensors):
-            dst.copy_(src)
-        self.hist.lockstep = lock
 
     # ---- the step
     def _kernel_shape(self) -> bool:
@@ -3127,7 +2991,7 @@ class DDPMACTPolicy:
 
     def fused_ok(self, s) -> bool:
         w = self.model.tok_emb.weight
-        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and os.environ.get("D3IL_POLICY_DDPM_ACT_FUSED", "1") == "1"
+        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
 
     def _noise(self, n, dev, need_host: bool):
         """The normals [n, T + 1, Ta, A] (index = chain index) as the torch path takes them / as the kernel is handed them: the given bank, or (``need_host``) the
@@ -3136,8 +3000,7 @@ class DDPMACTPolicy:
             return torch.as_tensor(self.noise_in(n), dtype=torch.float32).to(dev).reshape(n, self.T + 1, self.Ta, self.A).contiguous()
         if not need_host:
             return None
-        import numpy as np
-        t = int(self._t.item()) & 0xFFFFFFFF
+        t = self._host_step_word()
         z = np.zeros((n, self.T + 1, self.Ta, self.A))
         for k in range(1, self.T + 1):
             z[:, k] = ddpm_act_normals(self.seed, self.env_offset, n, t, k, self.Ta, self.A)
@@ -3172,7 +3035,7 @@ class DDPMACTPolicy:
         return torch.where(bad.reshape(-1, 1, 1), torch.full_like(y, float("nan")), y), bad, x
 
     def _step_torch(self, win, ln):
-        if win.is_cuda and torch.cuda.is_current_stream_capturing():
+        if win.is_cuda and _capturing():
             raise RuntimeError("DDPMACTPolicy: the torch path decides on the host which lanes are due, groups them by window length and draws its Philox numbers there; "
                                "it cannot be captured - the kernel can")
         n, dev = win.shape[0], win.device
@@ -3226,12 +3089,9 @@ class DDPMACTPolicy:
         if self.fused_ok(s):
             y = self._step_kernel(win.contiguous(), ln.contiguous())
         else:
-            if s.is_cuda and os.environ.get("D3IL_POLICY_DDPM_ACT_FUSED", "1") == "1" and not getattr(self, "_warned", False):
-                import warnings
-                self._warned = True      # (once per policy; forks copy the flag)
-                warnings.warn("DDPMACTPolicy: this network (width %d, %d heads, window %d, chunk %d, linear head %s) is not one the chain kernel is built for; every call "
-                              "runs the torch path with a device synchronisation per call and no graph capture"
-                              % (self.model.embed_dim, self.model.n_heads, self.S, self.Ta, self.model.linear_output))
+            self._warn_fallback(s, lambda: "this network (width %d, %d heads, window %d, chunk %d, linear head %s) is not one the chain kernel is built for; every call "
+                                "runs the torch path with a device synchronisation per call and no graph capture"
+                                % (self.model.embed_dim, self.model.n_heads, self.S, self.Ta, self.model.linear_output))
             y = self._step_torch(win, ln)
         if self.record:
             self.last_chunk = self.chunk.clone()
