@@ -9,8 +9,12 @@
 // the last term (2^-22 relative, below the f32 rounding of the sum it belongs to) is dropped.  The products are exact in the f32 accumulators of the matrix
 // core (22-bit significands); `hh` and the cross terms accumulate separately and are combined once per output (acc_hh + 2^-11 acc_x).  Operands carry 22 of the 24
 // bits of an f32, so a 120-term dot product differs from the f32-FMA chain by about as much as two f32 summation orders differ from each other (measured against an
-// f64 reference in tests/test_policies_f16x3.py).  Range: |operand| <= 65504 (saturating) - LayerNorm outputs, GELU outputs and weights are O(1).
-// The saturation is silent in the default instantiations (GUARD = false), and it is expected to swallow a NaN / Inf operand too (the clamp returns its bound; not asserted by a test).  The
+// f64 reference in tests/test_policies_f16x3.py).  Range: |operand| <= 65504 (saturating) - LayerNorm outputs, GELU outputs and weights are O(1).  The 22 bits hold
+// for |operand| >= 2^-13; below that the low half is a subnormal f16 and the operand's absolute step is 2^-36 (2^-24 / 2^11).  The matrix cores do not flush subnormal
+// halves: rows and weights scaled down to 2^-20 - both halves subnormal - stay within the f32-level criterion of tests/test_gpu_f16x3_edges.py.
+// The saturation is silent in the default instantiations (GUARD = false), and it swallows a NaN / Inf operand too: an operand beyond +-65504, +-Inf included, gives
+// the row of that operand clamped to +-65504, and a NaN operand gives the row of the operand := -65504 (the clamp's maximum with -65504 comes first and returns its
+// bound), the same on every launch; every other row is bit-equal to a clean launch (pinned by the same test file on the MI355X, linear entry without LayerNorm).  The
 // GUARD = true instantiations (d3il_f16x3_set_guard; "range / NaN guard" below) count the rows it touched and let a non-finite operand through as NaN.
 // The kernels keep the structure of k_mlp_gelu_residual_f32 / k_linear120_f32 (policy_f32.h): one wave owns 16 token rows, the transposed product D[feature][row]
 // makes the D registers of the first MLP product the B operand of the second, four waves share the weight stream through a double-buffered LDS stage.

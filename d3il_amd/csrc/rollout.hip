@@ -1399,7 +1399,8 @@ int d3il_mlp_ln_gelu_residual_f16x3(const float* h, const float* ln_weight, cons
   if (!h || !x || !w_packed || !b1 || !b2 || !out) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: null argument");
   if (C != HX_C || H != HX_H) return fail(D3IL_EUNSUPPORTED, "d3il_mlp_ln_gelu_residual_f16x3: built for n_embd 120, hidden 480 (the DiffusionGPT of the BESO configs)");
   if (rows < 0) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: negative row count");
-  if (((uintptr_t)h | (uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)b2 | (uintptr_t)out) % 16 != 0) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: pointers must be 16-byte aligned");
+  // (b1 too: unlike the f32 kernel, k_mlp_gelu_residual_f16x3 copies fc1's bias to LDS with 16-byte loads)
+  if (((uintptr_t)h | (uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)out) % 16 != 0) return fail(D3IL_EINVAL, "d3il_mlp_ln_gelu_residual_f16x3: pointers must be 16-byte aligned");
   if (rows == 0) return D3IL_OK;
   const dim3 grid((unsigned)((rows + 16 * HX_MLP_NW - 1) / (16 * HX_MLP_NW))), block(64 * HX_MLP_NW);
   if (long long* counts = g_hx_guard_counts)

@@ -201,7 +201,9 @@ int d3il_linear120_f32(const float* xin, const float* ln_weight, const float* ln
  * significant bits), w x = wh xh + 2^-11 (wh xl + wl xh) in f32 accumulators - three v_mfma_f32_16x16x32_f16 per f32 product instead of sixteen f32-MFMA issue slots.
  * Agreement with an f64 reference is that of an f32 FMA chain (tests/test_policies_f16x3.py); operands saturate at +-65504.  w_packed: f16 halves in the kernels' tile
  * order (d3il_amd/policies.py pack_mlp_weights_f16x3: 16 stages of 2048 x 16 bytes; pack_linear120_weights_f16x3: an even number of tiles of 512 x 16 bytes).
- * The saturation is silent, and it is expected to turn a NaN / Inf operand into a finite number too (the clamp returns its bound), unless the range / NaN guard below is on. */
+ * The saturation is silent, and it turns a NaN / Inf operand into a finite number too (+-Inf into +-65504, NaN into -65504: tests/test_gpu_f16x3_edges.py), unless the
+ * range / NaN guard below is on.  Every pointer the kernels read or write by 16-byte vectors has to be 16-byte aligned (D3IL_EINVAL otherwise, before any launch):
+ * h | x | w_packed | b1 | b2 | out of the MLP, xin | w_packed | bias | resid | out of the linear layer. */
 int d3il_mlp_ln_gelu_residual_f16x3(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* x, const void* w_packed, const float* b1, const float* b2,
                                     float* out, long rows, int C, int H, void* stream);
 int d3il_linear120_f16x3(const float* xin, const float* ln_weight, const float* ln_bias, float ln_eps, const void* w_packed, const float* bias, const float* resid, float* out,
