@@ -99,12 +99,12 @@ class RowwiseAgent:
 
 def as_batched(agent, n_envs: int | None = None):
     """What the batched sims call: agents that provide ``predict_batch`` (the adapters of this module, or any policy written
-    for the batch) are used as they are; a reference ``BeT_Agent`` becomes a native ``policies.BeTPolicy``, a ``DiffusionAgent`` with the transformer denoiser a ``policies.DDPMGPTPolicy``, an ``IBCAgent`` with the plain Langevin sampler a ``policies.IBCPolicy``, an ``ActAgent`` (VAE-ACT, no goals) a ``policies.ACTPolicy``, a ``CVAEAgent`` with a plain Mish decoder a ``policies.CVAEPolicy``, a ``DiffusionAgent`` with the encoder-decoder denoiser (DDPM-ACT, no goals) a ``policies.DDPMACTPolicy``; everything else is wrapped row by row with per-lane state."""
+    for the batch) are used as they are; a reference ``BeT_Agent`` becomes a native ``policies.BeTPolicy``, a ``DiffusionAgent`` with the transformer denoiser a ``policies.DDPMGPTPolicy``, an ``IBCAgent`` with the plain Langevin sampler a ``policies.IBCPolicy``, an ``ActAgent`` (VAE-ACT, no goals) a ``policies.ACTPolicy``, a ``CVAEAgent`` with a plain Mish decoder a ``policies.CVAEPolicy``, a ``DiffusionAgent`` with the encoder-decoder denoiser (DDPM-ACT, no goals) a ``policies.DDPMACTPolicy``, a ``BetMLP_Agent`` with a plain Mish network and 64 bins a ``policies.BeTMLPPolicy``, a ``Gpt_Agent`` (BC-GPT, state observations) a ``policies.GPTBCPolicy``; everything else is wrapped row by row with per-lane state."""
     if hasattr(agent, "predict_batch"):
         if not hasattr(agent, "reset"):
             agent.reset = lambda: None
         return agent
-    from .policies import ACTPolicy, BeTPolicy, CVAEPolicy, DDPMACTPolicy, DDPMGPTPolicy, IBCPolicy
+    from .policies import ACTPolicy, BeTMLPPolicy, BeTPolicy, CVAEPolicy, DDPMACTPolicy, DDPMGPTPolicy, GPTBCPolicy, IBCPolicy
     if BeTPolicy.matches(agent):      # the reference's BeT_Agent: one batched forward + the sampling-head kernel per step instead of one predict per environment
         return BeTPolicy.from_reference(agent)
     if DDPMGPTPolicy.matches(agent):      # the reference's DiffusionAgent around a DiffusionTransformerNetwork: the batched sampler with the fused step kernel
@@ -117,6 +117,10 @@ def as_batched(agent, n_envs: int | None = None):
         return CVAEPolicy.from_reference(agent, n_envs=n_envs)
     if DDPMACTPolicy.matches(agent):      # the reference's enc-dec DiffusionAgent (DDPM-ACT) without goals: the whole reverse chain and the chunk bookkeeping in one kernel per step
         return DDPMACTPolicy.from_reference(agent, n_envs=n_envs)
+    if BeTMLPPolicy.matches(agent):      # the reference's BetMLP_Agent with a plain Mish network and 64 bins with offsets: network, draw and action tail in one kernel per step
+        return BeTMLPPolicy.from_reference(agent)
+    if GPTBCPolicy.matches(agent):      # the reference's Gpt_Agent (BC-GPT) on state observations: one batched forward + the head kernel per step
+        return GPTBCPolicy.from_reference(agent)
     return RowwiseAgent(agent, n_envs)
 
 

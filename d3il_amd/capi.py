@@ -44,10 +44,11 @@ IBC_TAG = 0x49420000      # ... of d3il_ibc_langevin_f32, or-ed with kind << 14 
 ACT_TAG = 0x41430000      # ... of d3il_act_chunk_f32, or-ed with q (csrc/policy_act.h)
 CVAE_TAG = 0x43560000      # ... of d3il_cvae_decode_f32, or-ed with q (csrc/policy_cvae.h)
 DDPM_ACT_TAG = 0x44410000      # ... of d3il_ddpm_act_chunk_f32, or-ed with k << 8 | t << 1 | q (csrc/policy_ddpm_act.h)
+BET_MLP_TAG = 0x424D4C50      # ... of d3il_bet_mlp_f32 (csrc/policy_bet_mlp.h)
 HXG_CLIPPED, HXG_NONFINITE, HXG_LAUNCHES, HXG_N = 0, 1, 2, 4      # the counters of d3il_f16x3_set_guard (D3IL_HXG_*)
 
 EXPORTS = ["d3il_create", "d3il_destroy", "d3il_start", "d3il_reset", "d3il_step", "d3il_get_buffers", "d3il_get_state",
-           "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
+           "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_bet_mlp_f32", "d3il_gpt_bc_head_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
            "d3il_rccl_available", "d3il_comm_unique_id", "d3il_comm_init", "d3il_comm_count", "d3il_comm_destroy", "d3il_reduce_metrics", "d3il_set_timing",
            "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_group_create", "d3il_group_flush", "d3il_group_destroy", "d3il_group_set_option", "d3il_group_stats", "d3il_group_pipeline_stats", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_debug_build_flags", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
 
@@ -119,6 +120,9 @@ def load():
         L.d3il_debug_scratch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.d3il_debug_build_flags.argtypes = [C.c_void_p]
         L.d3il_set_link_guard.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        if hasattr(L, "d3il_bet_mlp_f32"):      # (the parent build loaded through D3IL_LIB_PATH has neither the BeT-MLP kernel nor the BC-GPT head)
+            L.d3il_bet_mlp_f32.argtypes = [C.c_void_p] * 14 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 6 + [C.c_long] + [C.c_int] * 5 + [C.c_void_p]
+            L.d3il_gpt_bc_head_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 7 + [C.c_long, C.c_int, C.c_int, C.c_void_p]
         if hasattr(L, "d3il_group_create"):      # (an older build loaded through D3IL_LIB_PATH has no step group: has_step_group())
             L.d3il_group_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
             L.d3il_group_flush.argtypes = [C.c_void_p]

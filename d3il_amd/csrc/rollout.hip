@@ -33,6 +33,8 @@ constexpr int WAVE = 64;
 #include "policy_ddpm_act.h"
 #include "policy_f32.h"
 #include "policy_cvae.h"
+#include "policy_bet_mlp.h"
+#include "policy_gpt_bc.h"
 
 namespace d3il {
 
@@ -1573,6 +1575,42 @@ int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_i
   const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
   if (hidden == 128) hipLaunchKernelGGL(k_cvae_decode<128>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_cvae_decode<256>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_bet_mlp_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_logit, const float* b_logit,
+                     const float* w_off, const float* b_off, const float* centers, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed,
+                     uint64_t env_offset, const uint32_t* t_device, const float* u_in, float* actions, int32_t* bins, float* u_out, float* probs, long n_env, int obs_dim,
+                     int V, int A, int hidden, int n_blocks, void* stream) {
+  if ((hidden != 128 && hidden != 256) || V != BM_V || obs_dim < 1 || obs_dim > BM_OBSMAX || A < 1 || A > BM_AMAX || n_blocks < 0 || n_env > 0x7FFFFFFFL * 16)
+    return fail(D3IL_EUNSUPPORTED, "d3il_bet_mlp_f32: built for hidden 128 / 256, 64 bins, obs_dim 1 .. 28, 1 .. 8 action components and n_blocks >= 0");
+  if (!state || !w_in || !b_in || !w_blocks || !b_blocks || !w_logit || !b_logit || !w_off || !b_off || !centers || !lo || !hi || !scale || !shift || !t_device || !actions || !bins)
+    return fail(D3IL_EINVAL, "d3il_bet_mlp_f32: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_bet_mlp_f32: negative environment count");
+  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_logit | (uintptr_t)b_logit | (uintptr_t)w_off) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_bet_mlp_f32: the packed weights, their biases and the offset rows must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  BetMlpArgs a{state, w_in, b_in, w_blocks, b_blocks, w_logit, b_logit, w_off, b_off, centers, lo, hi, scale, shift, t_device, u_in, actions, bins, u_out, probs,
+               (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, n_blocks};
+  // one workgroup of eight waves per 16 environments; the last one may be partly filled
+  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
+  if (hidden == 128) hipLaunchKernelGGL(k_bet_mlp<128>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_bet_mlp<256>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_gpt_bc_head_f32(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_head, const float* lo, const float* hi, const float* scale,
+                         const float* shift, float* actions, int32_t* bad, long rows, int C, int A, void* stream) {
+  if (C < 4 || C > GB_CMAX || C % 4 != 0 || A < 1 || A > GB_AMAX)
+    return fail(D3IL_EUNSUPPORTED, "d3il_gpt_bc_head_f32: built for n_embd <= 128 (a multiple of 4) and 1 .. 16 action components");
+  if (!h || !ln_weight || !ln_bias || !w_head || !lo || !hi || !scale || !shift || !actions) return fail(D3IL_EINVAL, "d3il_gpt_bc_head_f32: null argument");
+  if (rows < 0) return fail(D3IL_EINVAL, "d3il_gpt_bc_head_f32: negative row count");
+  if (rows == 0) return D3IL_OK;
+  GptBcHeadArgs a{h, ln_weight, ln_bias, w_head, lo, hi, scale, shift, actions, bad, rows, ln_eps, C, A};
+  // four rows per wave where the batch allows it (a wave loads its 2 A head registers once), at most 1024 workgroups
+  long blocks = (rows + 4 * GB_NW - 1) / (4 * GB_NW);
+  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks))), block(64 * GB_NW);
+  hipLaunchKernelGGL(k_gpt_bc_head, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -2682,6 +2682,357 @@ class CVAEPolicy(NativePolicy):
         return cls(net.to(device), sc, latent_dim, seed=policy_seed, **kw)
 
 
+# ------------------------------------------------------------------------------------------------ BeT-MLP: the Behaviour Transformer's sampling tail on a residual MLP
+BET_MLP_TAG = 0x424D4C50      # fourth Philox counter word of the BeT-MLP kernel (csrc/policy_bet_mlp.h; never 0, never a word of the six tags above)
+BET_MLP_EDGE = 1e-4           # a draw this close to an edge of the normalised CDF is not decided between two arithmetics (tests, golden generator)
+
+
+def bet_mlp_words(seed: int, env_offset: int, n: int, t: int):
+    """The Philox words of the BeT-MLP kernel: uint32 [n, 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t, BET_MLP_TAG))."""
+    return philox_words(seed, env_offset, n, t, BET_MLP_TAG)
+
+
+def bet_mlp_uniforms(seed: int, env_offset: int, n: int, t: int):
+    """The kernel's uniforms of rows 0 .. n-1 at step word t, on the host: the upper 24 bits of word 0, float32 in [0, 1 - 2^-24]."""
+    return uniform24(bet_mlp_words(seed, env_offset, n, t)[:, 0])
+
+
+def pack_bet_mlp_weights(lin_in, blocks, lin_out, V: int = 64) -> dict:
+    """The ResidualMLPNetwork of a BeT-MLP policy for k_bet_mlp: input layer and blocks as ``pack_resmlp_weights`` packs them (32 input columns); rows 0 .. V-1 of the
+    output layer (the logits) as V / 16 output tiles in the operand order of its ``w_out`` tile, w_logit [V / 16][NT][lane (g, i)][r] = W[16 T + i][16 t + 4 g + r],
+    with b_logit [V]; rows V .. (the offsets, layout "(V A)") row-major as they are, w_off [V A][H] with b_off [V A]."""
+    from types import SimpleNamespace
+    dev, H = lin_in.weight.device, lin_in.out_features
+    NT = H // 16
+    assert V % 16 == 0 and lin_out.out_features % V == 0 and lin_out.out_features > V and lin_out.in_features == H and lin_out.bias is not None
+    none = SimpleNamespace(out_features=0, weight=torch.zeros(0, H, device=dev), bias=torch.zeros(0, device=dev))
+    pk = pack_resmlp_weights(lin_in, blocks, none)
+    del pk["w_out"], pk["b_out"]
+    ar = lambda k: torch.arange(k, device=dev)
+    T, t, g, i, r = ar(V // 16)[:, None, None, None, None], ar(NT)[None, :, None, None, None], ar(4)[None, None, :, None, None], ar(16)[None, None, None, :, None], ar(4)[None, None, None, None, :]
+    f = lambda x: x.detach().to(torch.float32).contiguous()
+    W, b = lin_out.weight, lin_out.bias
+    pk.update(w_logit=f(W[16 * T + i, 16 * t + 4 * g + r].reshape(V // 16, NT, 64, 4)), b_logit=f(b[:V]), w_off=f(W[V:]), b_off=f(b[V:]))
+    return pk
+
+
+class BeTMLPPolicy(NativePolicy):
+    """BetMLP_Agent.predict (agents/bet_mlp_agent.py:366-406) on a batch: scale the observation (no history - the agent's ``obs_context`` is never read in predict,
+    the reference feeds a [1, 1, obs] row), run the Mish ResidualMLPNetwork whose output layer (WITH bias) has V (1 + A) rows, softmax over the first V, ONE
+    categorical draw, the offsets of the drawn bin in the layout "(V A)" (generate_latents, same file 114-147), bin_centers[bin] + offset in f32
+    (k_means.py decode_actions), clamp to the data bounds IN SCALED SPACE (the f32 sum against the f64 bounds: the same as against their f32 roundings), inverse
+    scaling as an f64 product and sum on the f32 scale and shift, rounded to f32 once (the reference's output scaler is f64) - the dtypes CVAEPolicy has.
+
+    The draw is BeTPolicy's: bin = min(#{v : c_v <= u S}, V - 1), c the inclusive prefix sums of exp(logit - max), S = c_{V-1}, on ONE uniform per lane and step -
+    24 bits of Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word, BET_MLP_TAG), independent of batch order, sub-batches and ranks, unlike
+    torch.multinomial's device generator - or ``uniform_fn(n) -> [n]`` when given (golden replay, tests).
+
+    On a HIP device the whole call is ONE kernel (csrc/policy_bet_mlp.h through d3il_bet_mlp_f32: hidden 128 / 256, V = 64, obs <= 28, A <= 8, any number of blocks),
+    then a device-side add on the step word, so a captured graph draws fresh numbers at every replay.  On the CPU, for other shapes and with
+    D3IL_POLICY_BET_MLP_FUSED=0 the same arithmetic runs as torch ops (``_predict_torch``) with the uniforms computed on the host - that path cannot be captured.
+    An environment with a NaN / Inf in its scaled state row, final hidden row or logits gets bin -1 and NaN in every action component."""
+
+    def __init__(self, model: ResidualMLP, bin_centers, scaler: Scaler, seed: int = 0, uniform_fn=None):
+        self.model, self.scaler = model.eval(), scaler
+        dev = scaler.x_mean.device
+        self.device = dev
+        f = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.centers = f(bin_centers)
+        self.V, self.A = int(self.centers.shape[0]), int(self.centers.shape[1])
+        lin_in, _, lin_out = model._parts()
+        self.obs_dim = int(lin_in.in_features)
+        assert lin_out.out_features == self.V * (1 + self.A) and lin_out.bias is not None, "the output layer has V (1 + A) rows and a bias"
+        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self._init_stream(seed)
+        self.uniform_fn = uniform_fn
+        self.record = False           # also keep the probabilities (last_probs)
+        self.last_bins = self.last_u = self.last_probs = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, uniform_fn=None, device=None):
+        """From a live reference ``BetMLP_Agent`` (duck-typed): ``agent.model.model.state_dict()`` (the ResidualMLPNetwork), ``agent.action_ae.bin_centers``,
+        ``agent.scaler`` (its ``y_bounds`` are the clamp)."""
+        sd = {k: torch.as_tensor(v) for k, v in agent.model.model.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["layers.0.weight"].device
+        hidden, in_dim = sd["layers.0.weight"].shape
+        n_blocks = len({k.split(".")[1] for k in sd if ".l1." in k})
+        last = max(int(k.split(".")[1]) for k in sd)
+        net = ResidualMLP(in_dim, hidden, 2 * n_blocks, sd["layers.%d.weight" % last].shape[0])
+        net.load_state_dict(sd)
+        net = net.to(dev)
+        for p in net.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        return cls(net, torch.as_tensor(agent.action_ae.bin_centers), scaler, seed=seed, uniform_fn=uniform_fn)
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: a BetMLP_Agent whose policy predicts offsets on 64 bins with a ResidualMLPNetwork of plain ``nn.Linear``
+        layers and Mish blocks without norm and without spectral norm, an ``nn.Identity`` observation encoder, bin centres [64, A] with A <= 8 and a scaler with
+        bounds?  Everything else stays on the row-by-row adapter, which runs the reference's own code."""
+        try:
+            pol = agent.model
+            if type(agent).__name__ != "BetMLP_Agent" or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None:
+                return False
+            if not pol.predict_offsets or int(pol.vocab_size) != 64 or type(agent.obs_encoding_net) is not nn.Identity:
+                return False
+            layers = list(pol.model.layers)
+            if len(layers) < 2 or not all(type(l) is nn.Linear for l in (layers[0], layers[-1])):
+                return False
+            blocks = layers[1:-1]
+            lins = [layers[0], layers[-1]] + [l for b in blocks for l in (b.l1, b.l2)]
+            if not all(type(l) is nn.Linear and not hasattr(l, "weight_orig") and l.bias is not None for l in lins):
+                return False
+            if not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in blocks):
+                return False
+            H = layers[0].out_features
+            if not all(l.in_features == H and l.out_features == H for b in blocks for l in (b.l1, b.l2)) or layers[-1].in_features != H:
+                return False
+            centers = torch.as_tensor(agent.action_ae.bin_centers)
+            if centers.dim() != 2 or centers.shape[0] != 64 or not 1 <= centers.shape[1] <= 8:
+                return False
+            return layers[-1].out_features == 64 * (1 + centers.shape[1]) and int(getattr(pol, "act_dim", centers.shape[1])) == centers.shape[1]
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
+    SWITCH, LAST = "D3IL_POLICY_BET_MLP_FUSED", ("last_bins", "last_u", "last_probs")
+
+    def reset(self):
+        pass
+
+    def load_reference_state_dict(self, sd):
+        """``ResidualMLPNetwork.state_dict()`` of the reference (bet_mlp_agent.py: agent.model.model)."""
+        self.model.load_state_dict(sd)
+
+    # ---- packed tables
+    def _pack_params(self):
+        return list(self.model.parameters())
+
+    def _pack(self):
+        return pack_bet_mlp_weights(*self.model._parts(), V=self.V)
+
+    def _kernel_shape(self) -> bool:
+        lin_in, _, _ = self.model._parts()
+        return lin_in.out_features in (128, 256) and 1 <= lin_in.in_features <= 28 and self.V == 64 and 1 <= self.A <= 8
+
+    # ---- the call
+    def fused_ok(self, s) -> bool:
+        w = self.model._parts()[0].weight
+        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
+
+    def _uniforms(self, n, dev, need_host: bool):
+        """The uniforms as the torch path takes them / as the kernel is handed them: ``uniform_fn``, or (``need_host``) the host form of the kernel's draw, or None."""
+        if self.uniform_fn is not None:
+            return torch.as_tensor(self.uniform_fn(n), dtype=torch.float32).to(dev).reshape(n).contiguous()
+        if not need_host:
+            return None
+        return torch.as_tensor(bet_mlp_uniforms(self.seed, self.env_offset, n, self._host_step_word())).to(dev)
+
+    def _tail_torch(self, s, h, out, u):
+        """Steps 3 - 7 of csrc/policy_bet_mlp.h as torch ops in the dtype of ``out`` (f32 in the policy; the tests run it in f64 too), in the kernel's order of
+        operations where the order is defined (S is the last prefix sum): returns (actions, bins i32, probabilities)."""
+        V, A, dt, dev = self.V, self.A, out.dtype, out.device
+        logits = out[:, :V]
+        p = torch.exp(logits - logits.max(dim=1, keepdim=True).values)
+        c = torch.cumsum(p, dim=1)
+        S = c[:, -1:]
+        bins = (c <= u.to(dev, dt).unsqueeze(1) * S).sum(dim=1).clamp_max(V - 1)
+        off = out[:, V:].reshape(-1, V, A)[torch.arange(out.shape[0], device=dev), bins]
+        d = lambda v: v.to(device=dev, dtype=torch.float64)
+        v = self.centers.to(dev, dt)[bins] + off
+        y = (torch.minimum(torch.maximum(v, self.lo.to(dev, dt)), self.hi.to(dev, dt)).double() * d(self.out_scale) + d(self.out_shift)).to(dt)
+        bad = ~(torch.isfinite(s).all(dim=1) & torch.isfinite(h).all(dim=1) & torch.isfinite(logits).all(dim=1))
+        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        return y, torch.where(bad, torch.full_like(bins, -1), bins).to(torch.int32), p / S
+
+    def _predict_torch(self, s, u):
+        """Steps 1 - 7 on torch's layers: (actions, bins, probabilities)."""
+        h = s
+        for layer in self.model.layers[:-1]:
+            h = layer(h)
+        return self._tail_torch(s, h, self.model.layers[-1](h), u)
+
+    def _predict_kernel(self, s):
+        from . import capi
+        n, dev = s.shape[0], s.device
+        w = self._packed.current(self._pack_params(), self._pack)
+        u_in = self._uniforms(n, dev, False)
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        bins = torch.empty(n, dtype=torch.int32, device=dev)
+        u_out = torch.empty(n, dtype=torch.float32, device=dev)
+        probs = torch.empty(n, self.V, dtype=torch.float32, device=dev) if self.record else None
+        lin_in, blocks, _ = self.model._parts()
+        assert s.is_contiguous() and self._t.device == dev
+        capi.check(capi.load().d3il_bet_mlp_f32(s.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_logit"].data_ptr(),
+                                                w["b_logit"].data_ptr(), w["w_off"].data_ptr(), w["b_off"].data_ptr(), self.centers.data_ptr(), self.lo.data_ptr(),
+                                                self.hi.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed, self.env_offset, self._t.data_ptr(),
+                                                None if u_in is None else u_in.data_ptr(), y.data_ptr(), bins.data_ptr(), u_out.data_ptr(),
+                                                None if probs is None else probs.data_ptr(), n, self.obs_dim, self.V, self.A, lin_in.out_features, len(blocks),
+                                                torch.cuda.current_stream(dev).cuda_stream))
+        self.last_bins, self.last_u, self.last_probs = bins, u_out, probs
+        return y
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "BeTMLPPolicy: observation width %d, the network takes %d" % (s.shape[-1], self.obs_dim)
+        if self.fused_ok(s):
+            y = self._predict_kernel(s)
+        else:
+            self._warn_fallback(s, lambda: "this network (hidden %d, %d inputs, %d bins, %d action components) is not one the kernel is built for; every call runs "
+                                "torch's layers with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                                % (self.model._parts()[0].out_features, self.obs_dim, self.V, self.A))
+            u = self._uniforms(s.shape[0], s.device, True)
+            y, self.last_bins, probs = self._predict_torch(s, u)
+            self.last_u, self.last_probs = u, probs if self.record else None
+        self._t.add_(1)
+        return y
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, action_scale: float = 0.002, policy_seed: int = 0,
+               logit_std: float = 2.0, bound: float = 1.5, uniform_fn=None):
+        """A policy of the reference's shape with fixed random weights (there are no checkpoints offline): the shipped scripts use hidden 128 / 256 with 6 / 8 hidden
+        layers (3 / 4 blocks) and 64 bins; torch's default layer initialisation, the logit rows scaled to logits of a standard deviation of about ``logit_std`` (neither
+        uniform nor one-hot), small offsets, centres of 0.9, unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            net = ResidualMLP(obs_dim, hidden_dim, 2 * n_blocks, 64 * (1 + action_dim))
+        with torch.no_grad():
+            out = net.layers[-1]
+            out.weight[:64] = torch.randn(64, hidden_dim, generator=g) * (logit_std / hidden_dim ** 0.5)
+            out.weight[64:] = torch.randn(64 * action_dim, hidden_dim, generator=g) * (0.4 / hidden_dim ** 0.5)
+            out.bias.copy_(torch.randn(out.bias.shape, generator=g) * 0.1)
+            for p in net.parameters():
+                p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        return cls(net.to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, seed=policy_seed, uniform_fn=uniform_fn)
+
+
+# ------------------------------------------------------------------------------------------------ BC-GPT: the minGPT trunk with a regression head
+class GPTBCPolicy(BeTPolicy):
+    """Gpt_Agent.predict (agents/gpt_bc_agent.py:221-247) on a batch: scaled observation window (deque maxlen W; the window GROWS at episode start), the minGPT
+    trunk - the BeT library's GPT with vocab_size = action_dim (agents/models/transformer/gpt_policy.py), so ``ln_f`` and a BIAS-FREE head of A rows - and at every
+    lane's last token the tail: ln_f, the head, clamp to the data bounds IN SCALED SPACE (the f32 output against the f64 bounds: the same as against their f32
+    roundings), inverse scaling as an f64 product and sum on the f32 scale and shift, rounded to f32 once (the reference's output scaler is f64).  No random numbers;
+    the step word is advanced all the same (the protocol of NativePolicy).
+
+    The window handling is BeTPolicy's, inherited: ``_History``, the lockstep and the right-padded path, ``begin_episodes``, the fixed-shape chain of a capture and the
+    blocks' packed weights.  On a HIP device the tail is one kernel (csrc/policy_gpt_bc.h through d3il_gpt_bc_head_f32; C <= 128, A <= 16); on the CPU, for other
+    shapes and with D3IL_POLICY_GPT_BC_HEAD=0 the same arithmetic as torch ops (``_tail_torch``).  A lane with a NaN / Inf in its hidden row, its normalised row or
+    a head output gets NaN in every action component (``last_bad``)."""
+
+    SWITCH, LAST = "D3IL_POLICY_GPT_BC_HEAD", ("last_bad",)
+
+    def __init__(self, trunk: MinGPTTrunk, scaler: Scaler, window_size: int, seed: int = 0):
+        self.trunk, self.scaler, self.W = trunk.eval(), scaler, int(window_size)
+        dev = scaler.x_mean.device
+        self.device = dev
+        f = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.A = int(trunk.head.weight.shape[0])
+        assert trunk.head.bias is None and trunk.block_size >= self.W
+        self.min_action, self.max_action = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        assert self.min_action.numel() == self.A, "one bound per head row"
+        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self._init_stream(seed)
+        self.hist = None
+        self._static = False          # fixed-shape chain with device-only state (set by capture_snapshot)
+        self.last_bad = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, device=None):
+        """From a live reference ``Gpt_Agent`` (duck-typed): ``agent.model.model.model.state_dict()`` (the GPT), ``agent.scaler`` (its ``y_bounds`` are the clamp),
+        ``agent.window_size``."""
+        mingpt = agent.model.model
+        sd = mingpt.model.state_dict()
+        dev = torch.device(device) if device is not None else sd["tok_emb.weight"].device
+        n_embd, input_dim = sd["tok_emb.weight"].shape
+        n_layer = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        n_head = int(getattr(mingpt, "n_head", 0) or mingpt.model.blocks[0].attn.n_head)
+        trunk = MinGPTTrunk(input_dim, n_embd, n_layer, n_head, sd["pos_emb"].shape[1], sd["head.weight"].shape[0], 0)
+        trunk.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+        trunk = trunk.to(dev)
+        for p in trunk.parameters():
+            p.requires_grad_(False)
+        sc = agent.scaler
+        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        return cls(trunk, scaler, int(agent.window_size), seed=seed)
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: a Gpt_Agent around GptPolicy / MinGPT with continuous input, an ``nn.Identity`` observation encoder, no
+        visual input, a bias-free head of one row per action component and a scaler with bounds?  Everything else stays on the row-by-row adapter."""
+        try:
+            pol = agent.model
+            if type(agent).__name__ != "Gpt_Agent" or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None or getattr(pol, "visual_input", False):
+                return False
+            if type(pol.obs_encoder) is not nn.Identity:
+                return False
+            gpt = pol.model.model
+            sd = gpt.state_dict()
+            if "head.bias" in sd or "tok_emb.bias" not in sd or sd["tok_emb.weight"].dim() != 2 or "ln_f.weight" not in sd:
+                return False
+            A = sd["head.weight"].shape[0]
+            W = int(agent.window_size)
+            return 1 <= A == int(np.asarray(agent.scaler.y_bounds).shape[1]) and 1 <= W <= sd["pos_emb"].shape[1] and sd["head.weight"].shape[1] == sd["tok_emb.weight"].shape[0]
+        except (AttributeError, TypeError, ValueError, IndexError, KeyError):
+            return False
+
+    # ---- the tail
+    def head_kernel_ok(self, h) -> bool:
+        C = h.shape[-1]
+        return h.is_cuda and h.dtype == torch.float32 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 16 and self.trunk.head.weight.dtype == torch.float32 and self._switch_on()
+
+    def _tail_torch(self, h):
+        """Steps 1 - 3 of csrc/policy_gpt_bc.h as torch ops in the dtype of ``h`` and the parameters (f32 in the policy; the tests run it in f64 too)."""
+        dt, dev = h.dtype, h.device
+        x = self.trunk.ln_f(h)
+        o = F.linear(x, self.trunk.head.weight)
+        d = lambda v: v.to(device=dev, dtype=torch.float64)
+        y = (torch.minimum(torch.maximum(o, self.min_action.to(dev, dt)), self.max_action.to(dev, dt)).double() * d(self.out_scale) + d(self.out_shift)).to(dt)
+        bad = ~(torch.isfinite(h).all(dim=1) & torch.isfinite(x).all(dim=1) & torch.isfinite(o).all(dim=1))
+        self.last_bad = bad.to(torch.int32)
+        return torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+
+    def _tail_kernel(self, h):
+        from . import capi
+        n, C = h.shape
+        h = h.contiguous()
+        dev = h.device
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        bad = torch.empty(n, dtype=torch.int32, device=dev)
+        ln, w = self.trunk.ln_f, self.trunk.head.weight
+        assert w.is_contiguous()
+        capi.check(capi.load().d3il_gpt_bc_head_f32(h.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w.data_ptr(), self.min_action.data_ptr(),
+                                                    self.max_action.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), y.data_ptr(), bad.data_ptr(), n, C, self.A,
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+        self.last_bad = bad
+        return y
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, n_embd: int = 120, n_layer: int = 6, n_head: int = 6, window_size: int = 5,
+               action_scale: float = 0.002, policy_seed: int = 0, head_gain: float = 1.0, bound: float = 1.5):
+        """A BC-GPT policy of the reference's shape (n_embd 72 or 120, window 1 or 5) with fixed random weights - there are no checkpoints offline: torch's default
+        layer initialisation, head rows that give outputs of about ``head_gain`` in the scaled space, unit observation scaling, actions of ``action_scale`` per unit
+        of the scaled space, bounds +-``bound``."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            trunk = MinGPTTrunk(obs_dim, n_embd, n_layer, n_head, window_size, action_dim, 0)
+        with torch.no_grad():
+            trunk.pos_emb.copy_(torch.randn(trunk.pos_emb.shape, generator=g) * 0.1)
+            trunk.head.weight.copy_(torch.randn(action_dim, n_embd, generator=g) * (head_gain / n_embd ** 0.5))
+        for p in trunk.parameters():
+            p.requires_grad_(False)
+        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        return cls(trunk.to(device), sc, window_size, seed=policy_seed)
+
+
 # ------------------------------------------------------------------------------------------------ DDPM-ACT: encoder-decoder diffusion sampler that emits action chunks
 DDPM_ACT_TAG = 0x44410000     # fourth Philox counter word of the chain kernel, or-ed with k << 8 | j << 1 | q (csrc/policy_ddpm_act.h; never 0, never a word of the five tags above)
 

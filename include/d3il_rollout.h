@@ -318,6 +318,29 @@ int d3il_ddpm_act_chunk_f32(const float* window, const int64_t* len, const float
 int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out,
                          const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device,
                          const float* z_in, float* actions, float* z_out, long n_env, int obs_dim, int latent, int A, int hidden, int n_blocks, void* stream);
+/* The whole inference of the batched BeT-MLP policy (policies.BeTMLPPolicy; bet_mlp_agent.py:366-406 around generate_latents, 114-147, and k_means.py
+ * decode_actions) in one launch, f32: per environment h = the input layer and the residual blocks of the ResidualMLPNetwork (Mish) on the scaled state row,
+ * logit_v = w_out[v] . h + b_out[v] for v < 64, p = exp(logit - max) with inclusive prefix sums c and S = c_63, u = u_in[n] or 24 bits of Philox4x32-10 (key = seed,
+ * counter = (env_offset + n, *t_device, 0x424D4C50)), bins[n] = min(#{v : c_v <= u S}, 63), off_a = w_out[64 + bin A + a] . h + b_out[64 + bin A + a] (layout
+ * "(V A)"), actions[n][a] = clamp(centers[bin][a] + off_a, lo_a, hi_a) scale_a + shift_a (sum and clamp in f32; product and sum in f64, rounded once).
+ * state [n_env][obs_dim] (scaled); w_in, b_in, w_blocks, b_blocks as d3il_resmlp_f32 (input layer packed to 32 columns); w_logit: rows 0 .. 63 of the output layer
+ * packed like d3il_resmlp_f32's w_out tiles, [4][NT][64][4] (NT = hidden / 16; policies.pack_bet_mlp_weights), b_logit [64]; w_off: rows 64 .. of the output layer
+ * row-major [64 A][hidden], b_off [64 A]; centers [64][A]; lo / hi (scaled space) / scale / shift [A]; t_device: DEVICE u32, read only.  u_in [n_env], u_out [n_env]
+ * (the uniform that was used) and probs [n_env][64] (p / S) may be NULL.  An environment with a NaN / Inf in its state row, in its final hidden row or in a logit
+ * gets bins = -1 and NaN in every action component; no other environment changes.  Built for hidden 128 / 256, V = 64, 1 <= obs_dim <= 28, 1 <= A <= 8,
+ * n_blocks >= 0: D3IL_EUNSUPPORTED otherwise, answered before any launch.  Packed arrays, biases and w_off 16-byte aligned. */
+int d3il_bet_mlp_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_logit, const float* b_logit,
+                     const float* w_off, const float* b_off, const float* centers, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed,
+                     uint64_t env_offset, const uint32_t* t_device, const float* u_in, float* actions, int32_t* bins, float* u_out, float* probs, long n_env, int obs_dim,
+                     int V, int A, int hidden, int n_blocks, void* stream);
+/* The tail of the batched BC-GPT policy (policies.GPTBCPolicy; gpt_bc_agent.py:221-247 around gpt_policy.py MinGPT) in one launch: per row x = LayerNorm(h)
+ * (biased variance), o_a = w_head[a] . x (no bias), actions[row][a] = clamp(o_a, lo_a, hi_a) scale_a + shift_a (clamp in f32; product and sum in f64, rounded once).
+ * h [rows][C] (the last block's output at every environment's last token, before ln_f); ln_weight / ln_bias [C]; w_head [A][C] row-major; lo / hi (scaled space) /
+ * scale / shift [A]; bad i32 [rows] (may be NULL): 1 for a row with a NaN / Inf in h, in the normalised row or in a head output - it gets NaN in every action
+ * component -, 0 for every other one.  No other row changes.  No random numbers.  Built for C <= 128 (a multiple of 4) and 1 <= A <= 16: D3IL_EUNSUPPORTED otherwise,
+ * answered before any launch. */
+int d3il_gpt_bc_head_f32(const float* h, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_head, const float* lo, const float* hi, const float* scale,
+                         const float* shift, float* actions, int32_t* bad, long rows, int C, int A, void* stream);
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
