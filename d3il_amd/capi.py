@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 from .model.blob import ModelBlob
 
 _LIB = None
@@ -52,6 +54,43 @@ EXPORTS = ["d3il_create", "d3il_destroy", "d3il_start", "d3il_reset", "d3il_step
            "d3il_rccl_available", "d3il_comm_unique_id", "d3il_comm_init", "d3il_comm_count", "d3il_comm_destroy", "d3il_reduce_metrics", "d3il_set_timing",
            "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_group_create", "d3il_group_flush", "d3il_group_destroy", "d3il_group_set_option", "d3il_group_stats", "d3il_group_pipeline_stats", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_debug_build_flags", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
 
+# The policy kernel entries: parameter names in the order of include/d3il_rollout.h, ``name`` a pointer, ``name:i`` int, ``:l`` long, ``:f`` float, ``:q`` uint64_t,
+# ``:u`` uint32_t.  load() derives the argtypes from it, launch() the keywords it demands; tests/test_capi_signatures.py holds it against the header.
+_CTYPES = {"": C.c_void_p, "i": C.c_int, "l": C.c_long, "f": C.c_float, "q": C.c_uint64, "u": C.c_uint32}
+_RESMLP = "w_in b_in w_blocks b_blocks"
+_TAIL = "lo hi scale shift"
+_DRAW = _TAIL + " seed:q env_offset:q t_device"
+_LN = "ln_weight ln_bias ln_eps:f"
+_MLP = "h " + _LN + " x w_packed b1 b2 out rows:l C:i H:i"
+_LINEAR = "xin " + _LN + " w_packed bias resid out rows:l N:i"
+_ENCDEC = "w_in tab enc_w enc_v dec_w dec_v head_w " + _DRAW
+SIGNATURES = {name: tuple((a.partition(":")[0], _CTYPES[a.partition(":")[2]]) for a in (spec + " stream").split()) for name, spec in {
+    "d3il_attention_causal_f32": "qkv out B:i T:i H:i D:i",
+    "d3il_layernorm_f32": "x weight bias y rows:l C:i eps:f",
+    "d3il_linear120_f32": _LINEAR,
+    "d3il_mlp_gelu_residual_f32": "h x w_packed b1 b2 out rows:l C:i H:i",
+    "d3il_mlp_ln_gelu_residual_f32": _MLP,
+    "d3il_mlp_ln_gelu_residual_f16x3": _MLP,
+    "d3il_linear120_f16x3": _LINEAR,
+    "d3il_attn_half_f16x3": "x " + _LN + " w_packed b_qkv b_proj out n_seq:l T:i n_head:i C:i",
+    "d3il_ddpm_mlp_f32": "state noise temb " + _RESMLP + " w_out b_out sched bounds out rows:l state_dim:i n_timesteps:i hidden:i n_blocks:i",
+    "d3il_resmlp_f32": "x " + _RESMLP + " w_out b_out out rows:l in_dim:i hidden:i n_blocks:i out_dim:i",
+    "d3il_bet_head_f32": "h " + _LN + " w_head centers " + _DRAW + " u_in actions bins u_out probs rows:l C:i V:i A:i",
+    "d3il_ddpm_gpt_step_f32": "hk " + _LN + " w_pred b_pred w_aemb bias_pos temb sched " + _TAIL + " len seed:q env_offset:q t_device noise_in x xbuf actions bad noise_out "
+                              "n_env:l C:i A:i W:i T:i k:i",
+    "d3il_ibc_langevin_f32": "state " + _RESMLP + " w_out b_out wT_blocks wT_in_act coef noise_scale:f lo hi clip scale shift seed:q env_offset:q t_device x0_in noise_in u_in "
+                             "actions picks x_final energies x0_out noise_out u_out n_env:l obs_dim:i A:i hidden:i n_blocks:i S:i K:i",
+    "d3il_act_chunk_f32": "state " + _ENCDEC + " latent_in counter chunk actions latent_out n_env:l obs_dim:i A:i T:i width:i n_head:i latent:i n_enc:i n_dec:i",
+    "d3il_ddpm_act_chunk_f32": "window len " + _ENCDEC + " noise_in x_in counter chunk actions bad x_out noise_out n_env:l obs_dim:i A:i obs_seq_len:i action_seq_len:i "
+                               "width:i n_head:i n_enc:i n_dec:i n_timesteps:i linear_head:i k_start:i k_stop:i",
+    "d3il_cvae_decode_f32": "state " + _RESMLP + " w_out b_out " + _DRAW + " z_in actions z_out n_env:l obs_dim:i latent:i A:i hidden:i n_blocks:i",
+    "d3il_bet_mlp_f32": "state " + _RESMLP + " w_logit b_logit w_off b_off centers " + _DRAW + " u_in actions bins u_out probs n_env:l obs_dim:i V:i A:i hidden:i n_blocks:i",
+    "d3il_gpt_bc_head_f32": "h " + _LN + " w_head " + _TAIL + " actions bad rows:l C:i A:i",
+}.items()}
+# what launch() works from, resolved once per entry: the keywords it demands (everything but the stream), the same as a set, the positions of the pointers
+_LAUNCH = {name: (tuple(n for n, _ in sig[:-1]), frozenset(n for n, _ in sig[:-1]), tuple(i for i, (_, t) in enumerate(sig[:-1]) if t is C.c_void_p))
+           for name, sig in SIGNATURES.items()}
+
 
 class D3ilError(RuntimeError):
     pass
@@ -85,23 +124,10 @@ def load():
         L.d3il_policy_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.d3il_policy_action.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.d3il_count_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.d3il_attention_causal_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.d3il_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_void_p]
-        L.d3il_mlp_ln_gelu_residual_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]
-        L.d3il_linear120_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
-        L.d3il_mlp_ln_gelu_residual_f16x3.argtypes = L.d3il_mlp_ln_gelu_residual_f32.argtypes
-        L.d3il_linear120_f16x3.argtypes = L.d3il_linear120_f32.argtypes
-        L.d3il_attn_half_f16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        for name, sig in SIGNATURES.items():
+            if hasattr(L, name):      # (an older build loaded through D3IL_LIB_PATH lacks the newest entries: skipped, not an error)
+                getattr(L, name).argtypes = [t for _, t in sig]
         L.d3il_f16x3_set_guard.argtypes = [C.c_void_p]
-        L.d3il_bet_head_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 6 + [C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.d3il_ddpm_gpt_step_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 11 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 7 + [C.c_long] + [C.c_int] * 5 + [C.c_void_p]
-        L.d3il_ibc_langevin_f32.argtypes = [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 11 + [C.c_long] + [C.c_int] * 6 + [C.c_void_p]
-        L.d3il_act_chunk_f32.argtypes = [C.c_void_p] * 12 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 6 + [C.c_long] + [C.c_int] * 8 + [C.c_void_p]
-        L.d3il_ddpm_act_chunk_f32.argtypes = [C.c_void_p] * 13 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 9 + [C.c_long] + [C.c_int] * 12 + [C.c_void_p]
-        L.d3il_cvae_decode_f32.argtypes = [C.c_void_p] * 11 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 4 + [C.c_long] + [C.c_int] * 5 + [C.c_void_p]
-        L.d3il_ddpm_mlp_f32.argtypes = [C.c_void_p] * 12 + [C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.d3il_resmlp_f32.argtypes = [C.c_void_p] * 8 + [C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.d3il_mlp_gelu_residual_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]
         L.d3il_auto_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.d3il_step_auto_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.d3il_random_rollout_step.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -120,9 +146,6 @@ def load():
         L.d3il_debug_scratch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.d3il_debug_build_flags.argtypes = [C.c_void_p]
         L.d3il_set_link_guard.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
-        if hasattr(L, "d3il_bet_mlp_f32"):      # (the parent build loaded through D3IL_LIB_PATH has neither the BeT-MLP kernel nor the BC-GPT head)
-            L.d3il_bet_mlp_f32.argtypes = [C.c_void_p] * 14 + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 6 + [C.c_long] + [C.c_int] * 5 + [C.c_void_p]
-            L.d3il_gpt_bc_head_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 7 + [C.c_long, C.c_int, C.c_int, C.c_void_p]
         if hasattr(L, "d3il_group_create"):      # (an older build loaded through D3IL_LIB_PATH has no step group: has_step_group())
             L.d3il_group_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
             L.d3il_group_flush.argtypes = [C.c_void_p]
@@ -162,6 +185,24 @@ def is_unknown_group_option(err: Exception) -> bool:
 def check(rc: int):
     if rc != 0:
         raise D3ilError("libd3il_rollout error %d: %s" % (rc, load().d3il_last_error().decode()))
+
+
+def launch(name: str, device, **args):
+    """Call the policy kernel entry ``name`` of SIGNATURES by keyword on the current stream of ``device``: exactly the header's parameter names but ``stream``
+    (TypeError naming the missing / unknown ones, or a tensor on another device, before the library is touched); a pointer parameter takes a tensor, which goes as its
+    data_ptr(), or None for NULL, numbers go as they are; a non-zero return code raises D3ilError."""
+    names, keys, pointers = _LAUNCH[name]
+    if args.keys() != keys:
+        raise TypeError("%s: missing arguments %s, unknown arguments %s" % (name, sorted(keys - args.keys()), sorted(args.keys() - keys)))
+    where = -1 if device.type == "cpu" else torch.cuda.current_device() if device.index is None else device.index      # what Tensor.get_device() says there
+    vals = [args[k] for k in names]
+    for i in pointers:      # (this loop runs once per eager policy step: an integer compare per tensor, no device objects)
+        v = vals[i]
+        if v is not None:
+            if v.get_device() != where:
+                raise TypeError("%s: %s is on %s, the launch is on %s" % (name, names[i], v.device, device))
+            vals[i] = v.data_ptr()
+    check(getattr(load(), name)(*vals, torch.cuda.current_stream(device).cuda_stream))
 
 
 _CAPSULES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "model", "blobs", "panda_link_capsules.json")

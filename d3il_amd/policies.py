@@ -39,6 +39,16 @@ class Scaler:
         self.x_mean, self.x_std, self.y_mean, self.y_std = f(x_mean), f(x_std), f(y_mean), f(y_std)
         self.y_bounds = None if y_bounds is None else f(y_bounds)
 
+    @classmethod
+    def from_reference(cls, sc, device, bounds_optional: bool = False):
+        """A reference agent's scaler on ``device``; ``bounds_optional``: one without ``y_bounds`` is taken too (BeTPolicy gets its bounds from the agent)."""
+        return cls(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, getattr(sc, "y_bounds", None) if bounds_optional else sc.y_bounds, device=device)
+
+    @classmethod
+    def unit(cls, obs_dim: int, action_dim: int, action_scale: float, bound: float, device):
+        """The scaler of the ``random()`` policies: observations as they are, actions of ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
+        return cls([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+
     def scale_input(self, x):
         return ((x - self.x_mean) / (self.x_std + 1e-12)).to(torch.float32)
 
@@ -92,7 +102,43 @@ class ResidualMLP(FusedResMLPHook, nn.Module):
         self.layers = nn.ModuleList([nn.Linear(input_dim, hidden_dim)] + [_ResBlock(hidden_dim) for _ in range(1, num_hidden_layers, 2)] + [nn.Linear(hidden_dim, output_dim)])
 
     def _parts(self):
-        return (self.layers[0], [(b.l1, b.l2) for b in self.layers[1:-1]], self.layers[-1])
+        layers = list(self.layers)      # (a slice of a ModuleList builds a new ModuleList: 10 us in every eager step of the policies that ask for the parts)
+        return (layers[0], [(b.l1, b.l2) for b in layers[1:-1]], layers[-1])
+
+    @classmethod
+    def from_reference_state(cls, sd, device=None):
+        """The network of a reference ``ResidualMLPNetwork.state_dict()`` - widths and block count read from the keys -, loaded, on ``device`` (default: where the
+        state dict lives), frozen."""
+        sd = {k: torch.as_tensor(v) for k, v in sd.items()}
+        hidden, in_dim = sd["layers.0.weight"].shape
+        last = max(int(k.split(".")[1]) for k in sd)
+        net = cls(in_dim, hidden, 2 * len({k.split(".")[1] for k in sd if ".l1." in k}), sd["layers.%d.weight" % last].shape[0])
+        net.load_state_dict(sd)
+        return net.to(torch.device(device) if device is not None else sd["layers.0.weight"].device).requires_grad_(False)
+
+    @staticmethod
+    def is_plain(layers, strict: bool) -> bool:
+        """Are the ``layers`` of a reference ResidualMLPNetwork what this class restates: plain ``nn.Linear`` layers without spectral norm around Mish blocks without
+        norm?  ``strict`` (CVAE, BeT-MLP): no subclass of nn.Linear, every layer with a bias, square blocks of the input layer's width."""
+        blocks = layers[1:-1]
+        lins = [layers[0], layers[-1]] + [l for b in blocks for l in (b.l1, b.l2)]
+        if not all(isinstance(l, nn.Linear) and not hasattr(l, "weight_orig") for l in lins) or not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in blocks):
+            return False
+        H = layers[0].out_features
+        return not strict or (len(layers) >= 2 and all(type(l) is nn.Linear and l.bias is not None for l in lins) and layers[-1].in_features == H
+                              and all(l.in_features == H and l.out_features == H for l in lins[2:]))
+
+    @classmethod
+    def random(cls, input_dim, hidden_dim, n_blocks, output_dim, seed: int, weight_gain: float = 1.0):
+        """Fixed random weights for the ``random()`` policies: torch's default layer initialisation under ``seed`` (the global generator is left alone) times
+        ``weight_gain``, frozen."""
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            net = cls(input_dim, hidden_dim, 2 * n_blocks, output_dim)
+        with torch.no_grad():
+            for p in net.parameters():
+                p.mul_(weight_gain)
+        return net.requires_grad_(False)
 
     def forward(self, x):
         x = x.to(torch.float32)
@@ -150,7 +196,7 @@ class _CausalSelfAttention(nn.Module):     # score_gpts.py:15-80
             bqkv = torch.cat((self.query.bias, self.key.bias, self.value.bias), dim=0)
             qkv = F.linear(x, w, bqkv).contiguous()
             y = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
-            capi.check(capi.load().d3il_attention_causal_f32(qkv.data_ptr(), y.data_ptr(), B, T, self.n_head, hd, torch.cuda.current_stream(x.device).cuda_stream))
+            capi.launch("d3il_attention_causal_f32", x.device, qkv=qkv, out=y, B=B, T=T, H=self.n_head, D=hd)
             return self.proj(y)
         k = self.key(x).view(B, T, self.n_head, hd).transpose(1, 2)
         q = self.query(x).view(B, T, self.n_head, hd).transpose(1, 2)
@@ -168,8 +214,7 @@ def _layer_norm(ln: nn.LayerNorm, x):
     if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and 4 <= C <= 128 and C % 4 == 0 and x.data_ptr() % 16 == 0:
         from . import capi
         y = torch.empty_like(x)
-        capi.check(capi.load().d3il_layernorm_f32(x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), y.data_ptr(), x.numel() // C, C, float(ln.eps),
-                                                 torch.cuda.current_stream(x.device).cuda_stream))
+        capi.launch("d3il_layernorm_f32", x.device, x=x, weight=ln.weight, bias=ln.bias, y=y, rows=x.numel() // C, C=C, eps=float(ln.eps))
         return y
     return ln(x)
 
@@ -489,41 +534,37 @@ class _Block(nn.Module):                   # score_gpts.py:83-115
             # LayerNorms, biases, GELU and residuals fused in: ln1 + (query | key | value) product -> causal attention -> output projection + residual -> ln2 + fc1 + GELU + fc2 + residual
             # (the [B T][480] hidden activations stay in registers)
             from . import capi
-            L = capi.load()
-            st = torch.cuda.current_stream(x.device).cuda_stream
+            dev = x.device
             B, T, C = x.shape
             M = B * T
             a = self.attn
             w = self._packed.current(self._pack_params(), self._pack)
             f16x3 = policy_gemm_mode() == "f16x3"
             if f16x3 and not _ENV_GUARD_TRIED:
-                _env_range_guard(x.device)
-            linear = L.d3il_linear120_f16x3 if f16x3 else L.d3il_linear120_f32
-            mlp = L.d3il_mlp_ln_gelu_residual_f16x3 if f16x3 else L.d3il_mlp_ln_gelu_residual_f32
+                _env_range_guard(dev)
+            linear, mlp = ("d3il_linear120_f16x3", "d3il_mlp_ln_gelu_residual_f16x3") if f16x3 else ("d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f32")
             w_qkv, w_proj, w_mlp = (w["hp_qkv"], w["hp_proj"], w["hp_mlp"]) if f16x3 else (w["wp_qkv"], w["wp_proj"], w["wp_mlp"])
+            ln1 = dict(ln_weight=self.ln1.weight, ln_bias=self.ln1.bias, ln_eps=float(self.ln1.eps))
             if f16x3 and T <= 16 and a.n_head == 6 and w["hp_attn"].shape[0] == 32 and os.environ.get("D3IL_POLICY_FUSED_ATTN", "1") == "1":
                 # the attention half in ONE launch, one wave per sequence: q | k | v and the attention output never leave the CU (csrc/policy_f16x3.h k_attn_half_f16x3)
                 x1 = torch.empty_like(x)
-                capi.check(L.d3il_attn_half_f16x3(x.data_ptr(), self.ln1.weight.data_ptr(), self.ln1.bias.data_ptr(), float(self.ln1.eps), w["hp_attn"].data_ptr(),
-                                                  w["b_qkv"].data_ptr(), a.proj.bias.data_ptr(), x1.data_ptr(), B, T, a.n_head, C, st))
+                capi.launch("d3il_attn_half_f16x3", dev, x=x, **ln1, w_packed=w["hp_attn"], b_qkv=w["b_qkv"], b_proj=a.proj.bias, out=x1, n_seq=B, T=T, n_head=a.n_head, C=C)
                 if keep is not None:
                     x1 = x1.index_select(1, keep)
                     M = x1.shape[0] * x1.shape[1]
             else:
-                qkv = torch.empty(B, T, 3 * C, dtype=torch.float32, device=x.device)
-                capi.check(linear(x.data_ptr(), self.ln1.weight.data_ptr(), self.ln1.bias.data_ptr(), float(self.ln1.eps), w_qkv.data_ptr(), w["b_qkv"].data_ptr(), None,
-                                  qkv.data_ptr(), M, 3 * C, st))
+                qkv = torch.empty(B, T, 3 * C, dtype=torch.float32, device=dev)
+                capi.launch(linear, dev, xin=x, **ln1, w_packed=w_qkv, bias=w["b_qkv"], resid=None, out=qkv, rows=M, N=3 * C)
                 y = torch.empty_like(x)
-                capi.check(L.d3il_attention_causal_f32(qkv.data_ptr(), y.data_ptr(), B, T, a.n_head, C // a.n_head, st))
+                capi.launch("d3il_attention_causal_f32", dev, qkv=qkv, out=y, B=B, T=T, H=a.n_head, D=C // a.n_head)
                 if keep is not None:
                     y, x = y.index_select(1, keep), x.index_select(1, keep)
                     M = y.shape[0] * y.shape[1]
                 x1 = torch.empty_like(x)
-                capi.check(linear(y.data_ptr(), None, None, 0.0, w_proj.data_ptr(), a.proj.bias.data_ptr(), x.data_ptr(), x1.data_ptr(), M, C, st))
-            fc1, fc2 = self.mlp[0], self.mlp[2]
+                capi.launch(linear, dev, xin=y, ln_weight=None, ln_bias=None, ln_eps=0.0, w_packed=w_proj, bias=a.proj.bias, resid=x, out=x1, rows=M, N=C)
             out = torch.empty_like(x1)
-            capi.check(mlp(x1.data_ptr(), self.ln2.weight.data_ptr(), self.ln2.bias.data_ptr(), float(self.ln2.eps), x1.data_ptr(), w_mlp.data_ptr(),
-                           fc1.bias.data_ptr(), fc2.bias.data_ptr(), out.data_ptr(), M, 120, 480, st))
+            capi.launch(mlp, dev, h=x1, ln_weight=self.ln2.weight, ln_bias=self.ln2.bias, ln_eps=float(self.ln2.eps), x=x1, w_packed=w_mlp, b1=self.mlp[0].bias,
+                        b2=self.mlp[2].bias, out=out, rows=M, C=120, H=480)
             return out
         x = x + self.attn(_layer_norm(self.ln1, x))
         if keep is not None:
@@ -719,6 +760,11 @@ def pack_resmlp_weights(lin_in, blocks, lin_out, in_cols: int = 32) -> dict:
     return {"w_in": f(w_in), "b_in": f(lin_in.bias), "w_blk": f(w_blk), "b_blk": f(b_blk), "w_out": f(w_out), "b_out": f(bo), "n_blocks": len(blocks)}
 
 
+def resmlp_args(w) -> dict:
+    """The packed input layer and blocks under the parameter names the kernel entries give them (include/d3il_rollout.h)."""
+    return dict(w_in=w["w_in"], b_in=w["b_in"], w_blocks=w["w_blk"], b_blocks=w["b_blk"])
+
+
 class FusedResMLP:
     """The device path of a ResidualMLPNetwork (csrc/policy_f32.h k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
     ``parts`` = (lin_in, [(l1, l2), ..], lin_out) of the module it serves (no reference to the module is kept).  Non-finite input: a row of x with a NaN / Inf comes
@@ -751,13 +797,12 @@ class FusedResMLP:
 
     def __call__(self, x, parts):
         from . import capi
-        lib = capi.load()
         lin_in, blocks, lin_out = parts
         w = self._packed.current(*self._pack_args(parts))
         x = x.to(torch.float32).contiguous()
         out = torch.empty(x.shape[0], lin_out.out_features, dtype=torch.float32, device=x.device)
-        capi.check(lib.d3il_resmlp_f32(x.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_out"].data_ptr(), w["b_out"].data_ptr(),
-                                       out.data_ptr(), x.shape[0], lin_in.in_features, lin_in.out_features, w["n_blocks"], lin_out.out_features, torch.cuda.current_stream(x.device).cuda_stream))
+        capi.launch("d3il_resmlp_f32", x.device, x=x, **resmlp_args(w), w_out=w["w_out"], b_out=w["b_out"], out=out, rows=x.shape[0], in_dim=lin_in.in_features,
+                    hidden=lin_in.out_features, n_blocks=w["n_blocks"], out_dim=lin_out.out_features)
         return out
 
 
@@ -908,16 +953,13 @@ class DDPMPolicy:
 
     def _sample_fused(self, state):
         from . import capi
-        lib = capi.load()
         n, sd = state.shape
         w = self._packed.current(list(self.model.parameters()), self._pack)
         shape = (n, 2)
         noise = torch.stack([self.noise_fn(shape) for _ in range(self.T + 1)]).to(torch.float32).contiguous() if self._custom_noise else torch.randn((self.T + 1, n, 2), device=self.device)
         out = torch.empty(n, 2, dtype=torch.float32, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        state = state.contiguous()
-        capi.check(lib.d3il_ddpm_mlp_f32(state.data_ptr(), noise.data_ptr(), w["temb"].data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(),
-                                         w["w_out"].data_ptr(), w["b_out"].data_ptr(), w["sched"].data_ptr(), w["bounds"].data_ptr(), out.data_ptr(), n, sd, self.T, 256, w["n_blocks"], st))
+        capi.launch("d3il_ddpm_mlp_f32", state.device, state=state.contiguous(), noise=noise, temb=w["temb"], **resmlp_args(w), w_out=w["w_out"], b_out=w["b_out"], sched=w["sched"],
+                    bounds=w["bounds"], out=out, rows=n, state_dim=sd, n_timesteps=self.T, hidden=256, n_blocks=w["n_blocks"])
         return out
 
     def fork(self):
@@ -1181,17 +1223,37 @@ def _tag_axes(*sizes):
     return [np.arange(s, dtype=np.uint64).reshape((1,) * (i + 1) + (s,) + (1,) * (len(sizes) - 1 - i)) for i, s in enumerate(sizes)]
 
 
+def _first_parameter(module):
+    """``next(module.parameters())`` without the generator chain of nn.Module (this runs in every eager policy step)."""
+    for p in module._parameters.values():
+        if p is not None:
+            return p
+    for child in module._modules.values():
+        p = _first_parameter(child)
+        if p is not None:
+            return p
+    return None
+
+
 class NativePolicy:
-    """What the Sims, SubBatchSet and CapturedPolicy call on a policy that draws from the Philox stream above, written once.  A subclass has ``model`` (the
-    network), ``device``, calls ``_init_stream(seed)`` in its constructor and states
+    """What the Sims, SubBatchSet and CapturedPolicy call on a policy that draws from the Philox stream above, and the steps every such policy takes, written
+    once.  A subclass has ``model`` (the network), ``scaler``, ``device`` and ``obs_dim``, calls ``_init_output(scaler)`` and ``_init_stream(seed)`` in its
+    constructor and states
       SWITCH   the D3IL_POLICY_* variable that turns its kernel off ("0": the torch path, which the tests compare the kernel against);
       STATE    the names of its per-lane device tensors (None until ``_state(n)`` has sized them);  ``hist``, a _History or None, is per-lane state too;
       LAST     the names of the ``last_*`` records a fork starts without;
+      TAKES    what reads the observation row, for the width check ("the decoder takes %d next to its latent");
+      BOUNDS   the attribute names of its clamp bounds (BeT, BC-GPT and DDPM-GPT say ``min_action`` / ``max_action``);
       _state(n)                 make the per-lane state fit n lanes (default: there is none);
-      _pack_params() / _pack()  the parameters its packed tables follow and the packer, for PackedWeights; _kernel_shape() where only some networks are packed.
+      _kernel_shape()           is the network one its kernel is built for?  Only then is it packed and launched;
+      _pack()                   the packer for PackedWeights (_pack_params(): the parameters the tables follow, default all of the model's);
+      _step_kernel(s)           one step on the scaled observations s [N, obs_dim] through its row of capi.SIGNATURES (capi.launch, by name);
+      _step_torch(s)            the same arithmetic as torch ops (``_draw`` for the random numbers, ``_action_tail`` for the end);
+      _fallback_text()          what the once-per-policy warning says when the kernel is on and does not apply.
+    ``predict_batch`` is then the template below; a policy that drives a trunk between its history and its tail (BeT, DDPM-GPT) writes its own.
     The step word ``_t`` lives on the device (the kernels read it as u32); a captured graph advances it at every replay."""
 
-    SWITCH, STATE, LAST = None, (), ()
+    SWITCH, STATE, LAST, TAKES, BOUNDS = None, (), (), "the network takes %d", ("lo", "hi")
     hist = None
 
     def _init_stream(self, seed):
@@ -1199,7 +1261,18 @@ class NativePolicy:
         self._t = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._packed = PackedWeights()
 
+    def _init_output(self, scaler, lo=None, hi=None):
+        """The constants of the action tail, f32 on the device: the clamp bounds in scaled space (default: the scaler's ``y_bounds``) under the names BOUNDS, and
+        ``out_scale`` / ``out_shift`` of the inverse scaling."""
+        f = lambda a: torch.as_tensor(a).detach().to(device=self.device, dtype=torch.float32).contiguous()
+        setattr(self, self.BOUNDS[0], f(scaler.y_bounds[0] if lo is None else lo))
+        setattr(self, self.BOUNDS[1], f(scaler.y_bounds[1] if hi is None else hi))
+        self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
+
     def _state(self, n):
+        pass
+
+    def reset(self):
         pass
 
     def _kernel_shape(self) -> bool:
@@ -1207,6 +1280,30 @@ class NativePolicy:
 
     def _switch_on(self) -> bool:
         return os.environ.get(self.SWITCH, "1") == "1"
+
+    def _pack_params(self):
+        return list(self.model.parameters())
+
+    def fused_ok(self, s) -> bool:
+        w = _first_parameter(self.model)
+        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
+
+    def _draw_args(self) -> dict:
+        """The keywords every drawing kernel takes: tail constants, Philox key, rollout offset, step word."""
+        return dict(lo=getattr(self, self.BOUNDS[0]), hi=getattr(self, self.BOUNDS[1]), scale=self.out_scale, shift=self.out_shift, seed=self.seed, env_offset=self.env_offset, t_device=self._t)
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "%s: observation width %d, %s" % (type(self).__name__, s.shape[-1], self.TAKES % self.obs_dim)
+        self._state(s.shape[0])
+        if self.fused_ok(s):
+            y = self._step_kernel(s)
+        else:
+            self._warn_fallback(s, self._fallback_text)
+            y = self._step_torch(s)
+        self._t.add_(1)
+        return y
 
     def set_rollout_range(self, offset, count):
         """Rows 0 .. count-1 of this policy's batch are rollouts offset .. offset+count-1: the Philox counter of row i is env_offset + i."""
@@ -1259,11 +1356,70 @@ class NativePolicy:
             raise RuntimeError("%s: the torch path draws its Philox numbers on the host and cannot be captured; the kernel draws on the device" % type(self).__name__)
         return int(self._t.item()) & 0xFFFFFFFF
 
+    def _draw(self, given_fn, n, shape, host_draw, need_host: bool, dev):
+        """A bank of random numbers, f32 ``shape`` on ``dev``, as the torch path takes it / as the kernel is handed it: ``given_fn(n)`` where the policy was given
+        one, or (``need_host``) ``host_draw(step word)`` - the host form of the kernel's own draw -, or None: the kernel draws."""
+        if given_fn is not None:
+            return torch.as_tensor(given_fn(n), dtype=torch.float32).to(dev).reshape(shape).contiguous()
+        if not need_host:
+            return None
+        return torch.as_tensor(host_draw(self._host_step_word()), dtype=torch.float32).to(dev)
+
+    def _action_tail(self, x, bad, f64: bool, lo=None, hi=None, dt=None):
+        """The end of every torch path: clamp ``x`` [N, .., A] to [lo, hi] in its dtype (None: the caller has clamped, or there is no clamp), scale and shift, NaN
+        for the rows marked in ``bad`` [N].  ``f64``: the product and the sum in f64, rounded once to ``dt`` (default: the dtype of x) - what the kernels of CVAE,
+        BeT-MLP, BC-GPT and IBC do; otherwise both in ``dt``, rounded twice - BeT, DDPM-GPT, ACT, DDPM-ACT."""
+        dt = x.dtype if dt is None else dt
+        if lo is not None:
+            x = torch.minimum(torch.maximum(x, lo.to(x.device, x.dtype)), hi.to(x.device, x.dtype))
+        wide = torch.float64 if f64 else dt
+        y = (x.to(wide) * self.out_scale.to(x.device, wide) + self.out_shift.to(x.device, wide)).to(dt)
+        return torch.where(bad.bool().reshape((-1,) + (1,) * (y.dim() - 1)), torch.full_like(y, float("nan")), y)
+
     def _warn_fallback(self, s, text):
         """Once per policy (forks copy the flag): the kernel is switched on, the input is on the device, and this network is not one it is built for."""
         if s.is_cuda and self._switch_on() and not getattr(self, "_warned", False):
             self._warned = True
             warnings.warn("%s: %s" % (type(self).__name__, text()))
+
+
+class _ChunkLanes:
+    """The per-lane bookkeeping of the policies that emit action chunks (ACT, DDPM-ACT), in front of NativePolicy: ``counter`` i32 [N] and ``chunk`` f32
+    [N, chunk length, A] (clamped, inverse-scaled) on the device.  A lane whose counter equals the chunk length (or lies outside 0 .. length) is due."""
+
+    def _chunk_state(self, n, length):
+        self.counter = torch.full((n,), length, dtype=torch.int32, device=self.device)
+        self.chunk = torch.zeros(n, length, self.A, dtype=torch.float32, device=self.device)
+
+    def _due(self):
+        return (self.counter >= self.chunk.shape[1]) | (self.counter < 0)
+
+    def _emit(self):
+        """chunk[counter] of every lane; the counters count on."""
+        y = self.chunk[torch.arange(self.chunk.shape[0], device=self.chunk.device), self.counter.long()]
+        self.counter.add_(1)
+        return y
+
+    def reset(self):
+        """The agent's reset for every lane: empty windows, the next call computes a chunk everywhere."""
+        if self.counter is not None:
+            self.counter.fill_(self.chunk.shape[1])
+            if self.hist is not None:
+                self.hist.reset()
+
+    def begin_episodes(self, mask):
+        """Lanes that start a new trajectory: window length 0, due at their next step (in place on the device, also under a captured graph)."""
+        self._state(int(mask.shape[0]))
+        m = mask.to(device=self.device, dtype=torch.bool).reshape(-1)
+        self.counter.masked_fill_(m, self.chunk.shape[1])
+        if self.hist is not None:
+            self.hist.reset_(m)
+
+    def predict_batch(self, obs):
+        y = super().predict_batch(obs)
+        if self.record:
+            self.last_chunk = self.chunk.clone()      # a copy of the chunk table after every call
+        return y
 
 
 # ------------------------------------------------------------------------------------------------ Behaviour Transformer
@@ -1332,8 +1488,7 @@ class BeTPolicy(NativePolicy):
         self.centers = f(bin_centers)
         self.V, self.A = int(self.centers.shape[0]), int(self.centers.shape[1])
         assert trunk.head.weight.shape[0] == self.V * (1 + self.A), "the head has V (1 + A) outputs"
-        self.min_action, self.max_action = f(min_action), f(max_action)
-        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self._init_output(scaler, min_action, max_action)
         self._init_stream(seed)
         self.uniform_fn = uniform_fn
         self.hist = None
@@ -1356,12 +1511,8 @@ class BeTPolicy(NativePolicy):
         n_head = int(getattr(mingpt, "n_head", 0) or mingpt.model.blocks[0].attn.n_head)
         trunk = MinGPTTrunk(input_dim, n_embd, n_layer, n_head, sd["pos_emb"].shape[1], V, A)
         trunk.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
-        trunk = trunk.to(dev)
-        for p in trunk.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, getattr(sc, "y_bounds", None), device=dev)
-        return cls(trunk, centers, scaler, agent.min_action, agent.max_action, int(agent.window_size), seed=seed, uniform_fn=uniform_fn)
+        trunk = trunk.to(dev).requires_grad_(False)
+        return cls(trunk, centers, Scaler.from_reference(agent.scaler, dev, bounds_optional=True), agent.min_action, agent.max_action, int(agent.window_size), seed=seed, uniform_fn=uniform_fn)
 
     @staticmethod
     def matches(agent) -> bool:
@@ -1373,7 +1524,7 @@ class BeTPolicy(NativePolicy):
             return False
 
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
-    SWITCH, LAST = "D3IL_POLICY_BET_HEAD", ("last_bins", "last_u", "last_probs", "last_logits")
+    SWITCH, LAST, BOUNDS = "D3IL_POLICY_BET_HEAD", ("last_bins", "last_u", "last_probs", "last_logits"), ("min_action", "max_action")
     model = property(lambda self: self.trunk)
 
     @property
@@ -1424,10 +1575,8 @@ class BeTPolicy(NativePolicy):
         return (h.is_cuda and h.dtype == torch.float32 and self.V == 64 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 8 and self.trunk.head.weight.dtype == torch.float32
                 and self._switch_on())
 
-    def _uniforms(self, n, dev):
-        if self.uniform_fn is not None:
-            return torch.as_tensor(self.uniform_fn(n), dtype=torch.float32).to(dev).reshape(n).contiguous()
-        return torch.as_tensor(bet_uniforms(self.seed, self.env_offset, n, self._host_step_word())).to(dev)
+    def _uniforms(self, n, dev, need_host: bool = True):
+        return self._draw(self.uniform_fn, n, (n,), lambda t: bet_uniforms(self.seed, self.env_offset, n, t), need_host, dev)
 
     def _tail_torch(self, h):
         """Steps 1 - 7 of csrc/policy_bet.h as torch ops, in the kernel's order of operations where the order is defined (S is the last prefix sum)."""
@@ -1442,9 +1591,8 @@ class BeTPolicy(NativePolicy):
         bins = (c <= u.unsqueeze(1) * S).sum(dim=1).clamp_max(V - 1)
         rows = V + bins.unsqueeze(1) * A + torch.arange(A, device=h.device)
         off = (w[rows] * x.unsqueeze(1)).sum(dim=2)
-        y = torch.clamp(self.centers[bins] + off, self.min_action, self.max_action) * self.out_scale + self.out_shift
         bad = ~torch.isfinite(h).all(dim=1)
-        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        y = self._action_tail(torch.clamp(self.centers[bins] + off, self.min_action, self.max_action), bad, f64=False)
         self.last_bins, self.last_u = torch.where(bad, torch.full_like(bins, -1), bins).to(torch.int32), u
         if self.record:
             self.last_logits, self.last_probs = logits, p / S
@@ -1459,13 +1607,10 @@ class BeTPolicy(NativePolicy):
         bins = torch.empty(n, dtype=torch.int32, device=dev)
         u_out = torch.empty(n, dtype=torch.float32, device=dev)
         probs = torch.empty(n, self.V, dtype=torch.float32, device=dev) if self.record else None
-        u_in = self._uniforms(n, dev) if self.uniform_fn is not None else None
         ln, w = self.trunk.ln_f, self.trunk.head.weight
-        assert w.is_contiguous() and self._t.device == dev
-        capi.check(capi.load().d3il_bet_head_f32(h.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w.data_ptr(), self.centers.data_ptr(),
-                                                 self.min_action.data_ptr(), self.max_action.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(),
-                                                 self.seed, self.env_offset, self._t.data_ptr(), None if u_in is None else u_in.data_ptr(), y.data_ptr(), bins.data_ptr(),
-                                                 u_out.data_ptr(), None if probs is None else probs.data_ptr(), n, C, self.V, self.A, torch.cuda.current_stream(dev).cuda_stream))
+        assert w.is_contiguous()
+        capi.launch("d3il_bet_head_f32", dev, h=h, ln_weight=ln.weight, ln_bias=ln.bias, ln_eps=float(ln.eps), w_head=w, centers=self.centers, **self._draw_args(),
+                    u_in=self._uniforms(n, dev, False), actions=y, bins=bins, u_out=u_out, probs=probs, rows=n, C=C, V=self.V, A=self.A)
         self.last_bins, self.last_u, self.last_probs, self.last_logits = bins, u_out, probs, None
         return y
 
@@ -1511,10 +1656,8 @@ class BeTPolicy(NativePolicy):
             trunk.pos_emb.copy_(torch.randn(trunk.pos_emb.shape, generator=g) * 0.1)
             trunk.head.weight[:64] = torch.randn(64, n_embd, generator=g) * (2.0 / n_embd ** 0.5)
             trunk.head.weight[64:] = torch.randn(64 * action_dim, n_embd, generator=g) * (0.4 / n_embd ** 0.5)
-        for p in trunk.parameters():
-            p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
-        return cls(trunk.to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, sc.y_bounds[0], sc.y_bounds[1], window_size, seed=policy_seed, uniform_fn=uniform_fn)
+        sc = Scaler.unit(obs_dim, action_dim, action_scale, 1.5, device)
+        return cls(trunk.requires_grad_(False).to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, sc.y_bounds[0], sc.y_bounds[1], window_size, seed=policy_seed, uniform_fn=uniform_fn)
 
 
 # ------------------------------------------------------------------------------------------------ DDPM with the transformer denoiser
@@ -1603,9 +1746,7 @@ class DDPMGPTPolicy(NativePolicy):
         self.A = int(model.action_dim)
         sch = ddpm_schedule(cosine_beta_schedule(self.T).to(dev))
         self.sqrt_recip_ac, self.sqrt_recipm1_ac, self.post_logvar, self.coef1, self.coef2, self._sched = (sch[k] for k in ("sqrt_recip_ac", "sqrt_recipm1_ac", "post_logvar", "coef1", "coef2", "sched"))
-        f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
-        self.min_action, self.max_action = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
-        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self._init_output(scaler)
         self._init_stream(seed)
         self.noise_in = noise_in
         self.hist = None
@@ -1627,12 +1768,8 @@ class DDPMGPTPolicy(NativePolicy):
         n_heads = int(net.blocks[0].attn.n_head)
         den = DiffusionGPTDenoiser(state_dim, A, C, n_layers, n_heads, sd["pos_emb"].shape[1] - 1, linear_output="action_pred.weight" in sd)
         den.load_state_dict(sd)
-        den = den.to(dev)
-        for p in den.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
-        pol = cls(den, scaler, int(diff.n_timesteps), int(agent.window_size), seed=seed, noise_in=noise_in)
+        den = den.to(dev).requires_grad_(False)
+        pol = cls(den, Scaler.from_reference(agent.scaler, dev), int(diff.n_timesteps), int(agent.window_size), seed=seed, noise_in=noise_in)
         if getattr(agent, "use_ema", False):
             pol.use_ema(agent.ema_helper.shadow_params)
         return pol
@@ -1659,7 +1796,7 @@ class DDPMGPTPolicy(NativePolicy):
             return False
 
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
-    SWITCH, LAST = "D3IL_POLICY_DDPM_GPT_STEP", ("last_bad", "last_noise")
+    SWITCH, LAST, BOUNDS = "D3IL_POLICY_DDPM_GPT_STEP", ("last_bad", "last_noise"), ("min_action", "max_action")
 
     @property
     def f16x3_blocks(self) -> bool:
@@ -1721,9 +1858,8 @@ class DDPMGPTPolicy(NativePolicy):
 
     def _noise(self, k, n, dev):
         """The normals of chain index k as the torch path takes them: ``noise_in(k, n)`` or the host form of the kernel's Philox draw."""
-        if self.noise_in is not None:
-            return torch.as_tensor(self.noise_in(k, n), dtype=torch.float32).to(dev).reshape(n, self.W, self.A).contiguous()
-        return torch.as_tensor(ddpm_gpt_normals(self.seed, self.env_offset, n, self._host_step_word(), k, self.W, self.A), dtype=torch.float32).to(dev)
+        return self._draw(self.noise_in and (lambda n: self.noise_in(k, n)), n, (n, self.W, self.A),
+                          lambda t: ddpm_gpt_normals(self.seed, self.env_offset, n, t, k, self.W, self.A), True, dev)
 
     def _step_torch(self, st, k, hk):
         """Steps 1 - 8 of csrc/policy_ddpm_gpt.h as torch ops, in the kernel's order of operations, on the chain state ``st`` (x, xbuf, bad, lengths, packed tables)."""
@@ -1754,8 +1890,7 @@ class DDPMGPTPolicy(NativePolicy):
             xbuf[:, 2::2] = w["bias_pos"] + xp @ m.action_emb.weight.t()
         else:
             last = xp.gather(1, (ln - 1).view(n, 1, 1).expand(-1, 1, self.A)).squeeze(1)
-            y = torch.minimum(torch.maximum(last, self.min_action), self.max_action) * self.out_scale + self.out_shift
-            st["actions"].copy_(torch.where(st["bad"].bool().unsqueeze(1), torch.full_like(y, float("nan")), y))
+            st["actions"].copy_(self._action_tail(last, st["bad"], False, self.min_action, self.max_action))
 
     def _step_kernel(self, st, k, hk):
         from . import capi
@@ -1763,14 +1898,12 @@ class DDPMGPTPolicy(NativePolicy):
         n = st["x"].shape[0]
         noise_in = self._noise(k, n, dev) if self.noise_in is not None else None
         noise_out = torch.empty(n, self.W, self.A, dtype=torch.float32, device=dev) if self.record else None
-        ptr = lambda v: None if v is None else v.data_ptr()
         assert hk is None or hk.is_contiguous()
-        assert m.action_pred.weight.is_contiguous() and m.action_emb.weight.is_contiguous() and self._t.device == dev
-        capi.check(capi.load().d3il_ddpm_gpt_step_f32(ptr(hk), m.ln_f.weight.data_ptr(), m.ln_f.bias.data_ptr(), float(m.ln_f.eps), m.action_pred.weight.data_ptr(),
-                                                      m.action_pred.bias.data_ptr(), m.action_emb.weight.data_ptr(), w["bias_pos"].data_ptr(), w["temb"].data_ptr(), w["sched"].data_ptr(),
-                                                      self.min_action.data_ptr(), self.max_action.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), st["len"].data_ptr(),
-                                                      self.seed, self.env_offset, self._t.data_ptr(), ptr(noise_in), st["x"].data_ptr(), st["xbuf"].data_ptr(), st["actions"].data_ptr(),
-                                                      st["bad"].data_ptr(), ptr(noise_out), n, m.embed_dim, self.A, self.W, self.T, k, torch.cuda.current_stream(dev).cuda_stream))
+        assert m.action_pred.weight.is_contiguous() and m.action_emb.weight.is_contiguous()
+        capi.launch("d3il_ddpm_gpt_step_f32", dev, hk=hk, ln_weight=m.ln_f.weight, ln_bias=m.ln_f.bias, ln_eps=float(m.ln_f.eps), w_pred=m.action_pred.weight,
+                    b_pred=m.action_pred.bias, w_aemb=m.action_emb.weight, bias_pos=w["bias_pos"], temb=w["temb"], sched=w["sched"], **self._draw_args(), len=st["len"],
+                    noise_in=noise_in, x=st["x"], xbuf=st["xbuf"], actions=st["actions"], bad=st["bad"], noise_out=noise_out, n_env=n, C=m.embed_dim, A=self.A, W=self.W,
+                    T=self.T, k=k)
         if self.record:
             self.last_noise[k] = noise_out
 
@@ -1819,10 +1952,7 @@ class DDPMGPTPolicy(NativePolicy):
             den.pos_emb.copy_(torch.randn(den.pos_emb.shape, generator=g) * 0.1)
             if linear_output:
                 den.action_pred.weight.copy_(torch.randn(den.action_pred.weight.shape, generator=g) * (1.0 / embed_dim ** 0.5))
-        for p in den.parameters():
-            p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
-        return cls(den.to(device), sc, n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)
+        return cls(den.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, 1.5, device), n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)
 
 
 # ------------------------------------------------------------------------------------------------ Implicit BC: Langevin chain on an energy network
@@ -1927,9 +2057,9 @@ class IBCPolicy(NativePolicy):
         self.steps = [float(v) for v in steps]
         self.noise_scale, self.delta_action_clip = float(noise_scale), float(delta_action_clip)
         f = lambda a: a.to(device=dev, dtype=torch.float32).contiguous()
-        self.lo, self.hi, self.clip = f(b[0]), f(b[1]), f(self.delta_action_clip * 0.5 * (b[1] - b[0]))      # (the clip in f64 from the f64 bounds, as the reference)
+        self._init_output(scaler, b[0], b[1])
+        self.clip = f(self.delta_action_clip * 0.5 * (b[1] - b[0]))      # (the clip in f64 from the f64 bounds, as the reference)
         self.coef = f(torch.tensor([[v * 0.5, v] for v in self.steps], dtype=torch.float64).reshape(self.K, 2))
-        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
         self._init_stream(seed)
         self.n_envs, self.x0_in, self.noise_in, self.u_in = n_envs, x0_in, noise_in, u_in
         self.record = False           # also keep the chain's start points, noise, final samples and energies (last_x0, last_noise, last_x, last_energies)
@@ -1941,17 +2071,8 @@ class IBCPolicy(NativePolicy):
         """From a live reference ``IBCAgent`` (duck-typed): ``agent.model.mlp.state_dict()``, ``agent.sampler``'s settings and f64 bounds, ``agent.scaler``; with
         ``agent.use_ema`` the EMA shadow parameters (the reference swaps them in for every predict)."""
         mlp, smp = agent.model.mlp, agent.sampler
-        sd = {k: torch.as_tensor(v) for k, v in mlp.state_dict().items()}
-        dev = torch.device(device) if device is not None else sd["layers.0.weight"].device
-        hidden, in_dim = sd["layers.0.weight"].shape
-        n_blocks = len({k.split(".")[1] for k in sd if ".l1." in k})
-        net = ResidualMLP(in_dim, hidden, 2 * n_blocks, 1)
-        net.load_state_dict(sd)
-        net = net.to(dev)
-        for p in net.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        net = ResidualMLP.from_reference_state(mlp.state_dict(), device)
+        scaler = Scaler.from_reference(agent.scaler, net.layers[0].weight.device)
         steps = ibc_step_sizes(smp.inference_iterations, smp.sampler_stepsize_init_infer, smp.sampler_stepsize_init, smp.sampler_stepsize_final, smp.sampler_stepsize_power,
                                smp.second_inference_stepsize_init, bool(smp.second_infer))
         pol = cls(net, scaler, steps, noise_scale=smp.noise_scale_infer, delta_action_clip=smp.delta_action_clip, samples=int(smp.inference_samples), seed=seed, n_envs=n_envs,
@@ -1972,10 +2093,7 @@ class IBCPolicy(NativePolicy):
             if agent.goal_conditioning is not False or type(ebm).__name__ != "EBMMLP" or not hasattr(agent, "scaler") or smp.bounds is None:
                 return False
             layers = list(ebm.mlp.layers)
-            lins = [layers[0], layers[-1]] + [l for b in layers[1:-1] for l in (b.l1, b.l2)]
-            if not all(isinstance(l, nn.Linear) and not hasattr(l, "weight_orig") for l in lins) or layers[-1].out_features != 1:
-                return False
-            if not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in layers[1:-1]):
+            if not ResidualMLP.is_plain(layers, strict=False) or layers[-1].out_features != 1:
                 return False
             K = int(smp.inference_iterations) * (2 if smp.second_infer else 1)
             return int(smp.inference_iterations) >= 2 and K <= 63 and 1 <= int(smp.inference_samples) <= 64 and 1 <= smp.bounds.shape[1] <= 8
@@ -1984,18 +2102,13 @@ class IBCPolicy(NativePolicy):
 
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
     SWITCH, LAST = "D3IL_POLICY_IBC_FUSED", ("last_picks", "last_u", "last_x0", "last_noise", "last_x", "last_energies")
-
-    def reset(self):
-        pass
+    TAKES = "the energy network takes %d"
 
     def load_reference_state_dict(self, sd):
         """``EBMMLP.state_dict()`` of the reference: the network sits under ``mlp.``."""
         self.model.load_state_dict({k[len("mlp."):]: v for k, v in sd.items() if k.startswith("mlp.")})
 
     # ---- packed tables
-    def _pack_params(self):
-        return list(self.model.parameters())
-
     def _pack(self):
         """pack_resmlp_weights of the network; the same packer on the transposed square layers (``wT_blk``) and on the action columns of the input layer as a
         16-row output tile (``wT_act``: row a = W_in[:, obs + a])."""
@@ -2009,29 +2122,18 @@ class IBCPolicy(NativePolicy):
         return out
 
     # ---- the chain
-    def fused_ok(self, s) -> bool:
+    def _kernel_shape(self) -> bool:
         lin_in, blocks, _ = self.model._parts()
-        w = lin_in.weight
-        return (s.is_cuda and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and len(blocks) <= 4 and lin_in.in_features <= 28
-                and self.S == 64 and self._switch_on())
+        return lin_in.out_features in (128, 256) and len(blocks) <= 4 and lin_in.in_features <= 28 and self.S == 64
 
     def _banks(self, n, dev, need_host: bool):
         """(x0, noise, u) as the torch path takes them / as the kernel is handed them: the given banks, or (``need_host``) the host form of the kernel's draws."""
-        f = lambda v, shape: torch.as_tensor(v, dtype=torch.float32).to(dev).reshape(shape).contiguous()
-        x0 = f(self.x0_in(n), (n, self.S, self.A)) if self.x0_in is not None else None
-        nz = f(self.noise_in(n), (self.K, n, self.S, self.A)) if self.noise_in is not None else None
-        u = f(self.u_in(n), (n,)) if self.u_in is not None else None
-        if need_host and (x0 is None or nz is None or u is None):
-            t = self._host_step_word()
-            if x0 is None:
-                uu = torch.as_tensor(ibc_start_uniforms(self.seed, self.env_offset, n, t, self.A, self.S)).to(dev)
-                x0 = self.lo + uu * (self.hi - self.lo)
-            if nz is None:
-                nz = f(np.stack([ibc_normals(self.seed, self.env_offset, n, t, k, self.A, self.S) for k in range(self.K)]) if self.K else np.zeros((0, n, self.S, self.A)),
-                       (self.K, n, self.S, self.A))
-            if u is None:
-                u = torch.as_tensor(ibc_pick_uniforms(self.seed, self.env_offset, n, t)).to(dev)
-        return x0, nz, u
+        S, A, K, draw = self.S, self.A, self.K, lambda fn, shape, host: self._draw(fn, n, shape, host, need_host, dev)
+        x0 = draw(self.x0_in, (n, S, A), lambda t: ibc_start_uniforms(self.seed, self.env_offset, n, t, A, S))
+        if x0 is not None and self.x0_in is None:
+            x0 = self.lo + x0 * (self.hi - self.lo)
+        nz = draw(self.noise_in, (K, n, S, A), lambda t: np.stack([ibc_normals(self.seed, self.env_offset, n, t, k, A, S) for k in range(K)]) if K else np.zeros((0, n, S, A)))
+        return x0, nz, draw(self.u_in, (n,), lambda t: ibc_pick_uniforms(self.seed, self.env_offset, n, t))
 
     def _chain_torch(self, s, x0=None, noise=None, u=None):
         """Steps 1 - 3 of csrc/policy_ibc.h as torch ops in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too): returns
@@ -2056,45 +2158,34 @@ class IBCPolicy(NativePolicy):
         p = torch.exp(-(e - e.min(dim=1, keepdim=True).values))
         cdf = torch.cumsum(p, dim=1)
         picks = (cdf <= c(u).unsqueeze(1) * cdf[:, -1:]).sum(dim=1).clamp_max(S - 1)
-        y = (x[torch.arange(n, device=s.device), picks] * d(self.out_scale) + d(self.out_shift)).to(dt)
-        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        y = self._action_tail(x[torch.arange(n, device=s.device), picks], bad, f64=True, dt=dt)
         return y, torch.where(bad, torch.full_like(picks, -1), picks).to(torch.int32), x.to(dt), e
 
-    def _chain_kernel(self, s):
+    def _step_torch(self, s):
+        x0, nz, u = self._banks(s.shape[0], s.device, True)
+        y, self.last_picks, self.last_x, self.last_energies = self._chain_torch(s, x0, nz, u)
+        self.last_u, self.last_x0, self.last_noise = u, x0, nz
+        return y
+
+    def _step_kernel(self, s):
         from . import capi
         n, dev, S, A, K = s.shape[0], s.device, self.S, self.A, self.K
         w = self._packed.current(self._pack_params(), self._pack)
         x0, nz, u = self._banks(n, dev, False)
         new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
         y, picks, u_out = new(n, A), new(n, dtype=torch.int32), new(n)
-        rec = self.record
-        xf, en, x0o, nzo = (new(n, S, A), new(n, S), new(n, S, A), new(K, n, S, A)) if rec else (None, None, None, None)
-        ptr = lambda v: None if v is None else v.data_ptr()
+        xf, en, x0o, nzo = (new(n, S, A), new(n, S), new(n, S, A), new(K, n, S, A)) if self.record else (None, None, None, None)
         lin_in, blocks, _ = self.model._parts()
-        assert s.is_contiguous() and self._t.device == dev
-        capi.check(capi.load().d3il_ibc_langevin_f32(s.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_out"].data_ptr(),
-                                                     w["b_out"].data_ptr(), w["wT_blk"].data_ptr(), w["wT_act"].data_ptr(), self.coef.data_ptr(), self.noise_scale, self.lo.data_ptr(),
-                                                     self.hi.data_ptr(), self.clip.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed, self.env_offset,
-                                                     self._t.data_ptr(), ptr(x0), ptr(nz), ptr(u), y.data_ptr(), picks.data_ptr(), ptr(xf), ptr(en), ptr(x0o), ptr(nzo), u_out.data_ptr(),
-                                                     n, self.obs_dim, A, lin_in.out_features, len(blocks), S, K, torch.cuda.current_stream(dev).cuda_stream))
+        capi.launch("d3il_ibc_langevin_f32", dev, state=s, **resmlp_args(w), w_out=w["w_out"], b_out=w["b_out"], wT_blocks=w["wT_blk"], wT_in_act=w["wT_act"], coef=self.coef,
+                    noise_scale=self.noise_scale, clip=self.clip, **self._draw_args(), x0_in=x0, noise_in=nz, u_in=u, actions=y, picks=picks, x_final=xf, energies=en,
+                    x0_out=x0o, noise_out=nzo, u_out=u_out, n_env=n, obs_dim=self.obs_dim, A=A, hidden=lin_in.out_features, n_blocks=len(blocks), S=S, K=K)
         self.last_picks, self.last_u, self.last_x, self.last_energies, self.last_x0, self.last_noise = picks, u_out, xf, en, x0o, nzo
         return y
 
-    @torch.no_grad()
-    def predict_batch(self, obs):
-        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
-        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "IBCPolicy: observation width %d, the energy network takes %d" % (s.shape[-1], self.obs_dim)
-        if self.fused_ok(s):
-            y = self._chain_kernel(s)
-        else:
-            self._warn_fallback(s, lambda: "this network (hidden %d, %d blocks, %d inputs, %d samples) is not one the chain kernel is built for; every call runs the torch chain "
-                                "with its Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
-                                % (self.model._parts()[0].out_features, len(self.model._parts()[1]), self.model._parts()[0].in_features, self.S))
-            x0, nz, u = self._banks(s.shape[0], s.device, True)
-            y, self.last_picks, self.last_x, self.last_energies = self._chain_torch(s, x0, nz, u)
-            self.last_u, self.last_x0, self.last_noise = u, x0, nz
-        self._t.add_(1)
-        return y
+    def _fallback_text(self):
+        lin_in, blocks, _ = self.model._parts()
+        return ("this network (hidden %d, %d blocks, %d inputs, %d samples) is not one the chain kernel is built for; every call runs the torch chain "
+                "with its Philox numbers drawn on the host (a device synchronisation per call, no graph capture)" % (lin_in.out_features, len(blocks), lin_in.in_features, self.S))
 
     @classmethod
     def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, action_scale: float = 0.002, policy_seed: int = 0,
@@ -2102,14 +2193,7 @@ class IBCPolicy(NativePolicy):
         """A policy of the reference's shape with fixed random weights (there are no checkpoints offline) and the shipped sampler settings of
         configs/agents/ibc_agent.yaml (64 samples, 10 + 10 iterations, step sizes 0.5 / 0.0493 -> 1e-5 with power 2, then 1e-5; noise scale 0.5; clip 0.1): torch's
         default layer initialisation times ``weight_gain``, unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-1.5."""
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(seed)
-            net = ResidualMLP(obs_dim + action_dim, hidden_dim, 2 * n_blocks, 1)
-        with torch.no_grad():
-            for p in net.parameters():
-                p.mul_(weight_gain)
-                p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-1.5] * action_dim, [1.5] * action_dim], device=device)
+        net, sc = ResidualMLP.random(obs_dim + action_dim, hidden_dim, n_blocks, 1, seed, weight_gain), Scaler.unit(obs_dim, action_dim, action_scale, 1.5, device)
         return cls(net.to(device), sc, ibc_step_sizes(10, 0.5, 0.0493, 1e-5, 2.0, 1e-5, True), noise_scale=0.5, delta_action_clip=0.1, seed=policy_seed, **kw)
 
 
@@ -2289,7 +2373,7 @@ def pack_act_weights(net: ActNet) -> dict:
             "enc_w": torch.stack(enc_w), "enc_v": torch.stack(enc_v), "dec_w": torch.stack(dec_w), "dec_v": torch.stack(dec_v), "head_w": flat(pack_tiles(net.action_head.weight))}
 
 
-class ACTPolicy(NativePolicy):
+class ACTPolicy(_ChunkLanes, NativePolicy):
     """ActAgent.predict without goals (agents/act_agent.py:207-239) around ActVAE.forward without actions (act_vae.py:389-445), on a batch: scale the observation;
     a lane whose ``counter`` equals the chunk length T is due and computes a new chunk of T actions from its CURRENT observation and a fresh uniform latent -
     clamped to the scaler's bounds in the scaled space, inverse-scaled, stored -; every lane then emits chunk[counter] and counts on.  ``reset()`` makes all lanes
@@ -2308,9 +2392,7 @@ class ACTPolicy(NativePolicy):
         self.device = dev
         self.T, self.A, self.obs_dim = int(model.T), int(model.A), int(model.obs_dim)
         assert scaler.y_bounds is not None and tuple(scaler.y_bounds.shape) == (2, self.A), "ACTPolicy clamps to the scaler's y_bounds"
-        f = lambda a: a.detach().to(device=dev, dtype=torch.float32).contiguous()
-        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
-        self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
+        self._init_output(scaler)
         self._init_stream(seed)
         self.n_envs, self.latent_in = n_envs, latent_in
         self.counter = self.chunk = self.last_latent = None          # per-lane state: i32 [N], f32 [N, T, A] (clamped, inverse-scaled), the latent of the lane's chunk [N, 32]
@@ -2329,8 +2411,7 @@ class ACTPolicy(NativePolicy):
         layers = lambda p: len({k.split(".")[2] for k in sd if k.startswith(p + ".blocks.")})
         net = ActNet(obs, sd["action_head.weight"].shape[0], sd["query_embed.weight"].shape[0], hidden_dim=C, n_heads=int(agent.model.encoder.blocks[0].attn.n_head),
                      enc_layers=layers("encoder"), dec_layers=layers("decoder"), latent_dim=sd["latent_out_proj.weight"].shape[1])
-        sc = agent.scaler
-        pol = cls(net.to(dev), Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev), seed=seed, n_envs=n_envs, latent_in=latent_in)
+        pol = cls(net.to(dev), Scaler.from_reference(agent.scaler, dev), seed=seed, n_envs=n_envs, latent_in=latent_in)
         pol.load_reference_state_dict(sd)
         return pol
 
@@ -2375,24 +2456,13 @@ class ACTPolicy(NativePolicy):
 
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
     SWITCH, STATE, LAST = "D3IL_POLICY_ACT_FUSED", ("counter", "chunk", "last_latent"), ("last_chunk",)
+    TAKES = "the state encoder takes %d"
 
     def _state(self, n):
         """counter / chunk / last_latent for n lanes; a new size starts with every lane due."""
         if self.counter is None or self.counter.shape[0] != n:
-            dev = self.device
-            self.counter = torch.full((n,), self.T, dtype=torch.int32, device=dev)
-            self.chunk = torch.zeros(n, self.T, self.A, dtype=torch.float32, device=dev)
-            self.last_latent = torch.zeros(n, self.model.latent_dim, dtype=torch.float32, device=dev)
-
-    def reset(self):
-        """ActAgent.reset for every lane: the next call computes a chunk everywhere."""
-        if self.counter is not None:
-            self.counter.fill_(self.T)
-
-    def begin_episodes(self, mask):
-        """Lanes that start a new trajectory are due at their next step (in place on the device, also under a captured graph)."""
-        self._state(int(mask.shape[0]))
-        self.counter.masked_fill_(mask.to(device=self.device, dtype=torch.bool), self.T)
+            self._chunk_state(n, self.T)
+            self.last_latent = torch.zeros(n, self.model.latent_dim, dtype=torch.float32, device=self.device)
 
     def load_reference_state_dict(self, sd):
         """``ActVAE.state_dict()`` of the reference: a plain load of the keys the inference path has (masks and the training-only modules are ignored)."""
@@ -2400,10 +2470,6 @@ class ACTPolicy(NativePolicy):
         self.model.load_state_dict({k: torch.as_tensor(sd[k]).to(own[k].dtype) for k in own})
         for p in self.model.parameters():
             p.requires_grad_(False)
-
-    # ---- packed tables
-    def _pack_params(self):
-        return list(self.model.parameters())
 
     def _pack(self):
         return pack_act_weights(self.model)
@@ -2414,72 +2480,42 @@ class ACTPolicy(NativePolicy):
         return (m.C == 64 and m.n_head == 4 and m.latent_dim == 32 and m.obs_dim <= 32 and 1 <= m.A <= 8 and 1 <= m.T <= 8 and 1 <= len(m.encoder.blocks) <= 4
                 and 1 <= len(m.decoder.blocks) <= 8)
 
-    def fused_ok(self, s) -> bool:
-        w = self.model.state_encoder.weight
-        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
-
     def _latent(self, n, dev, need_host: bool):
-        """The latent as the torch path takes it / as the kernel is handed it: the given bank, or (``need_host``) the host form of the kernel's draw."""
-        if self.latent_in is not None:
-            return torch.as_tensor(self.latent_in(n), dtype=torch.float32).to(dev).reshape(n, self.model.latent_dim).contiguous()
-        if not need_host:
-            return None
-        return torch.as_tensor(act_latent_uniforms(self.seed, self.env_offset, n, self._host_step_word())).to(dev)
+        return self._draw(self.latent_in, n, (n, self.model.latent_dim), lambda t: act_latent_uniforms(self.seed, self.env_offset, n, t), need_host, dev)
 
     def _chunk_torch(self, s, z):
         """A new chunk for every row, in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too): network, clamp to the bounds in the
         scaled space, inverse scaling as two operations; rows with a NaN / Inf in the state or a head output are NaN."""
-        dt = s.dtype
-        c = lambda v: v.to(device=s.device, dtype=dt)
-        a_hat = self.model(s, c(z))
+        a_hat = self.model(s, z.to(device=s.device, dtype=s.dtype))
         bad = ~torch.isfinite(s).all(dim=1) | ~torch.isfinite(a_hat).reshape(s.shape[0], -1).all(dim=1)
-        y = torch.minimum(torch.maximum(a_hat, c(self.lo)), c(self.hi)) * c(self.out_scale) + c(self.out_shift)
-        return torch.where(bad.reshape(-1, 1, 1), torch.full_like(y, float("nan")), y)
+        return self._action_tail(a_hat, bad, False, self.lo, self.hi)
 
     def _step_torch(self, s):
         if s.is_cuda and _capturing():
             raise RuntimeError("ACTPolicy: the torch path decides on the host which lanes are due and draws its Philox numbers there; it cannot be captured - the kernel can")
         n = s.shape[0]
-        due = (self.counter >= self.T) | (self.counter < 0)
+        due = self._due()
         if bool(due.any()):
             z = self._latent(n, s.device, True)
             new = self._chunk_torch(torch.where(due.unsqueeze(1), s, torch.zeros_like(s)), z)
             self.chunk.copy_(torch.where(due.reshape(-1, 1, 1), new, self.chunk))
             self.last_latent.copy_(torch.where(due.unsqueeze(1), z, self.last_latent))
             self.counter.masked_fill_(due, 0)
-        y = self.chunk[torch.arange(n, device=s.device), self.counter.long()]
-        self.counter.add_(1)
-        return y
+        return self._emit()
 
     def _step_kernel(self, s):
         from . import capi
         n, dev, m = s.shape[0], s.device, self.model
         w = self._packed.current(self._pack_params(), self._pack)
-        z = self._latent(n, dev, False)
         y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
-        assert s.is_contiguous() and self._t.device == dev and self.counter.device == dev
-        capi.check(capi.load().d3il_act_chunk_f32(s.data_ptr(), w["w_in"].data_ptr(), w["tab"].data_ptr(), w["enc_w"].data_ptr(), w["enc_v"].data_ptr(), w["dec_w"].data_ptr(),
-                                                  w["dec_v"].data_ptr(), w["head_w"].data_ptr(), self.lo.data_ptr(), self.hi.data_ptr(), self.out_scale.data_ptr(),
-                                                  self.out_shift.data_ptr(), self.seed, self.env_offset, self._t.data_ptr(), None if z is None else z.data_ptr(),
-                                                  self.counter.data_ptr(), self.chunk.data_ptr(), y.data_ptr(), self.last_latent.data_ptr(), n, self.obs_dim, self.A, self.T,
-                                                  m.C, m.n_head, m.latent_dim, len(m.encoder.blocks), len(m.decoder.blocks), torch.cuda.current_stream(dev).cuda_stream))
+        capi.launch("d3il_act_chunk_f32", dev, state=s, **w, **self._draw_args(), latent_in=self._latent(n, dev, False), counter=self.counter, chunk=self.chunk, actions=y,
+                    latent_out=self.last_latent, n_env=n, obs_dim=self.obs_dim, A=self.A, T=self.T, width=m.C, n_head=m.n_head, latent=m.latent_dim, n_enc=len(m.encoder.blocks),
+                    n_dec=len(m.decoder.blocks))
         return y
 
-    @torch.no_grad()
-    def predict_batch(self, obs):
-        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
-        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "ACTPolicy: observation width %d, the state encoder takes %d" % (s.shape[-1], self.obs_dim)
-        self._state(s.shape[0])
-        if self.fused_ok(s):
-            y = self._step_kernel(s)
-        else:
-            self._warn_fallback(s, lambda: "this network (width %d, %d heads, latent %d, T %d) is not one the chunk kernel is built for; every call runs the torch path "
-                                "with a device synchronisation per call and no graph capture" % (self.model.C, self.model.n_head, self.model.latent_dim, self.T))
-            y = self._step_torch(s)
-        if self.record:
-            self.last_chunk = self.chunk.clone()
-        self._t.add_(1)
-        return y
+    def _fallback_text(self):
+        return ("this network (width %d, %d heads, latent %d, T %d) is not one the chunk kernel is built for; every call runs the torch path "
+                "with a device synchronisation per call and no graph capture" % (self.model.C, self.model.n_head, self.model.latent_dim, self.T))
 
     @classmethod
     def random(cls, obs_dim: int, action_dim: int, act_seq_size: int = 3, device="cuda", seed: int = 0, enc_layers: int = 2, dec_layers: int = 4, hidden_dim: int = 64,
@@ -2489,10 +2525,7 @@ class ACTPolicy(NativePolicy):
         scaled space, bounds +-``bound``."""
         net = ActNet(obs_dim, action_dim, act_seq_size, hidden_dim, n_heads, enc_layers, dec_layers, latent_dim)
         net.load_state_dict({k: torch.as_tensor(v) for k, v in act_synthetic_state({k: v.shape for k, v in net.state_dict().items()}, seed).items()})
-        for p in net.parameters():
-            p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
-        return cls(net.to(device), sc, seed=policy_seed, **kw)
+        return cls(net.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, bound, device), seed=policy_seed, **kw)
 
 
 # ------------------------------------------------------------------------------------------------ conditional VAE: a clamped prior sample through the decoder
@@ -2536,9 +2569,7 @@ class CVAEPolicy(NativePolicy):
         self.obs_dim = int(lin_in.in_features) - self.L
         assert 1 <= self.L <= 32, "the Philox counter layout holds a latent of at most 32 components"
         assert self.obs_dim >= 1, "the decoder reads [state | latent]"
-        f = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous()
-        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
-        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self._init_output(scaler)
         self._init_stream(seed)
         self.n_envs, self.z_in = n_envs, z_in
         self.last_z = None
@@ -2548,19 +2579,8 @@ class CVAEPolicy(NativePolicy):
     def from_reference(cls, agent, seed: int = 0, n_envs: int | None = None, device=None, z_in=None):
         """From a live reference ``CVAEAgent`` (duck-typed): ``agent.model.decoder.state_dict()``, ``agent.model.latent_dim``, ``agent.scaler`` (its ``y_bounds`` are
         the clamp).  The encoder is left where it is."""
-        sd = {k: torch.as_tensor(v) for k, v in agent.model.decoder.state_dict().items()}
-        dev = torch.device(device) if device is not None else sd["layers.0.weight"].device
-        hidden, in_dim = sd["layers.0.weight"].shape
-        n_blocks = len({k.split(".")[1] for k in sd if ".l1." in k})
-        last = max(int(k.split(".")[1]) for k in sd)
-        net = ResidualMLP(in_dim, hidden, 2 * n_blocks, sd["layers.%d.weight" % last].shape[0])
-        net.load_state_dict(sd)
-        net = net.to(dev)
-        for p in net.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
-        return cls(net, scaler, int(agent.model.latent_dim), seed=seed, n_envs=n_envs, z_in=z_in)
+        net = ResidualMLP.from_reference_state(agent.model.decoder.state_dict(), device)
+        return cls(net, Scaler.from_reference(agent.scaler, net.layers[0].weight.device), int(agent.model.latent_dim), seed=seed, n_envs=n_envs, z_in=z_in)
 
     @staticmethod
     def matches(agent) -> bool:
@@ -2572,53 +2592,32 @@ class CVAEPolicy(NativePolicy):
             if type(agent).__name__ != "CVAEAgent" or type(vae).__name__ != "VariationalAE" or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None:
                 return False
             layers = list(vae.decoder.layers)
-            if len(layers) < 2 or not all(type(l) is nn.Linear for l in (layers[0], layers[-1])):
+            if not ResidualMLP.is_plain(layers, strict=True):
                 return False
-            blocks = layers[1:-1]
-            lins = [layers[0], layers[-1]] + [l for b in blocks for l in (b.l1, b.l2)]
-            if not all(type(l) is nn.Linear and not hasattr(l, "weight_orig") and l.bias is not None for l in lins):
-                return False
-            if not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in blocks):
-                return False
-            L, H = int(vae.latent_dim), layers[0].out_features
-            if not all(l.in_features == H and l.out_features == H for b in blocks for l in (b.l1, b.l2)) or layers[-1].in_features != H:
-                return False
+            L = int(vae.latent_dim)
             return 1 <= L <= 32 and L < layers[0].in_features <= 64 and 1 <= layers[-1].out_features <= 16
         except (AttributeError, TypeError, ValueError, IndexError):
             return False
 
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
-    SWITCH, LAST = "D3IL_POLICY_CVAE_FUSED", ("last_z",)
-
-    def reset(self):
-        pass
+    SWITCH, LAST, TAKES = "D3IL_POLICY_CVAE_FUSED", ("last_z",), "the decoder takes %d next to its latent"
 
     def load_reference_state_dict(self, sd):
         """``VariationalAE.state_dict()`` of the reference: the decoder sits under ``decoder.``; the encoder's entries are ignored."""
         self.model.load_state_dict({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")})
-
-    # ---- packed tables
-    def _pack_params(self):
-        return list(self.model.parameters())
 
     def _pack(self):
         """pack_resmlp_weights of the decoder with the input layer packed to 64 columns."""
         return pack_resmlp_weights(*self.model._parts(), in_cols=64)
 
     # ---- the decode
-    def fused_ok(self, s) -> bool:
+    def _kernel_shape(self) -> bool:
         lin_in, _, lin_out = self.model._parts()
-        w = lin_in.weight
-        return (s.is_cuda and w.is_cuda and w.dtype == torch.float32 and lin_in.out_features in (128, 256) and lin_in.in_features <= 64 and self.L <= 32
-                and lin_out.out_features <= 16 and self._switch_on())
+        return lin_in.out_features in (128, 256) and lin_in.in_features <= 64 and self.L <= 32 and lin_out.out_features <= 16
 
     def _bank(self, n, dev, need_host: bool):
-        """The unclamped latent as the torch path takes it / as the kernel is handed it: ``z_in``, or (``need_host``) the host form of the kernel's draw, or None."""
-        if self.z_in is not None:
-            return torch.as_tensor(self.z_in(n), dtype=torch.float32).to(dev).reshape(n, self.L).contiguous()
-        if not need_host:
-            return None
-        return torch.as_tensor(cvae_latent_normals(self.seed, self.env_offset, n, self._host_step_word(), self.L), dtype=torch.float32).to(dev)
+        """The unclamped latent (``_draw``)."""
+        return self._draw(self.z_in, n, (n, self.L), lambda t: cvae_latent_normals(self.seed, self.env_offset, n, t, self.L), need_host, dev)
 
     def _decode_torch(self, s, z):
         """Steps 1 - 3 of csrc/policy_cvae.h as torch ops in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too) on the unclamped
@@ -2630,40 +2629,27 @@ class CVAEPolicy(NativePolicy):
         for layer in self.model.layers:
             x = layer(x)
         bad = ~(torch.isfinite(s).all(dim=1) & torch.isfinite(z).all(dim=1) & torch.isfinite(x).all(dim=1))
-        d = lambda v: v.to(device=s.device, dtype=torch.float64)
-        y = (torch.minimum(torch.maximum(x, self.lo.to(s.device, dt)), self.hi.to(s.device, dt)).double() * d(self.out_scale) + d(self.out_shift)).to(dt)
-        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
-        return y, torch.where(torch.isfinite(z), zc, torch.full_like(zc, float("nan")))
+        return self._action_tail(x, bad, True, self.lo, self.hi), torch.where(torch.isfinite(z), zc, torch.full_like(zc, float("nan")))
 
-    def _decode_kernel(self, s):
+    def _step_torch(self, s):
+        y, self.last_z = self._decode_torch(s, self._bank(s.shape[0], s.device, True))
+        return y
+
+    def _step_kernel(self, s):
         from . import capi
         n, dev = s.shape[0], s.device
         w = self._packed.current(self._pack_params(), self._pack)
-        z = self._bank(n, dev, False)
         y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
-        z_out = torch.empty(n, self.L, dtype=torch.float32, device=dev)
+        self.last_z = torch.empty(n, self.L, dtype=torch.float32, device=dev)
         lin_in, blocks, _ = self.model._parts()
-        assert s.is_contiguous() and self._t.device == dev
-        capi.check(capi.load().d3il_cvae_decode_f32(s.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_out"].data_ptr(),
-                                                    w["b_out"].data_ptr(), self.lo.data_ptr(), self.hi.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed,
-                                                    self.env_offset, self._t.data_ptr(), None if z is None else z.data_ptr(), y.data_ptr(), z_out.data_ptr(), n, self.obs_dim, self.L,
-                                                    self.A, lin_in.out_features, len(blocks), torch.cuda.current_stream(dev).cuda_stream))
-        self.last_z = z_out
+        capi.launch("d3il_cvae_decode_f32", dev, state=s, **resmlp_args(w), w_out=w["w_out"], b_out=w["b_out"], **self._draw_args(), z_in=self._bank(n, dev, False), actions=y,
+                    z_out=self.last_z, n_env=n, obs_dim=self.obs_dim, latent=self.L, A=self.A, hidden=lin_in.out_features, n_blocks=len(blocks))
         return y
 
-    @torch.no_grad()
-    def predict_batch(self, obs):
-        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
-        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "CVAEPolicy: observation width %d, the decoder takes %d next to its latent" % (s.shape[-1], self.obs_dim)
-        if self.fused_ok(s):
-            y = self._decode_kernel(s)
-        else:
-            self._warn_fallback(s, lambda: "this decoder (hidden %d, %d inputs, %d outputs) is not one the decode kernel is built for; every call runs torch's layers "
-                                "with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
-                                % (self.model._parts()[0].out_features, self.model._parts()[0].in_features, self.A))
-            y, self.last_z = self._decode_torch(s, self._bank(s.shape[0], s.device, True))
-        self._t.add_(1)
-        return y
+    def _fallback_text(self):
+        lin_in = self.model._parts()[0]
+        return ("this decoder (hidden %d, %d inputs, %d outputs) is not one the decode kernel is built for; every call runs torch's layers "
+                "with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)" % (lin_in.out_features, lin_in.in_features, self.A))
 
     @classmethod
     def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, latent_dim: int = 16, action_scale: float = 0.002,
@@ -2671,14 +2657,7 @@ class CVAEPolicy(NativePolicy):
         """A policy of the reference's shape with fixed random weights (there are no checkpoints offline): the shipped scripts use hidden 128 / 256 with 6 / 8 hidden
         layers (3 / 4 blocks) and a latent of 16, 24 or 32; torch's default layer initialisation times ``weight_gain``, unit observation scaling, actions of
         ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(seed)
-            net = ResidualMLP(obs_dim + latent_dim, hidden_dim, 2 * n_blocks, action_dim)
-        with torch.no_grad():
-            for p in net.parameters():
-                p.mul_(weight_gain)
-                p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        net, sc = ResidualMLP.random(obs_dim + latent_dim, hidden_dim, n_blocks, action_dim, seed, weight_gain), Scaler.unit(obs_dim, action_dim, action_scale, bound, device)
         return cls(net.to(device), sc, latent_dim, seed=policy_seed, **kw)
 
 
@@ -2742,8 +2721,7 @@ class BeTMLPPolicy(NativePolicy):
         lin_in, _, lin_out = model._parts()
         self.obs_dim = int(lin_in.in_features)
         assert lin_out.out_features == self.V * (1 + self.A) and lin_out.bias is not None, "the output layer has V (1 + A) rows and a bias"
-        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
-        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
+        self._init_output(scaler)
         self._init_stream(seed)
         self.uniform_fn = uniform_fn
         self.record = False           # also keep the probabilities (last_probs)
@@ -2754,18 +2732,8 @@ class BeTMLPPolicy(NativePolicy):
     def from_reference(cls, agent, seed: int = 0, uniform_fn=None, device=None):
         """From a live reference ``BetMLP_Agent`` (duck-typed): ``agent.model.model.state_dict()`` (the ResidualMLPNetwork), ``agent.action_ae.bin_centers``,
         ``agent.scaler`` (its ``y_bounds`` are the clamp)."""
-        sd = {k: torch.as_tensor(v) for k, v in agent.model.model.state_dict().items()}
-        dev = torch.device(device) if device is not None else sd["layers.0.weight"].device
-        hidden, in_dim = sd["layers.0.weight"].shape
-        n_blocks = len({k.split(".")[1] for k in sd if ".l1." in k})
-        last = max(int(k.split(".")[1]) for k in sd)
-        net = ResidualMLP(in_dim, hidden, 2 * n_blocks, sd["layers.%d.weight" % last].shape[0])
-        net.load_state_dict(sd)
-        net = net.to(dev)
-        for p in net.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
+        net = ResidualMLP.from_reference_state(agent.model.model.state_dict(), device)
+        scaler = Scaler.from_reference(agent.scaler, net.layers[0].weight.device)
         return cls(net, torch.as_tensor(agent.action_ae.bin_centers), scaler, seed=seed, uniform_fn=uniform_fn)
 
     @staticmethod
@@ -2780,16 +2748,7 @@ class BeTMLPPolicy(NativePolicy):
             if not pol.predict_offsets or int(pol.vocab_size) != 64 or type(agent.obs_encoding_net) is not nn.Identity:
                 return False
             layers = list(pol.model.layers)
-            if len(layers) < 2 or not all(type(l) is nn.Linear for l in (layers[0], layers[-1])):
-                return False
-            blocks = layers[1:-1]
-            lins = [layers[0], layers[-1]] + [l for b in blocks for l in (b.l1, b.l2)]
-            if not all(type(l) is nn.Linear and not hasattr(l, "weight_orig") and l.bias is not None for l in lins):
-                return False
-            if not all(isinstance(b.act, nn.Mish) and not b.use_norm for b in blocks):
-                return False
-            H = layers[0].out_features
-            if not all(l.in_features == H and l.out_features == H for b in blocks for l in (b.l1, b.l2)) or layers[-1].in_features != H:
+            if not ResidualMLP.is_plain(layers, strict=True):
                 return False
             centers = torch.as_tensor(agent.action_ae.bin_centers)
             if centers.dim() != 2 or centers.shape[0] != 64 or not 1 <= centers.shape[1] <= 8:
@@ -2801,16 +2760,9 @@ class BeTMLPPolicy(NativePolicy):
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
     SWITCH, LAST = "D3IL_POLICY_BET_MLP_FUSED", ("last_bins", "last_u", "last_probs")
 
-    def reset(self):
-        pass
-
     def load_reference_state_dict(self, sd):
         """``ResidualMLPNetwork.state_dict()`` of the reference (bet_mlp_agent.py: agent.model.model)."""
         self.model.load_state_dict(sd)
-
-    # ---- packed tables
-    def _pack_params(self):
-        return list(self.model.parameters())
 
     def _pack(self):
         return pack_bet_mlp_weights(*self.model._parts(), V=self.V)
@@ -2820,17 +2772,8 @@ class BeTMLPPolicy(NativePolicy):
         return lin_in.out_features in (128, 256) and 1 <= lin_in.in_features <= 28 and self.V == 64 and 1 <= self.A <= 8
 
     # ---- the call
-    def fused_ok(self, s) -> bool:
-        w = self.model._parts()[0].weight
-        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
-
     def _uniforms(self, n, dev, need_host: bool):
-        """The uniforms as the torch path takes them / as the kernel is handed them: ``uniform_fn``, or (``need_host``) the host form of the kernel's draw, or None."""
-        if self.uniform_fn is not None:
-            return torch.as_tensor(self.uniform_fn(n), dtype=torch.float32).to(dev).reshape(n).contiguous()
-        if not need_host:
-            return None
-        return torch.as_tensor(bet_mlp_uniforms(self.seed, self.env_offset, n, self._host_step_word())).to(dev)
+        return self._draw(self.uniform_fn, n, (n,), lambda t: bet_mlp_uniforms(self.seed, self.env_offset, n, t), need_host, dev)
 
     def _tail_torch(self, s, h, out, u):
         """Steps 3 - 7 of csrc/policy_bet_mlp.h as torch ops in the dtype of ``out`` (f32 in the policy; the tests run it in f64 too), in the kernel's order of
@@ -2842,11 +2785,8 @@ class BeTMLPPolicy(NativePolicy):
         S = c[:, -1:]
         bins = (c <= u.to(dev, dt).unsqueeze(1) * S).sum(dim=1).clamp_max(V - 1)
         off = out[:, V:].reshape(-1, V, A)[torch.arange(out.shape[0], device=dev), bins]
-        d = lambda v: v.to(device=dev, dtype=torch.float64)
-        v = self.centers.to(dev, dt)[bins] + off
-        y = (torch.minimum(torch.maximum(v, self.lo.to(dev, dt)), self.hi.to(dev, dt)).double() * d(self.out_scale) + d(self.out_shift)).to(dt)
         bad = ~(torch.isfinite(s).all(dim=1) & torch.isfinite(h).all(dim=1) & torch.isfinite(logits).all(dim=1))
-        y = torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        y = self._action_tail(self.centers.to(dev, dt)[bins] + off, bad, True, self.lo, self.hi)
         return y, torch.where(bad, torch.full_like(bins, -1), bins).to(torch.int32), p / S
 
     def _predict_torch(self, s, u):
@@ -2856,41 +2796,31 @@ class BeTMLPPolicy(NativePolicy):
             h = layer(h)
         return self._tail_torch(s, h, self.model.layers[-1](h), u)
 
-    def _predict_kernel(self, s):
+    def _step_torch(self, s):
+        u = self._uniforms(s.shape[0], s.device, True)
+        y, self.last_bins, probs = self._predict_torch(s, u)
+        self.last_u, self.last_probs = u, probs if self.record else None
+        return y
+
+    def _step_kernel(self, s):
         from . import capi
         n, dev = s.shape[0], s.device
         w = self._packed.current(self._pack_params(), self._pack)
-        u_in = self._uniforms(n, dev, False)
         y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
         bins = torch.empty(n, dtype=torch.int32, device=dev)
         u_out = torch.empty(n, dtype=torch.float32, device=dev)
         probs = torch.empty(n, self.V, dtype=torch.float32, device=dev) if self.record else None
         lin_in, blocks, _ = self.model._parts()
-        assert s.is_contiguous() and self._t.device == dev
-        capi.check(capi.load().d3il_bet_mlp_f32(s.data_ptr(), w["w_in"].data_ptr(), w["b_in"].data_ptr(), w["w_blk"].data_ptr(), w["b_blk"].data_ptr(), w["w_logit"].data_ptr(),
-                                                w["b_logit"].data_ptr(), w["w_off"].data_ptr(), w["b_off"].data_ptr(), self.centers.data_ptr(), self.lo.data_ptr(),
-                                                self.hi.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed, self.env_offset, self._t.data_ptr(),
-                                                None if u_in is None else u_in.data_ptr(), y.data_ptr(), bins.data_ptr(), u_out.data_ptr(),
-                                                None if probs is None else probs.data_ptr(), n, self.obs_dim, self.V, self.A, lin_in.out_features, len(blocks),
-                                                torch.cuda.current_stream(dev).cuda_stream))
+        capi.launch("d3il_bet_mlp_f32", dev, state=s, **resmlp_args(w), w_logit=w["w_logit"], b_logit=w["b_logit"], w_off=w["w_off"], b_off=w["b_off"], centers=self.centers,
+                    **self._draw_args(), u_in=self._uniforms(n, dev, False), actions=y, bins=bins, u_out=u_out, probs=probs, n_env=n, obs_dim=self.obs_dim, V=self.V, A=self.A,
+                    hidden=lin_in.out_features, n_blocks=len(blocks))
         self.last_bins, self.last_u, self.last_probs = bins, u_out, probs
         return y
 
-    @torch.no_grad()
-    def predict_batch(self, obs):
-        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
-        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "BeTMLPPolicy: observation width %d, the network takes %d" % (s.shape[-1], self.obs_dim)
-        if self.fused_ok(s):
-            y = self._predict_kernel(s)
-        else:
-            self._warn_fallback(s, lambda: "this network (hidden %d, %d inputs, %d bins, %d action components) is not one the kernel is built for; every call runs "
-                                "torch's layers with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
-                                % (self.model._parts()[0].out_features, self.obs_dim, self.V, self.A))
-            u = self._uniforms(s.shape[0], s.device, True)
-            y, self.last_bins, probs = self._predict_torch(s, u)
-            self.last_u, self.last_probs = u, probs if self.record else None
-        self._t.add_(1)
-        return y
+    def _fallback_text(self):
+        return ("this network (hidden %d, %d inputs, %d bins, %d action components) is not one the kernel is built for; every call runs "
+                "torch's layers with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                % (self.model._parts()[0].out_features, self.obs_dim, self.V, self.A))
 
     @classmethod
     def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, action_scale: float = 0.002, policy_seed: int = 0,
@@ -2899,17 +2829,13 @@ class BeTMLPPolicy(NativePolicy):
         layers (3 / 4 blocks) and 64 bins; torch's default layer initialisation, the logit rows scaled to logits of a standard deviation of about ``logit_std`` (neither
         uniform nor one-hot), small offsets, centres of 0.9, unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
         g = torch.Generator().manual_seed(seed)
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(seed)
-            net = ResidualMLP(obs_dim, hidden_dim, 2 * n_blocks, 64 * (1 + action_dim))
+        net = ResidualMLP.random(obs_dim, hidden_dim, n_blocks, 64 * (1 + action_dim), seed)
         with torch.no_grad():
             out = net.layers[-1]
             out.weight[:64] = torch.randn(64, hidden_dim, generator=g) * (logit_std / hidden_dim ** 0.5)
             out.weight[64:] = torch.randn(64 * action_dim, hidden_dim, generator=g) * (0.4 / hidden_dim ** 0.5)
             out.bias.copy_(torch.randn(out.bias.shape, generator=g) * 0.1)
-            for p in net.parameters():
-                p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
+        sc = Scaler.unit(obs_dim, action_dim, action_scale, bound, device)
         return cls(net.to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, seed=policy_seed, uniform_fn=uniform_fn)
 
 
@@ -2932,12 +2858,10 @@ class GPTBCPolicy(BeTPolicy):
         self.trunk, self.scaler, self.W = trunk.eval(), scaler, int(window_size)
         dev = scaler.x_mean.device
         self.device = dev
-        f = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous()
         self.A = int(trunk.head.weight.shape[0])
         assert trunk.head.bias is None and trunk.block_size >= self.W
-        self.min_action, self.max_action = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
+        self._init_output(scaler)
         assert self.min_action.numel() == self.A, "one bound per head row"
-        self.out_scale, self.out_shift = (scaler.y_std + 1e-12).to(torch.float32).contiguous(), scaler.y_mean.to(torch.float32).contiguous()
         self._init_stream(seed)
         self.hist = None
         self._static = False          # fixed-shape chain with device-only state (set by capture_snapshot)
@@ -2956,12 +2880,7 @@ class GPTBCPolicy(BeTPolicy):
         n_head = int(getattr(mingpt, "n_head", 0) or mingpt.model.blocks[0].attn.n_head)
         trunk = MinGPTTrunk(input_dim, n_embd, n_layer, n_head, sd["pos_emb"].shape[1], sd["head.weight"].shape[0], 0)
         trunk.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
-        trunk = trunk.to(dev)
-        for p in trunk.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        scaler = Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev)
-        return cls(trunk, scaler, int(agent.window_size), seed=seed)
+        return cls(trunk.to(dev).requires_grad_(False), Scaler.from_reference(agent.scaler, dev), int(agent.window_size), seed=seed)
 
     @staticmethod
     def matches(agent) -> bool:
@@ -2990,14 +2909,11 @@ class GPTBCPolicy(BeTPolicy):
 
     def _tail_torch(self, h):
         """Steps 1 - 3 of csrc/policy_gpt_bc.h as torch ops in the dtype of ``h`` and the parameters (f32 in the policy; the tests run it in f64 too)."""
-        dt, dev = h.dtype, h.device
         x = self.trunk.ln_f(h)
         o = F.linear(x, self.trunk.head.weight)
-        d = lambda v: v.to(device=dev, dtype=torch.float64)
-        y = (torch.minimum(torch.maximum(o, self.min_action.to(dev, dt)), self.max_action.to(dev, dt)).double() * d(self.out_scale) + d(self.out_shift)).to(dt)
         bad = ~(torch.isfinite(h).all(dim=1) & torch.isfinite(x).all(dim=1) & torch.isfinite(o).all(dim=1))
         self.last_bad = bad.to(torch.int32)
-        return torch.where(bad.unsqueeze(1), torch.full_like(y, float("nan")), y)
+        return self._action_tail(o, bad, True, self.min_action, self.max_action)
 
     def _tail_kernel(self, h):
         from . import capi
@@ -3008,9 +2924,8 @@ class GPTBCPolicy(BeTPolicy):
         bad = torch.empty(n, dtype=torch.int32, device=dev)
         ln, w = self.trunk.ln_f, self.trunk.head.weight
         assert w.is_contiguous()
-        capi.check(capi.load().d3il_gpt_bc_head_f32(h.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w.data_ptr(), self.min_action.data_ptr(),
-                                                    self.max_action.data_ptr(), self.out_scale.data_ptr(), self.out_shift.data_ptr(), y.data_ptr(), bad.data_ptr(), n, C, self.A,
-                                                    torch.cuda.current_stream(dev).cuda_stream))
+        capi.launch("d3il_gpt_bc_head_f32", dev, h=h, ln_weight=ln.weight, ln_bias=ln.bias, ln_eps=float(ln.eps), w_head=w, lo=self.min_action, hi=self.max_action,
+                    scale=self.out_scale, shift=self.out_shift, actions=y, bad=bad, rows=n, C=C, A=self.A)
         self.last_bad = bad
         return y
 
@@ -3027,10 +2942,7 @@ class GPTBCPolicy(BeTPolicy):
         with torch.no_grad():
             trunk.pos_emb.copy_(torch.randn(trunk.pos_emb.shape, generator=g) * 0.1)
             trunk.head.weight.copy_(torch.randn(action_dim, n_embd, generator=g) * (head_gain / n_embd ** 0.5))
-        for p in trunk.parameters():
-            p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
-        return cls(trunk.to(device), sc, window_size, seed=policy_seed)
+        return cls(trunk.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, bound, device), window_size, seed=policy_seed)
 
 
 # ------------------------------------------------------------------------------------------------ DDPM-ACT: encoder-decoder diffusion sampler that emits action chunks
@@ -3178,7 +3090,7 @@ def pack_ddpm_act_weights(net: EncDecDenoiser, n_timesteps: int) -> dict:
             "enc_w": torch.stack(enc_w), "enc_v": torch.stack(enc_v), "dec_w": torch.stack(dec_w), "dec_v": torch.stack(dec_v), "head_w": flat(pack_tiles(net.action_pred.weight))}
 
 
-class DDPMACTPolicy(NativePolicy):
+class DDPMACTPolicy(_ChunkLanes, NativePolicy):
     """DiffusionAgent.predict of the encoder-decoder agent without goals (agents/ddpm_encdec_agent.py:222-257) around Diffusion.sample (diffusion_policy.py:117-217)
     and DiffusionEncDec.forward (diffusion_models.py:844-905), on a batch: the scaled observation enters the lane's window (deque maxlen obs_seq_len S) on EVERY
     step; a lane whose ``counter`` equals the chunk length Ta is due and samples a new chunk of Ta actions from its window as it stands (L entries, 1 <= L <= S; the
@@ -3206,9 +3118,7 @@ class DDPMACTPolicy(NativePolicy):
         dev = scaler.x_mean.device
         self.device = dev
         self._sched = ddpm_schedule(cosine_beta_schedule(self.T).to(dev))["sched"]
-        f = lambda a: torch.as_tensor(a, device=dev).detach().to(torch.float32).contiguous()
-        self.lo, self.hi = f(scaler.y_bounds[0]), f(scaler.y_bounds[1])
-        self.out_scale, self.out_shift = f(scaler.y_std + 1e-12), f(scaler.y_mean)
+        self._init_output(scaler)
         self._init_stream(seed)
         self.n_envs, self.noise_in = n_envs, noise_in
         self.counter = self.chunk = self.hist = self.last_bad = None      # per-lane state: i32 [N], f32 [N, Ta, A] (clamped, inverse-scaled), the window, i32 [N]
@@ -3233,11 +3143,7 @@ class DDPMACTPolicy(NativePolicy):
                              int(net.encoder.blocks[0].attn.mask.shape[-1]), linear_output="action_pred.weight" in sd)
         own = den.state_dict()
         den.load_state_dict({k: sd[k].to(own[k].dtype) for k in own})
-        den = den.to(dev)
-        for p in den.parameters():
-            p.requires_grad_(False)
-        sc = agent.scaler
-        pol = cls(den, Scaler(sc.x_mean, sc.x_std, sc.y_mean, sc.y_std, sc.y_bounds, device=dev), int(diff.n_timesteps), obs_seq_len=int(agent.obs_seq_len), seed=seed,
+        pol = cls(den.to(dev).requires_grad_(False), Scaler.from_reference(agent.scaler, dev), int(diff.n_timesteps), obs_seq_len=int(agent.obs_seq_len), seed=seed,
                   n_envs=n_envs, noise_in=noise_in)
         if getattr(agent, "use_ema", False):
             pol.use_ema(agent.ema_helper.shadow_params)
@@ -3295,28 +3201,14 @@ class DDPMACTPolicy(NativePolicy):
 
     # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; a fork and a capture keep the window, ``hist``, with the rest)
     SWITCH, STATE, LAST = "D3IL_POLICY_DDPM_ACT_FUSED", ("counter", "chunk", "last_bad"), ("last_chunk", "last_noise")
+    TAKES = "the state tokens take %d"
 
     def _state(self, n):
         """counter / chunk / window / last_bad for n lanes; a new size starts with every lane due on an empty window."""
         if self.counter is None or self.counter.shape[0] != n:
-            dev = self.device
-            self.counter = torch.full((n,), self.Ta, dtype=torch.int32, device=dev)
-            self.chunk = torch.zeros(n, self.Ta, self.A, dtype=torch.float32, device=dev)
-            self.last_bad = torch.zeros(n, dtype=torch.int32, device=dev)
-            self.hist = _History(n, self.S, self.obs_dim, dev)
-
-    def reset(self):
-        """DiffusionAgent.reset for every lane: empty windows, the next call computes a chunk everywhere."""
-        if self.counter is not None:
-            self.counter.fill_(self.Ta)
-            self.hist.reset()
-
-    def begin_episodes(self, mask):
-        """Lanes that start a new trajectory: window length 0, due at their next step (in place on the device, also under a captured graph)."""
-        self._state(int(mask.shape[0]))
-        m = mask.to(device=self.device, dtype=torch.bool).reshape(-1)
-        self.counter.masked_fill_(m, self.Ta)
-        self.hist.reset_(m)
+            self._chunk_state(n, self.Ta)
+            self.last_bad = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.hist = _History(n, self.S, self.obs_dim, self.device)
 
     def load_reference_state_dict(self, sd):
         """``Diffusion.state_dict()`` of the reference: the denoiser sits under ``model.`` (a bare DiffusionEncDec state dict is taken as it is); masks are ignored."""
@@ -3327,10 +3219,6 @@ class DDPMACTPolicy(NativePolicy):
         for p in self.model.parameters():
             p.requires_grad_(False)
 
-    # ---- packed tables
-    def _pack_params(self):
-        return list(self.model.parameters())
-
     def _pack(self):
         return pack_ddpm_act_weights(self.model, self.T)
 
@@ -3340,22 +3228,14 @@ class DDPMACTPolicy(NativePolicy):
         return (m.embed_dim == 64 and m.n_heads == 4 and 1 <= m.state_dim <= 32 and 1 <= m.action_dim <= 8 and 1 <= self.S <= 5 and m.obs_seq_len <= 5 and 1 <= self.Ta <= 4
                 and 1 <= len(m.encoder.blocks) <= 4 and 1 <= len(m.decoder.blocks) <= 8 and 1 <= self.T <= 255 and m.linear_output)
 
-    def fused_ok(self, s) -> bool:
-        w = self.model.tok_emb.weight
-        return s.is_cuda and w.is_cuda and w.dtype == torch.float32 and self._kernel_shape() and self._switch_on()
-
     def _noise(self, n, dev, need_host: bool):
-        """The normals [n, T + 1, Ta, A] (index = chain index) as the torch path takes them / as the kernel is handed them: the given bank, or (``need_host``) the
-        host form of the kernel's draw (index 0, which is never drawn, is zero)."""
-        if self.noise_in is not None:
-            return torch.as_tensor(self.noise_in(n), dtype=torch.float32).to(dev).reshape(n, self.T + 1, self.Ta, self.A).contiguous()
-        if not need_host:
-            return None
-        t = self._host_step_word()
-        z = np.zeros((n, self.T + 1, self.Ta, self.A))
-        for k in range(1, self.T + 1):
-            z[:, k] = ddpm_act_normals(self.seed, self.env_offset, n, t, k, self.Ta, self.A)
-        return torch.as_tensor(z, dtype=torch.float32).to(dev)
+        """The normals [n, T + 1, Ta, A] (index = chain index; ``_draw``): in the host form index 0, which is never drawn, is zero."""
+        def host(t):
+            z = np.zeros((n, self.T + 1, self.Ta, self.A))
+            for k in range(1, self.T + 1):
+                z[:, k] = ddpm_act_normals(self.seed, self.env_offset, n, t, k, self.Ta, self.A)
+            return z
+        return self._draw(self.noise_in, n, (n, self.T + 1, self.Ta, self.A), host, need_host, dev)
 
     def _sched_for(self, dt, dev):
         if dt == torch.float32:
@@ -3382,15 +3262,21 @@ class DDPMACTPolicy(NativePolicy):
             mean = s[2] * x0 + s[3] * x
             x = mean if i == 0 else mean + s[4] * noise[:, i]
             bad |= ~torch.isfinite(eps).reshape(st.shape[0], -1).all(dim=1) | ~torch.isfinite(x).reshape(st.shape[0], -1).all(dim=1)
-        y = torch.minimum(torch.maximum(x, lo), hi) * c(self.out_scale) + c(self.out_shift)
-        return torch.where(bad.reshape(-1, 1, 1), torch.full_like(y, float("nan")), y), bad, x
+        return self._action_tail(x, bad, False, lo, hi), bad, x
 
-    def _step_torch(self, win, ln):
+    def _push(self, s):
+        """The scaled observation enters every lane's window: (window [N, S, obs] in its ``padded()`` form, lengths i64 [N])."""
+        self.hist.append_(s)
+        win, ln = self.hist.padded()
+        return win.contiguous(), ln.contiguous()
+
+    def _step_torch(self, s):
+        win, ln = self._push(s)
         if win.is_cuda and _capturing():
             raise RuntimeError("DDPMACTPolicy: the torch path decides on the host which lanes are due, groups them by window length and draws its Philox numbers there; "
                                "it cannot be captured - the kernel can")
         n, dev = win.shape[0], win.device
-        due = (self.counter >= self.Ta) | (self.counter < 0)
+        due = self._due()
         self.last_bad.zero_()
         if self.record:
             self.last_noise = torch.zeros(n, self.T + 1, self.Ta, self.A, dtype=torch.float32, device=dev)
@@ -3407,47 +3293,28 @@ class DDPMACTPolicy(NativePolicy):
                 drawn[:, 0] = 0
                 self.last_noise.copy_(torch.where(due.reshape(-1, 1, 1, 1), drawn, self.last_noise))
             self.counter.masked_fill_(due, 0)
-        y = self.chunk[torch.arange(n, device=dev), self.counter.long()]
-        self.counter.add_(1)
-        return y
+        return self._emit()
 
-    def _step_kernel(self, win, ln):
+    def _step_kernel(self, s):
         from . import capi
+        win, ln = self._push(s)
         n, dev, m = win.shape[0], win.device, self.model
         w = self._packed.current(self._pack_params(), self._pack)
-        z = self._noise(n, dev, False)
         y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
         noise_out = torch.zeros(n, self.T + 1, self.Ta, self.A, dtype=torch.float32, device=dev) if self.record else None
-        ptr = lambda v: None if v is None else v.data_ptr()
-        assert win.is_contiguous() and ln.is_contiguous() and ln.dtype == torch.int64 and self._t.device == dev and self.counter.device == dev
-        capi.check(capi.load().d3il_ddpm_act_chunk_f32(win.data_ptr(), ln.data_ptr(), w["w_in"].data_ptr(), w["tab"].data_ptr(), w["enc_w"].data_ptr(), w["enc_v"].data_ptr(),
-                                                       w["dec_w"].data_ptr(), w["dec_v"].data_ptr(), w["head_w"].data_ptr(), self.lo.data_ptr(), self.hi.data_ptr(),
-                                                       self.out_scale.data_ptr(), self.out_shift.data_ptr(), self.seed, self.env_offset, self._t.data_ptr(), ptr(z), None,
-                                                       self.counter.data_ptr(), self.chunk.data_ptr(), y.data_ptr(), self.last_bad.data_ptr(), None, ptr(noise_out), n,
-                                                       self.obs_dim, self.A, self.S, self.Ta, m.embed_dim, m.n_heads, len(m.encoder.blocks), len(m.decoder.blocks), self.T, 1, -1, 0,
-                                                       torch.cuda.current_stream(dev).cuda_stream))
+        assert ln.dtype == torch.int64
+        capi.launch("d3il_ddpm_act_chunk_f32", dev, window=win, len=ln, **w, **self._draw_args(), noise_in=self._noise(n, dev, False), x_in=None, counter=self.counter,
+                    chunk=self.chunk, actions=y, bad=self.last_bad, x_out=None, noise_out=noise_out, n_env=n, obs_dim=self.obs_dim, A=self.A, obs_seq_len=self.S,
+                    action_seq_len=self.Ta, width=m.embed_dim, n_head=m.n_heads, n_enc=len(m.encoder.blocks), n_dec=len(m.decoder.blocks), n_timesteps=self.T,
+                    linear_head=1, k_start=-1, k_stop=0)
         if self.record:
             self.last_noise = noise_out
         return y
 
-    @torch.no_grad()
-    def predict_batch(self, obs):
-        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32)).contiguous()
-        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "DDPMACTPolicy: observation width %d, the state tokens take %d" % (s.shape[-1], self.obs_dim)
-        self._state(s.shape[0])
-        self.hist.append_(s)
-        win, ln = self.hist.padded()
-        if self.fused_ok(s):
-            y = self._step_kernel(win.contiguous(), ln.contiguous())
-        else:
-            self._warn_fallback(s, lambda: "this network (width %d, %d heads, window %d, chunk %d, linear head %s) is not one the chain kernel is built for; every call "
-                                "runs the torch path with a device synchronisation per call and no graph capture"
-                                % (self.model.embed_dim, self.model.n_heads, self.S, self.Ta, self.model.linear_output))
-            y = self._step_torch(win, ln)
-        if self.record:
-            self.last_chunk = self.chunk.clone()
-        self._t.add_(1)
-        return y
+    def _fallback_text(self):
+        return ("this network (width %d, %d heads, window %d, chunk %d, linear head %s) is not one the chain kernel is built for; every call "
+                "runs the torch path with a device synchronisation per call and no graph capture"
+                % (self.model.embed_dim, self.model.n_heads, self.S, self.Ta, self.model.linear_output))
 
     @classmethod
     def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, obs_seq_len: int = 5, action_seq_len: int = 4, n_timesteps: int = 16, enc_layers: int = 2,
@@ -3459,7 +3326,4 @@ class DDPMACTPolicy(NativePolicy):
         net = EncDecDenoiser(obs_dim, action_dim, embed_dim, n_heads, enc_layers, dec_layers, obs_seq_len, action_seq_len, max(window_size + 1, 1 + obs_seq_len, action_seq_len),
                              linear_output=linear_output)
         net.load_state_dict({k: torch.as_tensor(v) for k, v in ddpm_act_synthetic_state({k: v.shape for k, v in net.state_dict().items()}, seed).items()})
-        for p in net.parameters():
-            p.requires_grad_(False)
-        sc = Scaler([0.0] * obs_dim, [1.0] * obs_dim, [0.0] * action_dim, [action_scale] * action_dim, y_bounds=[[-bound] * action_dim, [bound] * action_dim], device=device)
-        return cls(net.to(device), sc, n_timesteps, seed=policy_seed, **kw)
+        return cls(net.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, bound, device), n_timesteps, seed=policy_seed, **kw)
