@@ -47,10 +47,11 @@ ACT_TAG = 0x41430000      # ... of d3il_act_chunk_f32, or-ed with q (csrc/policy
 CVAE_TAG = 0x43560000      # ... of d3il_cvae_decode_f32, or-ed with q (csrc/policy_cvae.h)
 DDPM_ACT_TAG = 0x44410000      # ... of d3il_ddpm_act_chunk_f32, or-ed with k << 8 | t << 1 | q (csrc/policy_ddpm_act.h)
 BET_MLP_TAG = 0x424D4C50      # ... of d3il_bet_mlp_f32 (csrc/policy_bet_mlp.h)
+BESO_TAG = 0x42530000      # ... of d3il_beso_step, or-ed with draw << 8 | j << 1 | q (csrc/policy_beso.h)
 HXG_CLIPPED, HXG_NONFINITE, HXG_LAUNCHES, HXG_N = 0, 1, 2, 4      # the counters of d3il_f16x3_set_guard (D3IL_HXG_*)
 
 EXPORTS = ["d3il_create", "d3il_destroy", "d3il_start", "d3il_reset", "d3il_step", "d3il_get_buffers", "d3il_get_state",
-           "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_bet_mlp_f32", "d3il_gpt_bc_head_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
+           "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_beso_step", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_bet_mlp_f32", "d3il_gpt_bc_head_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
            "d3il_rccl_available", "d3il_comm_unique_id", "d3il_comm_init", "d3il_comm_count", "d3il_comm_destroy", "d3il_reduce_metrics", "d3il_set_timing",
            "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_group_create", "d3il_group_flush", "d3il_group_destroy", "d3il_group_set_option", "d3il_group_stats", "d3il_group_pipeline_stats", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_debug_build_flags", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
 
@@ -64,7 +65,11 @@ _LN = "ln_weight ln_bias ln_eps:f"
 _MLP = "h " + _LN + " x w_packed b1 b2 out rows:l C:i H:i"
 _LINEAR = "xin " + _LN + " w_packed bias resid out rows:l N:i"
 _ENCDEC = "w_in tab enc_w enc_v dec_w dec_v head_w " + _DRAW
-SIGNATURES = {name: tuple((a.partition(":")[0], _CTYPES[a.partition(":")[2]]) for a in (spec + " stream").split()) for name, spec in {
+def _table(specs: dict) -> dict:
+    return {name: tuple((a.partition(":")[0], _CTYPES[a.partition(":")[2]]) for a in (spec + " stream").split()) for name, spec in specs.items()}
+
+
+SIGNATURES = _table({
     "d3il_attention_causal_f32": "qkv out B:i T:i H:i D:i",
     "d3il_layernorm_f32": "x weight bias y rows:l C:i eps:f",
     "d3il_linear120_f32": _LINEAR,
@@ -86,10 +91,15 @@ SIGNATURES = {name: tuple((a.partition(":")[0], _CTYPES[a.partition(":")[2]]) fo
     "d3il_cvae_decode_f32": "state " + _RESMLP + " w_out b_out " + _DRAW + " z_in actions z_out n_env:l obs_dim:i latent:i A:i hidden:i n_blocks:i",
     "d3il_bet_mlp_f32": "state " + _RESMLP + " w_logit b_logit w_off b_off centers " + _DRAW + " u_in actions bins u_out probs n_env:l obs_dim:i V:i A:i hidden:i n_blocks:i",
     "d3il_gpt_bc_head_f32": "h " + _LN + " w_head " + _TAIL + " actions bad rows:l C:i A:i",
-}.items()}
+})
+# The policy kernel entries whose names carry no _f32 / _f16x3 suffix, in the same format; tests/test_capi_signatures2.py holds this table against the header.
+SIGNATURES2 = _table({
+    "d3il_beso_step": "hk " + _LN + " w_pred b_pred w_aemb bias_pos semb coef sigma_max:f c_in0:f " + _TAIL + " len seed:q env_offset:q t_device noise_in x xbuf a_hist actions bad "
+                      "noise_out n_env:l C:i A:i W:i S:i i:i",
+})
 # what launch() works from, resolved once per entry: the keywords it demands (everything but the stream), the same as a set, the positions of the pointers
 _LAUNCH = {name: (tuple(n for n, _ in sig[:-1]), frozenset(n for n, _ in sig[:-1]), tuple(i for i, (_, t) in enumerate(sig[:-1]) if t is C.c_void_p))
-           for name, sig in SIGNATURES.items()}
+           for name, sig in {**SIGNATURES, **SIGNATURES2}.items()}
 
 
 class D3ilError(RuntimeError):
@@ -124,7 +134,7 @@ def load():
         L.d3il_policy_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.d3il_policy_action.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.d3il_count_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        for name, sig in SIGNATURES.items():
+        for name, sig in {**SIGNATURES, **SIGNATURES2}.items():
             if hasattr(L, name):      # (an older build loaded through D3IL_LIB_PATH lacks the newest entries: skipped, not an error)
                 getattr(L, name).argtypes = [t for _, t in sig]
         L.d3il_f16x3_set_guard.argtypes = [C.c_void_p]
@@ -188,7 +198,7 @@ def check(rc: int):
 
 
 def launch(name: str, device, **args):
-    """Call the policy kernel entry ``name`` of SIGNATURES by keyword on the current stream of ``device``: exactly the header's parameter names but ``stream``
+    """Call the policy kernel entry ``name`` of SIGNATURES / SIGNATURES2 by keyword on the current stream of ``device``: exactly the header's parameter names but ``stream``
     (TypeError naming the missing / unknown ones, or a tensor on another device, before the library is touched); a pointer parameter takes a tensor, which goes as its
     data_ptr(), or None for NULL, numbers go as they are; a non-zero return code raises D3ilError."""
     names, keys, pointers = _LAUNCH[name]

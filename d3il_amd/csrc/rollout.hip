@@ -28,6 +28,7 @@ constexpr int WAVE = 64;
 #include "policy_f16x3.h"
 #include "policy_bet.h"
 #include "policy_ddpm_gpt.h"
+#include "policy_beso.h"
 #include "policy_ibc.h"
 #include "policy_act.h"
 #include "policy_ddpm_act.h"
@@ -1487,6 +1488,30 @@ int d3il_ddpm_gpt_step_f32(const float* hk, const float* ln_weight, const float*
   if (C == 72) hipLaunchKernelGGL(k_ddpm_gpt_step<72>, grid, block, 0, (hipStream_t)stream, a);
   else if (C == 120) hipLaunchKernelGGL(k_ddpm_gpt_step<120>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_ddpm_gpt_step<128>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_beso_step(const float* hk, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_pred, const float* b_pred, const float* w_aemb,
+                   const float* bias_pos, const float* semb, const float* coef, float sigma_max, float c_in0, const float* lo, const float* hi, const float* scale,
+                   const float* shift, const int64_t* len, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* noise_in, float* x, float* xbuf,
+                   float* a_hist, float* actions, int32_t* bad, float* noise_out, long n_env, int C, int A, int W, int S, int i, void* stream) {
+  if (C < 4 || C > BS_CMAX || C % 4 != 0 || A < 1 || A > BS_AMAX || W < 1 || W > BS_WMAX || S < 1 || S > BS_SMAX)
+    return fail(D3IL_EUNSUPPORTED, "d3il_beso_step: built for n_embd <= 128 (a multiple of 4), 1 .. 8 action components, a window of 1 .. 16 and 1 .. 254 sampling steps");
+  if (!ln_weight || !ln_bias || !w_pred || !b_pred || !w_aemb || !bias_pos || !semb || !coef || !lo || !hi || !scale || !shift || !len || !t_device || !x || !xbuf || !actions || !bad ||
+      (W > 1 && !a_hist))
+    return fail(D3IL_EINVAL, "d3il_beso_step: null argument");
+  if (i < -1 || i >= S) return fail(D3IL_EINVAL, "d3il_beso_step: step index outside -1 .. S - 1");
+  if (i >= 0 && !hk) return fail(D3IL_EINVAL, "d3il_beso_step: a sampling step needs the hidden rows");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_beso_step: negative environment count");
+  if (n_env == 0) return D3IL_OK;
+  BesoArgs a{hk, ln_weight, ln_bias, w_pred, b_pred, w_aemb, bias_pos, semb, coef, lo, hi, scale, shift, (const long long*)len, t_device, noise_in, x, xbuf, a_hist, actions, bad,
+             noise_out, (unsigned long long)seed, (unsigned long long)env_offset, n_env, ln_eps, sigma_max, c_in0, C, A, W, S, i};
+  // one environment per wave up to 1024 workgroups (the chain over an environment's W positions is latency-bound: more waves in flight hide it), then the block-stride loop
+  long blocks = (n_env + BS_NW - 1) / BS_NW;
+  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks))), block(64 * BS_NW);
+  if (C == 72) hipLaunchKernelGGL(k_beso_step<72>, grid, block, 0, (hipStream_t)stream, a);
+  else if (C == 120) hipLaunchKernelGGL(k_beso_step<120>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_beso_step<128>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

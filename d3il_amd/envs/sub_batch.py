@@ -7,7 +7,8 @@ The counterpart on one GPU: the rollouts of a rank are cut into S contiguous sub
 long as its slowest workgroup, and launches of different streams overlap - sub-batch B's physics runs while sub-batch A's policy does
 (DESIGN section 18.10).  Rollouts are independent of each other, so for a policy that computes every row from that row alone (deterministic, or seeded
 per rollout) the integer result tables are those of one batch (tests/test_subbatch_sims.py); a policy that draws from the process-wide torch generator
-(DDPM / BESO: torch.randn per predict call) draws in another order per sub-batch - the same distribution, not the same table.
+(DDPMPolicy and the older BESOPolicy: torch.randn per predict call) draws in another order per sub-batch - the same distribution, not the same table.
+BESO on the Philox stream is policies.BESONativePolicy: its noise is keyed by the global rollout index and its tables do not depend on the cut.
 
 Used by the Sim classes (``n_sub_batches=``) and by ``bench.py`` (``--sub-batches``).
 """
@@ -213,6 +214,11 @@ class SubBatchSet:
             if b.agent is not a and hasattr(b.agent, "set_rollout_range"):      # an adapter built from a reference agent (policies.BeTPolicy.from_reference)
                 b.agent.set_rollout_range(b.offset, b.n)
             b.agent.reset()
+        if len(self.batches) > 1:      # the clones' device state (step word, histories, tables) was written on the caller's stream: the sub-batch streams go on behind it
+            cur = torch.cuda.current_stream(self.device)
+            for b in self.batches:
+                if b.own_stream:
+                    b.stream.wait_stream(cur)
 
     @property
     def link_near_episodes(self) -> int:

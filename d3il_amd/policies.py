@@ -624,6 +624,13 @@ class DiffusionGPT(nn.Module):
         x = _layer_norm(self.ln_f, self.blocks[-1](x, keep=ctx["keep"]).contiguous())
         return self.action_pred(x)
 
+    def hidden(self, xbuf, keep):
+        """The block chain on a token buffer [b, 2 t + 1, C]: the last block's output at the positions ``keep`` (before ln_f) - BESONativePolicy's form."""
+        x = xbuf
+        for blk in self.blocks[:-1]:
+            x = blk(x)
+        return self.blocks[-1](x, keep=keep)
+
     def forward(self, states, actions, sigma):
         b, t, _ = states.size()
         emb_t = self.sigma_emb((sigma.log() / 4).reshape(b, 1).to(torch.float32)).unsqueeze(1)
@@ -1953,6 +1960,324 @@ class DDPMGPTPolicy(NativePolicy):
             if linear_output:
                 den.action_pred.weight.copy_(torch.randn(den.action_pred.weight.shape, generator=g) * (1.0 / embed_dim ** 0.5))
         return cls(den.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, 1.5, device), n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)
+
+
+# ------------------------------------------------------------------------------------------------ BESO on the Philox stream
+BESO_TAG = 0x42530000         # fourth Philox counter word of the step kernel, or-ed with draw << 8 | j << 1 | q (csrc/policy_beso.h; its upper half is no other tag's)
+
+
+def beso_words(seed: int, env_offset: int, n: int, t: int, d: int, W: int):
+    """The Philox words behind ``beso_normals``: uint32 [n, W, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
+    BESO_TAG | d << 8 | j << 1 | q)).  Draw index d = 0 is the init draw (the kernel takes j = 0 only), d = i + 1 the draw of sampling step i."""
+    assert 0 <= d <= 254 and 1 <= W <= 16, "the counter layout holds d <= 254 and j <= 15"
+    j, q = _tag_axes(W, 2)
+    return philox_words(seed, env_offset, n, t, np.uint64(BESO_TAG | (d << 8)) | (j << np.uint64(1)) | q)
+
+
+def beso_normals(seed: int, env_offset: int, n: int, t: int, d: int, W: int, A: int):
+    """The step kernel's normals of environments 0 .. n-1 at step word t and draw index d, on the host: float64 [n, W, A].  Exact on the 32-bit words
+    (``beso_words``: two calls q per (row, j)) and f64 from there on (``box_muller_f64``); component a = 4 q + m.  Of d = 0 the sampler uses row j = 0 only."""
+    assert 1 <= A <= 8
+    return box_muller_f64(beso_words(seed, env_offset, n, t, d, W)).reshape(n, W, 8)[:, :, :A]
+
+
+def beso_coefficients(sigmas, sigma_data: float):
+    """The per-step constants of the sampler from the noise levels ``sigmas`` (S + 1 host floats: the f32 schedule, last entry 0), computed in f64: rows i < S of
+    (c_skip, c_out, 1 / s_from, s_down - s_from, s_up, c_in of sigmas[i + 1]) - GCDenoiser.get_scalings (score_wrappers.py:31-43) and get_ancestral_step
+    (gc_sampling.py:107-114) with eta = 1 - and c_in of sigmas[0].  The last row's c_in is 0: there is no next iterate."""
+    sd2 = float(sigma_data) ** 2
+    c_in = lambda sg: 1.0 / (sg ** 2 + sd2) ** 0.5
+    rows = []
+    for i in range(len(sigmas) - 1):
+        s_from, s_to = float(sigmas[i]), float(sigmas[i + 1])
+        s_up = min(s_to, (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5)
+        s_down = (s_to ** 2 - s_up ** 2) ** 0.5
+        rows.append([sd2 / (s_from ** 2 + sd2), s_from * sigma_data / (s_from ** 2 + sd2) ** 0.5, 1.0 / s_from, s_down - s_from, s_up, c_in(s_to) if i + 2 < len(sigmas) else 0.0])
+    return rows, c_in(float(sigmas[0]))
+
+
+class BESONativePolicy(NativePolicy):
+    """BesoAgent.predict (beso_agent.py:316-443) with the euler_ancestral sampler on the linear noise schedule (gc_sampling.py:41-44, 107-114, 217-256) around the
+    Karras-preconditioned DiffusionGPT (score_wrappers.py GCDenoiser), on a batch and on the Philox stream - what BESOPolicy computes, as a NativePolicy: scaled
+    observation window (deque maxlen W), the previous W - 1 clamped scaled actions as the first iterate's earlier positions, sigma_max noise at the newest one, S
+    sampling steps over ALL positions, final clamp of the newest position, inverse scaling.
+
+    Always the fixed-shape form (as DDPMGPTPolicy): windows right-padded to W (_History.padded), lengths on the device, in-place histories - ONE code path that
+    CapturedPolicy can capture.  The action ring ``a_hist`` [N, W - 1, A] (newest entry last) is per-lane device state the kernel reads and pushes in place.
+
+    One predict_batch: the state tokens once (torch), one launch of the step kernel in its init mode (csrc/policy_beso.h through d3il_beso_step: first iterate, its
+    action tokens, the sigma token), then S times the block chain (the last block on the action positions only) and one launch of the step kernel (ln_f, head,
+    Karras combination, Euler step, ancestral noise, the next iterate's tokens; at step S - 1 the clamped, inverse-scaled action and the ring push), then a
+    device-side add on the step word.  The arithmetic follows the reference's order step by step (not the merged form of BESOPolicy._sample_device).
+
+    The noise is Box-Muller on Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word, BESO_TAG | d << 8 | j << 1 | q) - draw index d = 0 (j = 0)
+    for the init draw, d = i + 1 for sampling step i; the last step draws nothing - so results do not depend on batch order, sub-batches or ranks (``beso_normals`` is
+    the host form); or ``noise_in(d, n) -> [n, W, A]`` when given (golden replay, tests; of d = 0 row j = 0 is used).  On the CPU, for unsupported shapes (the
+    Linear-SiLU-Linear head among them) and with D3IL_POLICY_BESO_STEP=0 the same arithmetic runs as torch ops (``_step_torch``) with the Philox normals computed
+    on the host - that path cannot be captured.  A NaN / Inf in a valid hidden row or iterate marks the environment (``last_bad``): its action and the ring entry it
+    pushes come out NaN (D3IL_FLAG_SOLVER_FAIL in that lane's step)."""
+
+    def __init__(self, model: DiffusionGPT, scaler: Scaler, window_size: int, num_sampling_steps: int, sigma_min: float, sigma_max: float, sigma_data: float = 0.5,
+                 seed: int = 0, noise_in=None):
+        self.model, self.scaler, self.W, self.S = model.eval(), scaler, int(window_size), int(num_sampling_steps)
+        assert 1 <= self.S <= 254 and 1 <= self.W <= 16, "the Philox counter layout holds S <= 254 and W <= 16"
+        assert self.W <= model.obs_seq_len, "the window cannot exceed the network's obs_seq_len"
+        dev = scaler.x_mean.device
+        self.device = dev
+        self.A, self.obs_dim = int(model.action_emb.in_features), int(model.tok_emb.in_features)
+        self.sigma_min, self.sigma_max, self.sigma_data = float(sigma_min), float(sigma_max), float(sigma_data)
+        # the noise schedule as host floats of its f32 values (as BESOPolicy.sigmas) and the constants derived from them
+        self.sigmas = torch.cat([torch.linspace(self.sigma_max, self.sigma_min, self.S), torch.zeros(1)]).tolist()
+        self._coef, self.c_in0 = beso_coefficients(self.sigmas, self.sigma_data)
+        self._init_output(scaler)
+        self._init_stream(seed)
+        self.noise_in = noise_in
+        self.hist = self.a_hist = None
+        self.record = False           # also keep what every launch drew (last_noise: {d: [n, W, A]})
+        self.last_bad = self.last_noise = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, noise_in=None, device=None):
+        """From a live reference ``BesoAgent`` (duck-typed) whose ``model`` is a ``GCDenoiser`` around a ``DiffusionGPT``: the network's state dict, the sampler's
+        settings, ``agent.scaler``, ``agent.window_size``; with ``agent.use_ema`` the EMA shadow parameters (the reference swaps them in for every predict)."""
+        net = agent.model.inner_model
+        sd = {k: torch.as_tensor(v) for k, v in net.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["tok_emb.weight"].device
+        C, state_dim = sd["tok_emb.weight"].shape
+        A = sd["action_emb.weight"].shape[1]
+        n_layers = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        n_heads = int(net.blocks[0].attn.n_head)
+        own = DiffusionGPT(state_dim, A, C, n_layers, n_heads, sd["pos_emb"].shape[1] - 1, linear_output="action_pred.weight" in sd)
+        keys = own.state_dict()
+        own.load_state_dict({k: v for k, v in sd.items() if k in keys})
+        own = own.to(dev).requires_grad_(False)
+        pol = cls(own, Scaler.from_reference(agent.scaler, dev), int(agent.window_size), int(agent.num_sampling_steps), float(agent.sigma_min), float(agent.sigma_max),
+                  sigma_data=float(agent.sigma_data), seed=seed, noise_in=noise_in)
+        if getattr(agent, "use_ema", False):
+            pol.use_ema(agent.ema_helper.shadow_params)
+        return pol
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Does ``agent`` look like the reference's BesoAgent around GCDenoiser(DiffusionGPT) without goals (what from_reference reads), configured as the sampler
+        restated here: ``sampler_type`` euler_ancestral, ``noise_scheduler`` linear, a linear or Linear-SiLU-Linear head?  Any other setting keeps the agent on the
+        row-by-row adapter, which runs the reference's own code."""
+        try:
+            net = agent.model.inner_model
+            if not (hasattr(agent.model, "get_scalings") and hasattr(net, "sigma_emb") and hasattr(net, "action_emb") and hasattr(net, "blocks") and hasattr(net, "state_dict")
+                    and net.goal_conditioned is False and not getattr(agent, "gc", False) and hasattr(agent, "scaler") and hasattr(agent, "action_context")):
+                return False
+            if agent.sampler_type != "euler_ancestral" or agent.noise_scheduler != "linear":
+                return False
+            head = net.action_pred
+            if not (isinstance(head, nn.Linear) or (isinstance(head, nn.Sequential) and len(head) == 3 and isinstance(head[0], nn.Linear) and isinstance(head[1], nn.SiLU)
+                                                    and isinstance(head[2], nn.Linear))):
+                return False
+            W, S = int(agent.window_size), int(agent.num_sampling_steps)
+            return 1 <= W <= min(16, int(net.pos_emb.shape[1]) - 1) and 1 <= S <= 254 and float(agent.sigma_max) >= float(agent.sigma_min) > 0.0
+        except (AttributeError, TypeError, ValueError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy)
+    SWITCH, STATE, LAST, BOUNDS = "D3IL_POLICY_BESO_STEP", ("a_hist",), ("last_bad", "last_noise"), ("min_action", "max_action")
+
+    @property
+    def f16x3_blocks(self) -> bool:
+        """The blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
+        return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.model.blocks)
+
+    def weights_out_of_range(self) -> int:
+        """As BESOPolicy.weights_out_of_range: entries of the blocks' f16x3-packed matrices that are NaN / Inf or beyond +-65504; one synchronising read."""
+        return int(sum(blk._w_oor for blk in ensure_blocks_packed(self.model.blocks)))
+
+    def range_report(self) -> dict:
+        """The active RangeGuard's counters (clipped / nonfinite / launches) plus ``weights_out_of_range``."""
+        g = range_guard()
+        if g is None:
+            raise RuntimeError("range_report: no RangeGuard is enabled (policies.RangeGuard, D3IL_POLICY_RANGE_GUARD=1 or a Sim's policy_range_guard=True)")
+        rep = g.read()
+        rep["weights_out_of_range"] = self.weights_out_of_range()
+        return rep
+
+    def _state(self, n):
+        """The observation window and the action ring for n lanes; a new size starts empty."""
+        if self.hist is None or self.hist.buf.shape[0] != n:
+            self.hist = _History(n, self.W, self.obs_dim, self.device)
+            self.a_hist = torch.zeros(n, self.W - 1, self.A, dtype=torch.float32, device=self.device)
+
+    def reset(self):
+        if self.hist is not None:
+            self.hist.reset()
+
+    def begin_episodes(self, mask):
+        """Lanes that start a new trajectory: window length 0 (in place).  Their ring entries are not read again before they are overwritten."""
+        if self.hist is not None:
+            self.hist.reset_(mask)
+
+    def fork(self):
+        """A clone for another sub-batch: network, scaler and schedule shared; step word and packed tables its own, empty histories."""
+        c = super().fork()
+        c.hist = c.a_hist = None
+        return c
+
+    def load_reference_state_dict(self, sd):
+        """``GCDenoiser.state_dict()`` of the reference: the transformer sits under ``inner_model.``."""
+        own = self.model.state_dict()
+        self.model.load_state_dict({k[len("inner_model."):]: v for k, v in sd.items() if k.startswith("inner_model.") and k[len("inner_model."):] in own})
+
+    # ---- packed tables
+    def _pack_params(self):
+        m = self.model
+        return list(m.sigma_emb.parameters()) + [m.action_emb.bias, m.pos_emb]
+
+    def _pack(self):
+        """semb [S, C] = sigma_emb(log(sigma) / 4) of the S noise levels; coef [S, 6] (beso_coefficients); bias_pos [W, C] = action_emb.bias + pos_emb[:W]."""
+        m, dev = self.model, self.model.pos_emb.device
+        sig = torch.tensor(self.sigmas[:-1], dtype=torch.float32, device=dev)
+        return {"semb": m.sigma_emb(sig.reshape(-1, 1).log() / 4).to(torch.float32).contiguous(),
+                "coef": torch.tensor(self._coef, dtype=torch.float64).to(device=dev, dtype=torch.float32).contiguous(),
+                "bias_pos": (m.action_emb.bias + m.pos_emb[0, :self.W]).to(torch.float32).contiguous()}
+
+    def invalidate_packed(self):
+        super().invalidate_packed()
+        for blk in self.model.blocks:
+            blk.invalidate_packed()
+
+    def ensure_packed(self):
+        """The packed tables (on the CPU too: the torch path reads them) and the blocks' packed weights follow the parameters (outside any capture)."""
+        self._packed.ensure(self._pack_params(), self._pack)
+        if self.model.pos_emb.is_cuda:
+            ensure_blocks_packed(self.model.blocks)
+
+    # ---- one step of the chain
+    def step_kernel_ok(self, dev) -> bool:
+        m = self.model
+        C = m.embed_dim
+        return (dev.type == "cuda" and isinstance(m.action_pred, nn.Linear) and m.pos_emb.dtype == torch.float32 and C <= 128 and C % 4 == 0 and 1 <= self.A <= 8
+                and 1 <= self.W <= 16 and 1 <= self.S <= 254 and self._switch_on())
+
+    def _noise(self, d, n, dev):
+        """The normals of draw index d as the torch path takes them: ``noise_in(d, n)`` or the host form of the kernel's Philox draw."""
+        return self._draw(self.noise_in and (lambda n: self.noise_in(d, n)), n, (n, self.W, self.A),
+                          lambda t: beso_normals(self.seed, self.env_offset, n, t, d, self.W, self.A), True, dev)
+
+    def _step_torch(self, st, i, hk):
+        """Steps 1 - 8 of csrc/policy_beso.h as torch ops, in the kernel's order of operations, on the chain state ``st`` (x, xbuf, bad, lengths, packed tables)."""
+        m, S, W, A = self.model, self.S, self.W, self.A
+        x, xbuf, w = st["x"], st["xbuf"], st["w"]
+        n = x.shape[0]
+        ln = st["len"].clamp(1, W)
+        jj = torch.arange(W, device=x.device)
+        valid = (jj < ln.unsqueeze(1)).unsqueeze(2)
+        last = i == S - 1
+        if i < 0:
+            nz = self._noise(0, n, x.device)
+            noise = torch.zeros_like(x)
+            noise[:, 0] = nz[:, 0]
+            xp = torch.where((jj == (ln - 1).unsqueeze(1)).unsqueeze(2), (self.sigma_max * nz[:, :1]).expand(-1, W, -1), torch.zeros_like(x))
+            if W > 1:
+                src = ((W - 1) - (ln - 1)).unsqueeze(1) + jj
+                prev = torch.gather(self.a_hist, 1, src.clamp(0, W - 2).unsqueeze(2).expand(-1, -1, A))
+                xp = torch.where((jj < (ln - 1).unsqueeze(1)).unsqueeze(2), prev, xp)
+            st["bad"].zero_()
+            hit = ~torch.isfinite(xp)
+            c_in = self.c_in0
+        else:
+            noise = torch.zeros_like(x) if last else self._noise(i + 1, n, x.device)
+            net = m.action_pred(m.ln_f(hk))
+            c = w["coef"][i]
+            den = c[1] * net + c[0] * x
+            d = (x - den) * c[2]
+            xp = x + d * c[3]
+            if not last:
+                xp = xp + c[4] * noise
+            hit = ~torch.isfinite(hk).all(dim=2, keepdim=True) | ~torch.isfinite(net) | ~torch.isfinite(x) | ~torch.isfinite(xp)
+            c_in = c[5]
+        st["bad"] |= (hit & valid).any(dim=2).any(dim=1).to(torch.int32)
+        xp = torch.where(valid, xp, torch.zeros_like(xp))
+        if self.record:
+            self.last_noise[i + 1] = noise
+        if not last:
+            x.copy_(xp)
+            xbuf[:, 0] = w["semb"][i + 1]
+            xbuf[:, 2::2] = w["bias_pos"] + (c_in * xp) @ m.action_emb.weight.t()
+        else:
+            newest = xp.gather(1, (ln - 1).view(n, 1, 1).expand(-1, 1, A)).squeeze(1)
+            a_new = torch.minimum(torch.maximum(newest, self.min_action), self.max_action)
+            a_new = torch.where(st["bad"].bool().unsqueeze(1), torch.full_like(a_new, float("nan")), a_new)
+            st["actions"].copy_(self._action_tail(a_new, st["bad"], False))
+            if W > 1:
+                self.a_hist[:, :-1] = self.a_hist[:, 1:].clone()
+                self.a_hist[:, -1] = a_new
+
+    def _step_kernel(self, st, i, hk):
+        from . import capi
+        m, w, dev = self.model, st["w"], st["x"].device
+        n = st["x"].shape[0]
+        noise_in = self._noise(i + 1, n, dev) if (self.noise_in is not None and i < self.S - 1) else None
+        noise_out = torch.empty(n, self.W, self.A, dtype=torch.float32, device=dev) if self.record else None
+        assert hk is None or hk.is_contiguous()
+        assert m.action_pred.weight.is_contiguous() and m.action_emb.weight.is_contiguous() and self.a_hist.is_contiguous()
+        capi.launch("d3il_beso_step", dev, hk=hk, ln_weight=m.ln_f.weight, ln_bias=m.ln_f.bias, ln_eps=float(m.ln_f.eps), w_pred=m.action_pred.weight,
+                    b_pred=m.action_pred.bias, w_aemb=m.action_emb.weight, bias_pos=w["bias_pos"], semb=w["semb"], coef=w["coef"], sigma_max=self.sigma_max,
+                    c_in0=self.c_in0, **self._draw_args(), len=st["len"], noise_in=noise_in, x=st["x"], xbuf=st["xbuf"], a_hist=self.a_hist if self.W > 1 else None,
+                    actions=st["actions"], bad=st["bad"], noise_out=noise_out, n_env=n, C=m.embed_dim, A=self.A, W=self.W, S=self.S, i=i)
+        if self.record:
+            self.last_noise[i + 1] = noise_out
+
+    @torch.no_grad()
+    def predict_batch(self, obs):
+        s = self.scaler.scale_input(obs.to(device=self.device, dtype=torch.float32))
+        assert s.dim() == 2 and s.shape[1] == self.obs_dim, "BESONativePolicy: observation width %d, the network takes %d" % (s.shape[-1], self.obs_dim)
+        m, W, S = self.model, self.W, self.S
+        n, dev = s.shape[0], s.device
+        if s.is_cuda and not _ENV_GUARD_TRIED and self.f16x3_blocks:
+            _env_range_guard(dev)
+        if not (s.is_cuda and _capturing()):
+            self.ensure_packed()
+        assert self._packed.key is not None, "a captured graph replays the packed tables: call ensure_packed() before capturing"
+        w = self._packed.buf
+        self._state(n)
+        self.hist.append_(s)
+        states, ln = self.hist.padded()
+        C = m.embed_dim
+        st = dict(x=torch.empty(n, W, self.A, dtype=torch.float32, device=dev), xbuf=torch.empty(n, 2 * W + 1, C, dtype=torch.float32, device=dev),
+                  actions=torch.empty(n, self.A, dtype=torch.float32, device=dev), bad=torch.empty(n, dtype=torch.int32, device=dev), len=ln.contiguous(), w=w)
+        # 1. the state tokens: the same in every sampling step
+        torch.add(m.tok_emb(states), m.pos_emb[0, :W, :], out=st["xbuf"][:, 1::2])
+        if getattr(self, "_keep", None) is None or self._keep.device != dev:
+            self._keep = torch.arange(2, 2 * W + 1, 2, device=dev)
+        kernel = self.step_kernel_ok(dev)
+        if not kernel:
+            self._warn_fallback(s, lambda: "the step kernel is built for a linear head, n_embd <= 128 (a multiple of 4), 1 .. 8 action components, a window of 1 .. 16: torch glue")
+        step = self._step_kernel if kernel else self._step_torch
+        if self.record:
+            self.last_noise = {}
+        step(st, -1, None)                                                   # 2. the first iterate, its tokens, the sigma token of step 0
+        for i in range(S):                                                   # 3. S times: the blocks, then everything up to the next token buffer
+            step(st, i, m.hidden(st["xbuf"], self._keep).contiguous())
+        self._t.add_(1)                                                      # 4. the step word
+        self.last_bad = st["bad"]
+        return st["actions"]
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, embed_dim: int = 120, n_layers: int = 6, n_heads: int = 6, window_size: int = 5,
+               num_sampling_steps: int = 16, sigma_min: float = 0.01, sigma_max: float = 1.0, action_scale: float = 0.002, noise_in=None, policy_seed: int = 0,
+               linear_output: bool = True):
+        """A policy of the reference's Stacking shape (6 layers, 6 heads, 120 wide, window 5, 16 sampling steps, sigma 0.01 .. 1) with fixed random weights - there
+        are no checkpoints offline (as DDPMGPTPolicy.random): torch's default layer initialisation, position rows of standard deviation 0.1, a head of roughly unit
+        output, unit observation scaling, actions of ``action_scale`` per unit of the scaled space, bounds +-1.5."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            net = DiffusionGPT(obs_dim, action_dim, embed_dim, n_layers, n_heads, window_size, linear_output=linear_output)
+        with torch.no_grad():
+            net.pos_emb.copy_(torch.randn(net.pos_emb.shape, generator=g) * 0.1)
+            if linear_output:
+                net.action_pred.weight.copy_(torch.randn(net.action_pred.weight.shape, generator=g) * (1.0 / embed_dim ** 0.5))
+        return cls(net.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, 1.5, device), window_size, num_sampling_steps, sigma_min, sigma_max,
+                   seed=policy_seed, noise_in=noise_in)
 
 
 # ------------------------------------------------------------------------------------------------ Implicit BC: Langevin chain on an energy network

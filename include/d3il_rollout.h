@@ -242,6 +242,27 @@ int d3il_ddpm_gpt_step_f32(const float* hk, const float* ln_weight, const float*
                            const float* bias_pos, const float* temb, const float* sched, const float* lo, const float* hi, const float* scale, const float* shift,
                            const int64_t* len, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* noise_in, float* x, float* xbuf, float* actions,
                            int32_t* bad, float* noise_out, long n_env, int C, int A, int W, int T, int k, void* stream);
+/* Everything between two block chains of the batched BESO sampler (policies.BESONativePolicy; beso_agent.py:316-443, gc_sampling.py:107-114 and 217-256 around
+ * score_wrappers.py GCDenoiser and score_gpts.py DiffusionGPT; sampler euler_ancestral, linear noise schedule, no goals) in one launch, f32 throughout, in the
+ * reference's order of operations.  i = 0 .. S - 1 are the sampling steps, i = -1 the init mode.  For environment n and window position j < W:
+ * z = LayerNorm(hk[n][j]); net_a = w_pred[a] . z + b_pred[a]; den_a = coef[i][1] net_a + coef[i][0] x_a; d_a = (x_a - den_a) coef[i][2]; x'_a = x_a + d_a coef[i][3];
+ * i < S - 1: x'_a += coef[i][4] noise_a, x[n][j] = x', xbuf[n][2 + 2 j][c] = sum_a w_aemb[c][a] (coef[i][5] x'_a) + bias_pos[j][c] and xbuf[n][0] = semb[i + 1];
+ * i = S - 1 (nothing is drawn): a_new = clamp(x'_a, lo_a, hi_a) at j = len[n] - 1, actions[n][a] = a_new scale_a + shift_a, and a_new is pushed onto the action ring
+ * a_hist[n] in place (entries move down by one, a_new becomes the last).  Init mode (hk is not read and may be NULL; bad is cleared): x'[j] = a_hist[n][(W - 1) -
+ * (len[n] - 1) + j] for j < len[n] - 1, x'[len[n] - 1] = sigma_max noise, tokens with c_in0 and semb[0].  Positions j >= len[n]: x' = 0, the token is bias_pos[j].
+ * coef [S][6] = (c_skip, c_out, 1 / s_from, s_down - s_from, s_up, c_in of the NEXT sigma) of the Karras preconditioner and the ancestral step, built on the host.
+ * noise_a = noise_in[n][j][a] when given (the [n_env][W][A] slice of THIS draw; the init mode reads row j = 0 only), otherwise Box-Muller normals as
+ * d3il_ddpm_gpt_step_f32 on Philox4x32-10 with key = seed and counter = (env_offset + n, *t_device, 0x42530000 | draw << 8 | j << 1 | q), component a = 4 q + m;
+ * draw 0 with j = 0 is the init draw (one per environment), draw i + 1 the one of step i.  hk [n_env][W][C], w_pred [A][C], w_aemb [C][A] (nn.Linear weights as they
+ * are), bias_pos [W][C], semb [S][C], lo / hi (scaled space) / scale / shift [A], len i64 [n_env] (clamped to 1 .. W), t_device: DEVICE u32, x [n_env][W][A] (in /
+ * out), xbuf [n_env][2 W + 1][C], a_hist [n_env][W - 1][A] (newest entry last; may be NULL when W = 1), noise_out [n_env][W][A] may be NULL.  bad i32 [n_env]: sticky
+ * from the init launch on - set by a NaN / Inf in a valid hidden row, normalised row or iterate; at i = S - 1 such an environment gets NaN in every action component
+ * and in the ring entry it pushes.  Built for C <= 128 (a multiple of 4), 1 <= A <= 8, 1 <= W <= 16, 1 <= S <= 254: D3IL_EUNSUPPORTED otherwise, answered before
+ * any launch.  (No _f32 suffix: capi.SIGNATURES2 holds this entry.) */
+int d3il_beso_step(const float* hk, const float* ln_weight, const float* ln_bias, float ln_eps, const float* w_pred, const float* b_pred, const float* w_aemb,
+                   const float* bias_pos, const float* semb, const float* coef, float sigma_max, float c_in0, const float* lo, const float* hi, const float* scale,
+                   const float* shift, const int64_t* len, uint64_t seed, uint64_t env_offset, const uint32_t* t_device, const float* noise_in, float* x, float* xbuf,
+                   float* a_hist, float* actions, int32_t* bad, float* noise_out, long n_env, int C, int A, int W, int S, int i, void* stream);
 /* The whole inference of the batched Implicit-BC policy (policies.IBCPolicy; ibc_agent.py:248-286, samplers/langevin_mcmc.py:129-163,236-286, ebms.py:21-51) in one
  * launch, f32 throughout: per environment S = 64 samples, K Langevin iterations on the energy network E([state | x]) (ResidualMLPNetwork, Mish, one output) with the
  * analytic gradient, then a categorical draw from softmax(-E) of the final samples.  x_a starts at x0_in[n][s][a] or lo_a + u (hi_a - lo_a); iteration k:
