@@ -99,16 +99,18 @@ class RowwiseAgent:
 
 def as_batched(agent, n_envs: int | None = None):
     """What the batched sims call: agents that provide ``predict_batch`` (the adapters of this module, or any policy written
-    for the batch) are used as they are; a reference ``BeT_Agent`` becomes a native ``policies.BeTPolicy``, a ``DiffusionAgent`` with the transformer denoiser a ``policies.DDPMGPTPolicy``, a ``BesoAgent`` with the euler_ancestral sampler on the linear schedule (no goals) a ``policies.BESONativePolicy``, an ``IBCAgent`` with the plain Langevin sampler a ``policies.IBCPolicy``, an ``ActAgent`` (VAE-ACT, no goals) a ``policies.ACTPolicy``, a ``CVAEAgent`` with a plain Mish decoder a ``policies.CVAEPolicy``, a ``DiffusionAgent`` with the encoder-decoder denoiser (DDPM-ACT, no goals) a ``policies.DDPMACTPolicy``, a ``BetMLP_Agent`` with a plain Mish network and 64 bins a ``policies.BeTMLPPolicy``, a ``Gpt_Agent`` (BC-GPT, state observations) a ``policies.GPTBCPolicy``; everything else is wrapped row by row with per-lane state."""
+    for the batch) are used as they are; a reference ``BeT_Agent`` becomes a native ``policies.BeTPolicy``, a ``DiffusionAgent`` with the transformer denoiser a ``policies.DDPMGPTPolicy``, a ``DiffusionAgent`` with the residual MLP denoiser (no goals) a ``policies.DDPMNativePolicy``, a ``BesoAgent`` with the euler_ancestral sampler on the linear schedule (no goals) a ``policies.BESONativePolicy``, an ``IBCAgent`` with the plain Langevin sampler a ``policies.IBCPolicy``, an ``ActAgent`` (VAE-ACT, no goals) a ``policies.ACTPolicy``, a ``CVAEAgent`` with a plain Mish decoder a ``policies.CVAEPolicy``, a ``DiffusionAgent`` with the encoder-decoder denoiser (DDPM-ACT, no goals) a ``policies.DDPMACTPolicy``, a ``BetMLP_Agent`` with a plain Mish network and 64 bins a ``policies.BeTMLPPolicy``, a ``Gpt_Agent`` (BC-GPT, state observations) a ``policies.GPTBCPolicy``; everything else is wrapped row by row with per-lane state."""
     if hasattr(agent, "predict_batch"):
         if not hasattr(agent, "reset"):
             agent.reset = lambda: None
         return agent
-    from .policies import ACTPolicy, BESONativePolicy, BeTMLPPolicy, BeTPolicy, CVAEPolicy, DDPMACTPolicy, DDPMGPTPolicy, GPTBCPolicy, IBCPolicy
+    from .policies import ACTPolicy, BESONativePolicy, BeTMLPPolicy, BeTPolicy, CVAEPolicy, DDPMACTPolicy, DDPMGPTPolicy, DDPMNativePolicy, GPTBCPolicy, IBCPolicy
     if BeTPolicy.matches(agent):      # the reference's BeT_Agent: one batched forward + the sampling-head kernel per step instead of one predict per environment
         return BeTPolicy.from_reference(agent)
     if DDPMGPTPolicy.matches(agent):      # the reference's DiffusionAgent around a DiffusionTransformerNetwork: the batched sampler with the fused step kernel
         return DDPMGPTPolicy.from_reference(agent)
+    if DDPMNativePolicy.matches(agent):      # the reference's DiffusionAgent around a residual-style DiffusionMLPNetwork without goals: the whole reverse chain in one kernel per step
+        return DDPMNativePolicy.from_reference(agent)
     if BESONativePolicy.matches(agent):      # the reference's BesoAgent around GCDenoiser(DiffusionGPT), euler_ancestral on the linear schedule: the batched sampler with the fused step kernel
         return BESONativePolicy.from_reference(agent)
     if IBCPolicy.matches(agent):      # the reference's IBCAgent with the plain Langevin sampler, polynomial schedule, no goals: the whole chain in one kernel per step

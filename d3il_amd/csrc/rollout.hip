@@ -34,6 +34,7 @@ constexpr int WAVE = 64;
 #include "policy_ddpm_act.h"
 #include "policy_f32.h"
 #include "policy_cvae.h"
+#include "policy_ddpm_mlp.h"
 #include "policy_bet_mlp.h"
 #include "policy_gpt_bc.h"
 
@@ -1600,6 +1601,29 @@ int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_i
   const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
   if (hidden == 128) hipLaunchKernelGGL(k_cvae_decode<128>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_cvae_decode<256>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_ddpm_mlp_chain(const uint32_t* t_device, const float* state, const float* w_x, const float* w_state, const float* tbias, const float* w_blocks, const float* b_blocks,
+                        const float* w_out, const float* b_out, const float* sched, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed,
+                        uint64_t env_offset, const float* noise_in, float* actions, int32_t* bad, float* noise_out, long n_env, int obs_dim, int A, int t_dim, int n_timesteps,
+                        int hidden, int n_blocks, void* stream) {
+  // (t_dim is folded into tbias by the packer; the entry takes it to hold the network to the 64 input columns this tiling is built for)
+  if ((hidden != 128 && hidden != 256) || A < 1 || A > DM_AMAX || obs_dim < 1 || t_dim < 1 || (long)A + t_dim + obs_dim > DM_INMAX || n_timesteps > DM_TMAX || n_blocks < 0 || n_env > 0x7FFFFFFFL * 16)
+    return fail(D3IL_EUNSUPPORTED, "d3il_ddpm_mlp_chain: built for hidden 128 / 256, 1 .. 8 action components, obs_dim >= 1 with A + t_dim + obs_dim <= 64 input columns, 1 .. 255 timesteps and n_blocks >= 0");
+  if (n_timesteps < 1) return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: needs at least one timestep");
+  if (!t_device || !state || !w_x || !w_state || !tbias || !w_blocks || !b_blocks || !w_out || !b_out || !sched || !lo || !hi || !scale || !shift || !actions || !bad)
+    return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: negative environment count");
+  if (((uintptr_t)w_x | (uintptr_t)w_state | (uintptr_t)tbias | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_out) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: the packed weights, the bias table and the block biases must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  DdpmMlpArgs a{t_device, state, w_x, w_state, tbias, w_blocks, b_blocks, w_out, b_out, sched, lo, hi, scale, shift, noise_in, actions, bad, noise_out,
+                (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, n_timesteps, n_blocks};
+  // one workgroup of eight waves per 16 environments; the last one may be partly filled
+  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
+  if (hidden == 128) hipLaunchKernelGGL(k_ddpm_mlp_chain<128>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_ddpm_mlp_chain<256>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

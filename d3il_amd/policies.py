@@ -1962,8 +1962,238 @@ class DDPMGPTPolicy(NativePolicy):
         return cls(den.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, 1.5, device), n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)
 
 
+# ------------------------------------------------------------------------------------------------ DDPM with the MLP denoiser on the Philox stream
+DDPM_MLP_TAG = 0x444D0000     # fourth Philox counter word of the chain kernel, or-ed with k << 1 | q (csrc/policy_ddpm_mlp.h; its upper half is no other tag's)
+
+
+def ddpm_mlp_words(seed: int, env_offset: int, n: int, t: int, k: int):
+    """The Philox words behind ``ddpm_mlp_normals``: uint32 [n, 2 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t,
+    DDPM_MLP_TAG | k << 1 | q))."""
+    assert 0 <= k <= 254, "the chain draws k = 0 .. T - 1 with T <= 255"
+    q, = _tag_axes(2)
+    return philox_words(seed, env_offset, n, t, np.uint64(DDPM_MLP_TAG | (k << 1)) | q)
+
+
+def ddpm_mlp_normals(seed: int, env_offset: int, n: int, t: int, k: int, A: int):
+    """The chain kernel's normals of environments 0 .. n-1 at step word t and draw index k (0: the first iterate, 1 + (T - 1 - i): the noise of reverse step i > 0), on
+    the host: float64 [n, A].  Exact on the 32-bit words (``ddpm_mlp_words``: two calls q per row) and f64 from there on (``box_muller_f64``); component a = 4 q + m."""
+    assert 1 <= A <= 8
+    return box_muller_f64(ddpm_mlp_words(seed, env_offset, n, t, k)).reshape(n, 8)[:, :A]
+
+
+def pack_ddpm_mlp_weights(model: DiffusionMLP, n_timesteps: int) -> dict:
+    """The denoiser of a DDPM-MLP policy for k_ddpm_mlp_chain.  The input layer W_in on the row [x (A) | time embedding (t_dim) | state] is split by what its columns
+    depend on: ``w_x`` [NT][64][2], the A columns of x packed to 8 in the input-layer order of ``pack_resmlp_weights`` ([T_out][lane (g, i)][s] = W[16 T_out + i][4 s +
+    g]); ``w_state`` [NT][64][16], the state columns packed to 64 in the same order; ``tbias`` [T][H] = W_in[:, A : A + t_dim] temb[i] + b_in with ``temb`` [T][t_dim] =
+    temp_layers(arange(T)) - the time embedding is the same for every row.  Blocks and output layer as ``pack_resmlp_weights`` packs them."""
+    from types import SimpleNamespace
+    lin_in, blocks, lin_out = model.layers._parts()
+    H, A, td, W = lin_in.out_features, lin_out.out_features, model.temp_layers[-1].out_features, lin_in.weight
+    part = lambda a, b: SimpleNamespace(weight=W[:, a:b], bias=lin_in.bias, in_features=b - a, out_features=H)
+    pk = pack_resmlp_weights(part(A + td, W.shape[1]), blocks, lin_out, in_cols=64)
+    pk["w_state"] = pk.pop("w_in")
+    del pk["b_in"]
+    pk["w_x"] = pack_resmlp_weights(part(0, A), [], lin_out, in_cols=8)["w_in"]
+    f = lambda x: x.detach().to(torch.float32).contiguous()
+    pk["temb"] = f(model.temp_layers(torch.arange(n_timesteps, device=W.device)))
+    pk["tbias"] = f(pk["temb"] @ W[:, A:A + td].t().to(torch.float32) + lin_in.bias)
+    return pk
+
+
+class DDPMNativePolicy(NativePolicy):
+    """DiffusionAgent.predict (agents/ddpm_agent.py:213-274) around Diffusion.sample (gc_diffusion.py:101-216) with the MLP denoiser (diffusion_models.py:20-118 over
+    common/mlp.py ResidualMLPNetwork, Mish, not goal conditioned) on a batch, on the Philox stream - BASELINE config 4's policy as a NativePolicy, next to the older
+    DDPMPolicy (torch.randn on the device generator, one kernel shape), which bench.py keeps using.  Scale the observation, x = z_0, T reverse steps - eps =
+    ResidualMLP([x | temb[i] | s]), x0 = clamp(sra[i] x - srm1[i] eps, lo, hi) in scaled space, x = (c1[i] x0 + c2[i] x) + sig[i] z_k, nothing drawn at i = 0 -, final
+    clamp, inverse scaling (product and sum in f32: DDPMGPTPolicy's tail.  The reference's scaler holds f64 statistics, agents/utils/scaler.py:29-36,106-110, so its
+    f32 x times f64 std plus f64 mean is an f64 product and sum of the same operands; rounding that to f32 and this tail differ by at most one f32 rounding of
+    the product, far inside the reference's own f32 error of the chain).
+
+    No history, whatever ``window_size`` is: the MLP denoiser acts on every window position independently (the reference concatenates [x | t | state] along the last
+    axis of a [1, L, .] window and runs Linear layers on it: position l of the output reads position l of the input only), ``Diffusion.sample`` draws one normal per
+    position, and DiffusionAgent.predict returns position -1 only (ddpm_agent.py:262-264).  So the action is a function of the NEWEST observation and of the draws of
+    the newest position alone; the older positions are computed by the reference and thrown away.  ``window_size >= 1`` is accepted and ignored, ``reset`` and
+    ``begin_episodes`` do nothing; tests/golden/ref_ddpm_mlp_agent.npz pins this against the reference at window 5.  (As shipped, DiffusionMLPNetwork.forward raises on
+    a window of two or more - it concatenates a [batch, 1, t_dim] time embedding with the [batch, L, .] window, diffusion_models.py:95-104 -, so a live reference agent
+    runs this denoiser at window 1 only; the fixture's window case runs the reference with the embedding broadcast over the positions)
+
+    On a HIP device the whole call is ONE kernel (csrc/policy_ddpm_mlp.h through d3il_ddpm_mlp_chain: hidden 128 / 256, 1 <= A <= 8, A + t_dim + obs <= 64 input
+    columns, 1 <= T <= 255, any number of blocks), then a device-side add on the step word, so a captured graph draws fresh numbers at every replay.  On the CPU, for
+    other shapes and with D3IL_POLICY_DDPM_MLP_CHAIN=0 the same arithmetic in the same order runs as torch ops (``_chain_torch``) with the Philox normals computed
+    on the host - that path cannot be captured.  The noise is Box-Muller on Philox4x32-10 keyed by ``seed`` with counter (env_offset + lane, step word,
+    DDPM_MLP_TAG | k << 1 | q), k = 0 for z_0 and k = 1 + (T - 1 - i) for reverse step i > 0 - T draws per call -, so results do not depend on batch order,
+    sub-batches or ranks (``ddpm_mlp_normals`` is the host form); or ``noise_in(k, n) -> [n, A]`` when given (golden replay, tests).  ``last_bad`` i32 [n] marks
+    the environments with a NaN / Inf in their scaled state row, in a draw they use, in an eps or in their final x - their actions are NaN -; with ``record``,
+    ``last_noise`` [T + 1, n, A] is what was drawn (the last entry, step i = 0, is zeros)."""
+
+    def __init__(self, model: DiffusionMLP, scaler: Scaler, n_timesteps: int, window_size: int = 1, seed: int = 0, noise_in=None):
+        self.model, self.scaler, self.T, self.W = model.eval(), scaler, int(n_timesteps), int(window_size)
+        assert 1 <= self.T <= 255, "the Philox counter layout holds T <= 255"
+        assert self.W >= 1
+        dev = scaler.x_mean.device
+        self.device = dev
+        lin_in, _, lin_out = model.layers._parts()
+        self.A, self.t_dim = int(lin_out.out_features), int(model.temp_layers[-1].out_features)
+        self.obs_dim = int(lin_in.in_features) - self.A - self.t_dim
+        assert 1 <= self.A <= 8, "the Philox counter layout holds at most 8 action components"
+        assert self.obs_dim >= 1, "the denoiser reads [x | time embedding | state]"
+        self._sched = ddpm_schedule(cosine_beta_schedule(self.T).to(dev))["sched"]
+        self._init_output(scaler)
+        self._init_stream(seed)
+        self.noise_in = noise_in
+        self.record = False           # also keep what the call drew (last_noise)
+        self.last_bad = self.last_noise = None
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, noise_in=None, device=None):
+        """From a live reference ``DiffusionAgent`` (duck-typed) whose ``model`` is a ``Diffusion`` around a residual-style ``DiffusionMLPNetwork``: the denoiser's state
+        dict (widths and block count read from the keys), ``n_timesteps``, ``agent.scaler``, ``agent.window_size``; with ``agent.use_ema`` the EMA shadow parameters
+        (the reference swaps them in for every predict)."""
+        diff = agent.model
+        sd = {k: torch.as_tensor(v) for k, v in diff.model.state_dict().items()}
+        dev = torch.device(device) if device is not None else sd["layers.layers.0.weight"].device
+        H, in_dim = sd["layers.layers.0.weight"].shape
+        t_dim = sd["temp_layers.3.weight"].shape[0]
+        last = max(int(k.split(".")[2]) for k in sd if k.startswith("layers.layers."))
+        A = sd["layers.layers.%d.weight" % last].shape[0]
+        den = DiffusionMLP(A, in_dim - A - t_dim, t_dim, H, 2 * len({k.split(".")[2] for k in sd if ".l1." in k}))
+        den.load_state_dict(sd)
+        den = den.to(dev).requires_grad_(False)
+        pol = cls(den, Scaler.from_reference(agent.scaler, dev), int(diff.n_timesteps), int(agent.window_size), seed=seed, noise_in=noise_in)
+        if getattr(agent, "use_ema", False):
+            pol.use_ema(agent.ema_helper.shadow_params)
+        return pol
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Does ``agent`` look like the reference's DiffusionAgent around a residual-style DiffusionMLPNetwork without goals (``temp_layers`` and ``layers``, none of the
+        transformer denoisers' ``time_emb`` / ``action_emb`` / ``blocks`` / ``encoder`` / ``decoder``; plain ``nn.Linear`` layers and Mish blocks without norm, dropout or
+        spectral norm; at most 8 action components), configured as the sampler restated here (``model.betas`` = the cosine schedule, epsilon prediction, clip_denoised,
+        neither diffusion_x nor diffusion_kde, 1 <= T <= 255)?  Everything else stays on the row-by-row adapter, which runs the reference's own code."""
+        try:
+            diff = agent.model
+            net = diff.model
+            if not (hasattr(net, "temp_layers") and hasattr(net, "layers") and hasattr(net, "state_dict")) or any(hasattr(net, k) for k in ("time_emb", "action_emb", "blocks", "encoder", "decoder")):
+                return False
+            if net.goal_conditioned is not False or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None or int(agent.window_size) < 1:
+                return False
+            layers, temp = list(net.layers.layers), list(net.temp_layers)
+            if not ResidualMLP.is_plain(layers, strict=True) or any(float(getattr(getattr(b, "dropout", None), "p", 0.0)) != 0.0 for b in layers[1:-1]):
+                return False
+            if len(temp) != 4 or type(temp[1]) is not nn.Linear or not isinstance(temp[2], nn.Mish) or type(temp[3]) is not nn.Linear:
+                return False
+            A, t_dim = layers[-1].out_features, temp[3].out_features
+            if not 1 <= A <= 8 or temp[1].in_features != t_dim or layers[0].in_features - A - t_dim < 1:
+                return False
+            if getattr(diff, "diffusion_x", False) or getattr(agent, "diffusion_kde", False) or not getattr(diff, "predict_epsilon", True) or not getattr(diff, "clip_denoised", True):
+                return False
+            T = int(diff.n_timesteps)
+            betas = torch.as_tensor(diff.betas).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+            return 1 <= T <= 255 and betas.shape[0] == T and bool(torch.equal(betas, cosine_beta_schedule(T)))
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
+    SWITCH, LAST, TAKES = "D3IL_POLICY_DDPM_MLP_CHAIN", ("last_bad", "last_noise"), "the denoiser takes %d next to the action and the time embedding"
+
+    def begin_episodes(self, mask):
+        pass      # (no history: see the class docstring)
+
+    def load_reference_state_dict(self, sd):
+        """``Diffusion.state_dict()`` of the reference: the denoiser sits under ``model.``."""
+        self.model.load_state_dict({k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")})
+
+    def _pack(self):
+        """pack_ddpm_mlp_weights of the denoiser (kernel order, ``temb``, ``tbias``), the schedule table [T, 5] (ddpm_schedule: the one DDPMPolicy packs, sig[0] = 0) and
+        the action bounds (lo | hi)."""
+        dev = self.model.layers.layers[0].weight.device
+        fw = pack_ddpm_mlp_weights(self.model, self.T)
+        fw["sched"] = self._sched.to(device=dev, dtype=torch.float32).contiguous()
+        fw["bounds"] = torch.cat((self.lo.reshape(-1), self.hi.reshape(-1))).to(device=dev, dtype=torch.float32).contiguous()
+        return fw
+
+    def _kernel_shape(self) -> bool:
+        lin_in = self.model.layers._parts()[0]
+        return lin_in.out_features in (128, 256) and 1 <= self.A <= 8 and lin_in.in_features <= 64 and 1 <= self.T <= 255
+
+    # ---- the chain
+    def _noise(self, k, n, dev, need_host: bool):
+        """The normals of draw k, [n, A] (``_draw``)."""
+        return self._draw(self.noise_in and (lambda n: self.noise_in(k, n)), n, (n, self.A), lambda t: ddpm_mlp_normals(self.seed, self.env_offset, n, t, k, self.A), need_host, dev)
+
+    def _chain_torch(self, s, noise):
+        """Steps 1 - 3 of csrc/policy_ddpm_mlp.h as torch ops in the dtype of ``s`` (f32 in the policy), in the kernel's order of operations - the input layer as
+        (time share + x share) + state share - on the draws ``noise`` [T, n, A]: returns (actions, bad)."""
+        dt, dev, A, td = s.dtype, s.device, self.A, self.t_dim
+        m = self.model
+        lin_in, blocks, lin_out = m.layers._parts()
+        c = lambda p: p.to(device=dev, dtype=dt)
+        W, noise = c(lin_in.weight), c(noise)
+        tbias = c(m.temp_layers(torch.arange(self.T, device=lin_in.weight.device))) @ W[:, A:A + td].t() + c(lin_in.bias)
+        xs = s @ W[:, A + td:].t()
+        sched, lo, hi = c(self._sched), c(self.lo), c(self.hi)
+        x = noise[0]
+        bad = ~torch.isfinite(s).all(dim=1) | ~torch.isfinite(x).all(dim=1)
+        for step in range(self.T):
+            i = self.T - 1 - step
+            h = (tbias[i] + x @ W[:, :A].t()) + xs
+            for l1, l2 in blocks:
+                h = h + F.linear(F.mish(F.linear(F.mish(h), c(l1.weight), c(l1.bias))), c(l2.weight), c(l2.bias))
+            eps = F.linear(h, c(lin_out.weight), c(lin_out.bias))
+            sc = sched[i]
+            x0 = torch.minimum(torch.maximum(sc[0] * x - sc[1] * eps, lo), hi)
+            x = sc[2] * x0 + sc[3] * x
+            bad |= ~torch.isfinite(eps).all(dim=1)
+            if i > 0:
+                z = noise[step + 1]
+                bad |= ~torch.isfinite(z).all(dim=1)
+                x = x + sc[4] * z
+        bad |= ~torch.isfinite(x).all(dim=1)
+        return self._action_tail(x, bad, False, self.lo, self.hi), bad
+
+    def _step_torch(self, s):
+        n, dev = s.shape[0], s.device
+        noise = torch.stack([self._noise(k, n, dev, True) for k in range(self.T)])
+        y, bad = self._chain_torch(s, noise)
+        self.last_bad = bad.to(torch.int32)
+        self.last_noise = torch.cat((noise, torch.zeros_like(noise[:1]))) if self.record else None
+        return y
+
+    def _step_kernel(self, s):
+        from . import capi
+        n, dev = s.shape[0], s.device
+        w = self._packed.current(self._pack_params(), self._pack)
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        bad = torch.empty(n, dtype=torch.int32, device=dev)
+        noise_in = torch.stack([self._noise(k, n, dev, False) for k in range(self.T)]).contiguous() if self.noise_in is not None else None
+        noise_out = torch.empty(self.T + 1, n, self.A, dtype=torch.float32, device=dev) if self.record else None
+        lin_in, blocks, _ = self.model.layers._parts()
+        capi.launch("d3il_ddpm_mlp_chain", dev, state=s, w_x=w["w_x"], w_state=w["w_state"], tbias=w["tbias"], w_blocks=w["w_blk"], b_blocks=w["b_blk"], w_out=w["w_out"],
+                    b_out=w["b_out"], sched=w["sched"], **self._draw_args(), noise_in=noise_in, actions=y, bad=bad, noise_out=noise_out, n_env=n, obs_dim=self.obs_dim,
+                    A=self.A, t_dim=self.t_dim, n_timesteps=self.T, hidden=lin_in.out_features, n_blocks=len(blocks))
+        self.last_bad, self.last_noise = bad, noise_out
+        return y
+
+    def _fallback_text(self):
+        lin_in = self.model.layers._parts()[0]
+        return ("this denoiser (hidden %d, %d input columns, %d action components, %d timesteps) is not one the chain kernel is built for; every call runs torch's "
+                "layers with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)" % (lin_in.out_features, lin_in.in_features, self.A, self.T))
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 256, n_blocks: int = 4, t_dim: int = 8, n_timesteps: int = 4,
+               window_size: int = 1, action_scale: float = 0.002, policy_seed: int = 0, bound: float = 1.5, noise_in=None):
+        """A policy of the reference's shape with fixed random weights (there are no checkpoints offline; the defaults are Sorting-4: hidden 256, 8 hidden layers, t_dim
+        8, 4 timesteps): torch's default layer initialisation under ``seed`` (the global generator is left alone), unit observation scaling, actions of
+        ``action_scale`` per unit of the scaled space, bounds +-``bound``."""
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            den = DiffusionMLP(action_dim, obs_dim, t_dim, hidden_dim, 2 * n_blocks)
+        return cls(den.requires_grad_(False).to(device), Scaler.unit(obs_dim, action_dim, action_scale, bound, device), n_timesteps, window_size, seed=policy_seed, noise_in=noise_in)
+
+
 # ------------------------------------------------------------------------------------------------ BESO on the Philox stream
-BESO_TAG = 0x42530000         # fourth Philox counter word of the step kernel, or-ed with draw << 8 | j << 1 | q (csrc/policy_beso.h; its upper half is no other tag's)
+BESO_TAG = 0x42530000        # fourth Philox counter word of the step kernel, or-ed with draw << 8 | j << 1 | q (csrc/policy_beso.h; its upper half is no other tag's)
 
 
 def beso_words(seed: int, env_offset: int, n: int, t: int, d: int, W: int):

@@ -339,6 +339,24 @@ int d3il_ddpm_act_chunk_f32(const float* window, const int64_t* len, const float
 int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_out, const float* b_out,
                          const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const uint32_t* t_device,
                          const float* z_in, float* actions, float* z_out, long n_env, int obs_dim, int latent, int A, int hidden, int n_blocks, void* stream);
+/* The whole reverse chain of the batched DDPM-MLP policy (policies.DDPMNativePolicy; ddpm_agent.py:213-274 around gc_diffusion.py:101-216 over
+ * diffusion_models.py:20-118) in one launch, f32 throughout, on the Philox stream: per environment x = z_0; for i = n_timesteps - 1 .. 0: eps =
+ * ResidualMLPNetwork([x | temb[i] | state]) (Mish), x0 = clamp(sched[i][0] x - sched[i][1] eps, lo, hi), x = (sched[i][2] x0 + sched[i][3] x) + sched[i][4] z_k with
+ * k = 1 + (n_timesteps - 1 - i) (i = 0: nothing drawn or added); actions[n][a] = clamp(x_a, lo_a, hi_a) scale_a + shift_a (product and sum in f32).
+ * z_k = noise_in[k][n][a] when given, otherwise Box-Muller normals as d3il_ddpm_gpt_step_f32 on Philox4x32-10 with key = seed and counter = (env_offset + n,
+ * *t_device, 0x444D0000 | k << 1 | q), component a = 4 q + m; n_timesteps draws per call, k = 0 .. n_timesteps - 1.  t_device: DEVICE u32, read only.  state
+ * [n_env][obs_dim] (scaled).  The input layer comes split by column group (policies.pack_ddpm_mlp_weights): w_x [NT][64][2] the A columns of x packed to 8
+ * ([T_out][lane (g, i)][s] = W[16 T_out + i][4 s + g]; NT = hidden / 16), w_state [NT][64][16] the obs_dim state columns packed to 64 in the same order, tbias
+ * [n_timesteps][hidden] = W[:, A .. A + t_dim - 1] temb[i] + b_in; w_blocks .. b_out as d3il_resmlp_f32; sched [n_timesteps][5] (policies.ddpm_schedule);
+ * lo / hi (scaled space) / scale / shift [A].  noise_in [n_timesteps][n_env][A] may be NULL; noise_out [n_timesteps + 1][n_env][A] (what was used; the last entry,
+ * the step i = 0, is zeros) may be NULL.  bad i32 [n_env]: 1 for an environment with a NaN / Inf in its state row, in a draw it uses, in an eps or in its final x -
+ * it gets NaN in every action component -, 0 otherwise; no other environment changes.  Built for hidden 128 / 256, 1 <= A <= 8, obs_dim >= 1, A + t_dim + obs_dim
+ * <= 64 input columns, 1 <= n_timesteps <= 255, n_blocks >= 0: D3IL_EUNSUPPORTED otherwise (n_timesteps < 1: D3IL_EINVAL), answered before any launch.  Packed
+ * arrays 16-byte aligned.  (No _f32 suffix and the step word first: capi.SIGNATURES3 holds this entry.) */
+int d3il_ddpm_mlp_chain(const uint32_t* t_device, const float* state, const float* w_x, const float* w_state, const float* tbias, const float* w_blocks,
+                        const float* b_blocks, const float* w_out, const float* b_out, const float* sched, const float* lo, const float* hi, const float* scale,
+                        const float* shift, uint64_t seed, uint64_t env_offset, const float* noise_in, float* actions, int32_t* bad, float* noise_out, long n_env,
+                        int obs_dim, int A, int t_dim, int n_timesteps, int hidden, int n_blocks, void* stream);
 /* The whole inference of the batched BeT-MLP policy (policies.BeTMLPPolicy; bet_mlp_agent.py:366-406 around generate_latents, 114-147, and k_means.py
  * decode_actions) in one launch, f32: per environment h = the input layer and the residual blocks of the ResidualMLPNetwork (Mish) on the scaled state row,
  * logit_v = w_out[v] . h + b_out[v] for v < 64, p = exp(logit - max) with inclusive prefix sums c and S = c_63, u = u_in[n] or 24 bits of Philox4x32-10 (key = seed,
