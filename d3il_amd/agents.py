@@ -99,12 +99,12 @@ class RowwiseAgent:
 
 def as_batched(agent, n_envs: int | None = None):
     """What the batched sims call: agents that provide ``predict_batch`` (the adapters of this module, or any policy written
-    for the batch) are used as they are; a reference ``BeT_Agent`` becomes a native ``policies.BeTPolicy``, a ``DiffusionAgent`` with the transformer denoiser a ``policies.DDPMGPTPolicy``, a ``DiffusionAgent`` with the residual MLP denoiser (no goals) a ``policies.DDPMNativePolicy``, a ``BesoAgent`` with the euler_ancestral sampler on the linear schedule (no goals) a ``policies.BESONativePolicy``, an ``IBCAgent`` with the plain Langevin sampler a ``policies.IBCPolicy``, an ``ActAgent`` (VAE-ACT, no goals) a ``policies.ACTPolicy``, a ``CVAEAgent`` with a plain Mish decoder a ``policies.CVAEPolicy``, a ``DiffusionAgent`` with the encoder-decoder denoiser (DDPM-ACT, no goals) a ``policies.DDPMACTPolicy``, a ``BetMLP_Agent`` with a plain Mish network and 64 bins a ``policies.BeTMLPPolicy``, a ``Gpt_Agent`` (BC-GPT, state observations) a ``policies.GPTBCPolicy``; everything else is wrapped row by row with per-lane state."""
+    for the batch) are used as they are; a reference ``BeT_Agent`` becomes a native ``policies.BeTPolicy``, a ``DiffusionAgent`` with the transformer denoiser a ``policies.DDPMGPTPolicy``, a ``DiffusionAgent`` with the residual MLP denoiser (no goals) a ``policies.DDPMNativePolicy``, a ``BesoAgent`` with the euler_ancestral sampler on the linear schedule (no goals) a ``policies.BESONativePolicy``, an ``IBCAgent`` with the plain Langevin sampler a ``policies.IBCPolicy``, an ``ActAgent`` (VAE-ACT, no goals) a ``policies.ACTPolicy``, a ``CVAEAgent`` with a plain Mish decoder a ``policies.CVAEPolicy``, a ``DiffusionAgent`` with the encoder-decoder denoiser (DDPM-ACT, no goals) a ``policies.DDPMACTPolicy``, a ``BetMLP_Agent`` with a plain Mish network and 64 bins a ``policies.BeTMLPPolicy``, a ``Gpt_Agent`` (BC-GPT, state observations) a ``policies.GPTBCPolicy``, a ``BC_GMM_Agent`` (BC_Agent's contract around a ``BC_GMM`` in eval mode, plain Mish trunk, no tanh-wrapped distribution) a ``policies.BCGMMPolicy``; everything else is wrapped row by row with per-lane state."""
     if hasattr(agent, "predict_batch"):
         if not hasattr(agent, "reset"):
             agent.reset = lambda: None
         return agent
-    from .policies import ACTPolicy, BESONativePolicy, BeTMLPPolicy, BeTPolicy, CVAEPolicy, DDPMACTPolicy, DDPMGPTPolicy, DDPMNativePolicy, GPTBCPolicy, IBCPolicy
+    from .policies import ACTPolicy, BCGMMPolicy, BESONativePolicy, BeTMLPPolicy, BeTPolicy, CVAEPolicy, DDPMACTPolicy, DDPMGPTPolicy, DDPMNativePolicy, GPTBCPolicy, IBCPolicy
     if BeTPolicy.matches(agent):      # the reference's BeT_Agent: one batched forward + the sampling-head kernel per step instead of one predict per environment
         return BeTPolicy.from_reference(agent)
     if DDPMGPTPolicy.matches(agent):      # the reference's DiffusionAgent around a DiffusionTransformerNetwork: the batched sampler with the fused step kernel
@@ -125,6 +125,8 @@ def as_batched(agent, n_envs: int | None = None):
         return BeTMLPPolicy.from_reference(agent)
     if GPTBCPolicy.matches(agent):      # the reference's Gpt_Agent (BC-GPT) on state observations: one batched forward + the head kernel per step
         return GPTBCPolicy.from_reference(agent)
+    if BCGMMPolicy.matches(agent):      # a BC_GMM_Agent (BC_Agent's contract around the reference's BC_GMM) in eval mode: network, both draws and action tail in one kernel per step
+        return BCGMMPolicy.from_reference(agent)
     return RowwiseAgent(agent, n_envs)
 
 

@@ -6,7 +6,7 @@
 namespace d3il {
 
 // Philox4x32-10: key (k0, k1), counter (c0 .. c3) -> four words.  Every stream is key = seed, counter = (lo32, hi32 of env_offset + row, step word, tag): the
-// fourth word keeps the streams apart (0: the random-policy harness; BET_TAG, BET_MLP_TAG, DDPM_GPT_TAG, IBC_TAG, ACT_TAG, CVAE_TAG, DDPM_ACT_TAG, BESO_TAG, DDPM_MLP_TAG | layout bits: the policies).
+// fourth word keeps the streams apart (0: the random-policy harness; BET_TAG, BET_MLP_TAG, DDPM_GPT_TAG, IBC_TAG, ACT_TAG, CVAE_TAG, DDPM_ACT_TAG, BESO_TAG, DDPM_MLP_TAG, BC_GMM_TAG | layout bits: the policies).
 __device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out) {
   const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 #pragma unroll

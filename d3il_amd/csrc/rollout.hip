@@ -36,6 +36,7 @@ constexpr int WAVE = 64;
 #include "policy_cvae.h"
 #include "policy_ddpm_mlp.h"
 #include "policy_bet_mlp.h"
+#include "policy_bc_gmm.h"
 #include "policy_gpt_bc.h"
 
 namespace d3il {
@@ -1645,6 +1646,30 @@ int d3il_bet_mlp_f32(const float* state, const float* w_in, const float* b_in, c
   const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
   if (hidden == 128) hipLaunchKernelGGL(k_bet_mlp<128>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_bet_mlp<256>, grid, block, 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_bc_gmm(long n_env, const uint32_t* t_device, const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks, const float* w_feat,
+                const float* b_feat, const float* w_logit, const float* b_logit, const float* w_mean, const float* b_mean, const float* w_std, const float* b_std, const float* lo,
+                const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const float* u_in, const float* z_in, float* actions, int32_t* comps,
+                float* u_out, float* z_out, float* probs, int obs_dim, int G, int A, int hidden, int n_blocks, int std_mode, float min_std, void* stream) {
+  if ((hidden != 128 && hidden != 256) || obs_dim < 1 || obs_dim > BG_OBSMAX || G < 1 || G > BG_GMAX || A < 1 || A > BG_AMAX || n_blocks < 0 ||
+      (std_mode != BG_STD_LOW_NOISE && std_mode != BG_STD_EXP && std_mode != BG_STD_SOFTPLUS) || n_env > 0x7FFFFFFFL * 16)
+    return fail(D3IL_EUNSUPPORTED, "d3il_bc_gmm: built for hidden 128 / 256, obs_dim 1 .. 28, 1 .. 64 mixture components, 1 .. 8 action components, n_blocks >= 0 and std_mode 0 / 1 / 2");
+  if (!t_device || !state || !w_in || !b_in || !w_blocks || !b_blocks || !w_feat || !b_feat || !w_logit || !b_logit || !w_mean || !b_mean || !lo || !hi || !scale || !shift || !actions || !comps ||
+      (std_mode != BG_STD_LOW_NOISE && (!w_std || !b_std)))
+    return fail(D3IL_EINVAL, "d3il_bc_gmm: null argument");
+  if (n_env < 0) return fail(D3IL_EINVAL, "d3il_bc_gmm: negative environment count");
+  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_feat | (uintptr_t)b_feat | (uintptr_t)w_logit | (uintptr_t)b_logit | (uintptr_t)w_mean |
+       (uintptr_t)w_std) % 16 != 0)
+    return fail(D3IL_EINVAL, "d3il_bc_gmm: the packed weights, their biases and the head rows must be 16-byte aligned");
+  if (n_env == 0) return D3IL_OK;
+  BcGmmArgs a{t_device, state, w_in, b_in, w_blocks, b_blocks, w_feat, b_feat, w_logit, b_logit, w_mean, b_mean, w_std, b_std, lo, hi, scale, shift, u_in, z_in, actions, comps, u_out, z_out,
+              probs, (unsigned long long)seed, (unsigned long long)env_offset, n_env, min_std, obs_dim, G, A, n_blocks, std_mode};
+  // one workgroup of eight waves per 16 environments; the last one may be partly filled
+  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
+  if (hidden == 128) hipLaunchKernelGGL(k_bc_gmm<128>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_bc_gmm<256>, grid, block, 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -3394,6 +3394,266 @@ class BeTMLPPolicy(NativePolicy):
         return cls(net.to(device), torch.randn(64, action_dim, generator=g) * 0.9, sc, seed=policy_seed, uniform_fn=uniform_fn)
 
 
+# ------------------------------------------------------------------------------------------------ BC-GMM: a Gaussian mixture head on a residual MLP, sampled once per step
+BC_GMM_TAG = 0x474D0000       # fourth Philox counter word of the BC-GMM kernel, or-ed with q: 0 the uniform, 1 / 2 the normals (csrc/policy_bc_gmm.h; its upper half is no other tag's)
+BC_GMM_EDGE = 1e-4            # a draw this close to an edge of the normalised CDF is not decided between two arithmetics (tests, golden generator)
+BC_GMM_LOW_NOISE_STD = 1e-4   # robomimic's low_noise_eval, which bc_gmm.py:74-75 takes over
+BC_GMM_STD_MODES = {"low_noise": 0, "exp": 1, "softplus": 2}      # std_mode of d3il_bc_gmm
+
+
+def bc_gmm_words(seed: int, env_offset: int, n: int, t: int):
+    """The Philox words of the BC-GMM kernel: uint32 [n, 3 (q), 4] = Philox4x32-10(key = seed, counter = (lo32, hi32 of env_offset + row, t, BC_GMM_TAG | q))."""
+    return philox_words(seed, env_offset, n, t, np.uint64(BC_GMM_TAG) | _tag_axes(3)[0])
+
+
+def bc_gmm_uniforms(seed: int, env_offset: int, n: int, t: int):
+    """The kernel's uniforms of rows 0 .. n-1 at step word t, on the host: the upper 24 bits of word 0 of call q = 0, float32 in [0, 1 - 2^-24]."""
+    return uniform24(bc_gmm_words(seed, env_offset, n, t)[:, 0, 0])
+
+
+def bc_gmm_normals(seed: int, env_offset: int, n: int, t: int, A: int):
+    """The kernel's standard normals of rows 0 .. n-1 at step word t: float64 [n, A], component a = 4 (q - 1) + m from word m of call q = 1, 2.  Exact on the words
+    and f64 from there on (``box_muller_f64``: words 0, 1 -> components 0, 1; words 2, 3 -> components 2, 3), as ``cvae_latent_normals``."""
+    assert 1 <= A <= 8, "the counter layout holds two calls of four components"
+    return box_muller_f64(bc_gmm_words(seed, env_offset, n, t)[:, 1:3]).reshape(n, 8)[:, :A]
+
+
+class GMMNet(nn.Module):
+    """BC_GMM (agents/models/gmm/bc_gmm.py:13-90) without its distribution objects: ``mlp`` a Mish ResidualMLPNetwork whose output layer has ``hidden_dim`` rows
+    (mlp_output_dim = hidden_dim, as every shipped config sets it), and the three heads ``mean_mlp`` / ``std_mlp`` [G A rows, layout "(G A)"] and ``logits_mlp``
+    [G rows] under the reference's parameter names."""
+
+    def __init__(self, input_dim, hidden_dim, num_hidden_layers, output_dim, n_gaussians):
+        super().__init__()
+        self.mlp = ResidualMLP(input_dim, hidden_dim, num_hidden_layers, hidden_dim)
+        self.mean_mlp, self.std_mlp = nn.Linear(hidden_dim, output_dim * n_gaussians), nn.Linear(hidden_dim, output_dim * n_gaussians)
+        self.logits_mlp = nn.Linear(hidden_dim, n_gaussians)
+        self.n_gaussians, self.output_dim = int(n_gaussians), int(output_dim)
+
+    @classmethod
+    def from_reference_state(cls, sd, device=None):
+        """The network of a reference ``BC_GMM.state_dict()`` - widths, block count, G and A read from the shapes -, loaded, on ``device`` (default: where the state
+        dict lives), frozen."""
+        sd = {k: torch.as_tensor(v) for k, v in sd.items()}
+        hidden, in_dim = sd["mlp.layers.0.weight"].shape
+        G = sd["logits_mlp.weight"].shape[0]
+        rows = sd["mean_mlp.weight"].shape[0]
+        assert rows % G == 0 and sd["std_mlp.weight"].shape[0] == rows, "mean_mlp and std_mlp have n_gaussians * output_dim rows"
+        net = cls(in_dim, hidden, 2 * len({k.split(".")[2] for k in sd if ".l1." in k}), rows // G, G)
+        net.load_state_dict(sd)
+        return net.to(torch.device(device) if device is not None else sd["mlp.layers.0.weight"].device).requires_grad_(False).eval()
+
+
+def pack_bc_gmm_weights(net: GMMNet) -> dict:
+    """A GMMNet for k_bc_gmm: input layer and blocks as ``pack_resmlp_weights`` packs them (32 input columns); the trunk's output layer as one more square layer,
+    w_feat [T_out][t][lane (g, i)][r] = W_o[16 T_out + i][16 t + 4 g + r] with b_feat [H]; the G logit rows padded to 64 with zeros, as four output tiles in the same
+    operand order, w_logit [4][NT][64][4] with b_logit [64]; the mean and std rows (layout "(G A)") row-major as they are, w_mean / w_std [G A][H] with b_mean / b_std."""
+    from types import SimpleNamespace
+    lin_in, blocks, lin_out = net.mlp._parts()
+    dev, H, G = lin_in.weight.device, lin_in.out_features, net.n_gaussians
+    NT = H // 16
+    assert lin_out.out_features == H and lin_out.in_features == H and 1 <= G <= 64 and net.logits_mlp.out_features == G
+    none = SimpleNamespace(out_features=0, weight=torch.zeros(0, H, device=dev), bias=torch.zeros(0, device=dev))
+    pk = pack_resmlp_weights(lin_in, blocks, none)
+    del pk["w_out"], pk["b_out"]
+    ar = lambda k: torch.arange(k, device=dev)
+    t, g, i, r = ar(NT)[None, :, None, None, None], ar(4)[None, None, :, None, None], ar(16)[None, None, None, :, None], ar(4)[None, None, None, None, :]
+    tiles = lambda W, n: W[16 * ar(n)[:, None, None, None, None] + i, 16 * t + 4 * g + r].reshape(n, NT, 64, 4)
+    f = lambda x: x.detach().to(torch.float32).contiguous()
+    wl, bl = torch.zeros(64, H, device=dev), torch.zeros(64, device=dev)
+    wl[:G], bl[:G] = net.logits_mlp.weight, net.logits_mlp.bias
+    pk.update(w_feat=f(tiles(lin_out.weight, NT)), b_feat=f(lin_out.bias), w_logit=f(tiles(wl, 4)), b_logit=f(bl), w_mean=f(net.mean_mlp.weight), b_mean=f(net.mean_mlp.bias),
+              w_std=f(net.std_mlp.weight), b_std=f(net.std_mlp.bias))
+    return pk
+
+
+class BCGMMPolicy(NativePolicy):
+    """The BC-GMM agent on a batch.  The reference ships the model (agents/models/gmm/bc_gmm.py), its config (configs/agents/bc_gmm_agent.yaml) and its benchmark
+    scripts, but no agents/bc_gmm_agent.py; the yaml has BC_Agent's constructor keys, so the contract restated here is BC_Agent.predict (agents/bc_agent.py:240-271)
+    with ``model(state).sample()`` in place of ``model(state)``: window 1, no history, one sample per step as robomimic's GMMActorNetwork does.  Per environment:
+    scale the observation, h = input layer and blocks of the Mish ResidualMLPNetwork, f = Mish(output layer(h)) (no activation in front of that layer; it has
+    hidden_dim rows), logits = logits_mlp(f), ONE categorical draw k, mean = 0.01 tanh(mean_mlp(f))[k], std = 1e-4 with ``low_noise_eval`` (the shipped default;
+    std_mlp is not evaluated) or act(std_mlp(f))[k] + min_std with act = exp or torch's softplus, x = mean + std z, clamp to the data bounds IN SCALED SPACE,
+    inverse scaling as an f64 product and sum on the f32 scale and shift, rounded to f32 once - the dtypes CVAEPolicy and BeTMLPPolicy have.
+    ``use_tanh_wrapped_distribution`` is not restated: such a model stays on the row-by-row adapter.
+
+    MixtureSameFamily.sample draws a [1, 1, G, A] block of normals and keeps the drawn component's A values; this policy draws only the A normals it uses - the
+    same distribution with fewer draws.  The component is BeTMLPPolicy's inverse CDF: k = min(#{g : c_g <= u S}, G - 1) on the inclusive prefix sums of
+    exp(logit - max), on ONE uniform per lane and step; the normals are Box-Muller pairs.  Both come from Philox4x32-10 keyed by ``seed`` with counter (env_offset +
+    lane, step word, BC_GMM_TAG | q) - q = 0 the uniform, q = 1, 2 four normals each -, independent of batch order, sub-batches and ranks; ``u_in(n) -> [n]`` and
+    ``z_in(n) -> [n, A]`` replace them when given (golden replay, tests).  ``last_comps``, ``last_u``, ``last_z`` (and ``last_probs`` with ``record``) are what was used.
+
+    On a HIP device the whole call is ONE kernel (csrc/policy_bc_gmm.h through d3il_bc_gmm: hidden 128 / 256, obs <= 28, G <= 64, A <= 8, any number of blocks), then
+    a device-side add on the step word, so a captured graph draws fresh numbers at every replay.  On the CPU, for other shapes and with D3IL_POLICY_BC_GMM_FUSED=0 the
+    same arithmetic runs as torch ops (``_predict_torch``) with the numbers drawn on the host - that path cannot be captured.  An environment with a NaN / Inf in
+    its scaled state row, in f, in a logit, in its selected raw mean or std, in its std or in a normal it uses gets component -1 and NaN in every action component."""
+
+    def __init__(self, model: GMMNet, scaler: Scaler, min_std: float = 1e-4, std_activation: str = "exp", low_noise_eval: bool = True, seed: int = 0, u_in=None, z_in=None):
+        assert std_activation in ("exp", "softplus"), "std_activation is exp or softplus"
+        self.model, self.scaler = model.eval(), scaler
+        self.device = scaler.x_mean.device
+        lin_in, _, lin_out = model.mlp._parts()
+        self.G, self.A, self.obs_dim = int(model.n_gaussians), int(model.output_dim), int(lin_in.in_features)
+        assert lin_out.out_features == lin_in.out_features, "mlp_output_dim equals hidden_dim"
+        assert 1 <= self.G <= 64 and 1 <= self.A <= 8, "the Philox counter layout and the draw hold 64 mixture components of 8 action components"
+        self.min_std, self.std_activation, self.low_noise_eval = float(min_std), std_activation, bool(low_noise_eval)
+        self._init_output(scaler)
+        self._init_stream(seed)
+        self.u_in, self.z_in = u_in, z_in
+        self.record = False           # also keep the probabilities (last_probs)
+        self.last_comps = self.last_u = self.last_z = self.last_probs = None
+
+    @property
+    def std_mode(self) -> int:
+        return BC_GMM_STD_MODES["low_noise" if self.low_noise_eval else self.std_activation]
+
+    # ---- construction from the reference's objects
+    @classmethod
+    def from_model(cls, state_dict, scaler, min_std: float = 1e-4, std_activation: str = "exp", low_noise_eval: bool = True, seed: int = 0, device=None, u_in=None, z_in=None):
+        """From a reference ``BC_GMM.state_dict()`` (a checkpoint) and a scaler with the reference's attributes; the model's three settings as the config states them."""
+        net = GMMNet.from_reference_state(state_dict, device)
+        return cls(net, Scaler.from_reference(scaler, net.logits_mlp.weight.device), min_std, std_activation, low_noise_eval, seed=seed, u_in=u_in, z_in=z_in)
+
+    @classmethod
+    def from_reference(cls, agent, seed: int = 0, device=None, u_in=None, z_in=None):
+        """From a live ``BC_GMM_Agent`` (duck-typed, BC_Agent's attributes): ``agent.model`` (a BC_GMM: state dict, min_std, std_activation, low_noise_eval),
+        ``agent.scaler`` (its ``y_bounds`` are the clamp)."""
+        m = agent.model
+        return cls.from_model(m.state_dict(), agent.scaler, float(m.min_std), str(m.std_activation), bool(m.low_noise_eval), seed=seed, device=device, u_in=u_in, z_in=z_in)
+
+    @staticmethod
+    def matches(agent) -> bool:
+        """Is ``agent`` exactly what this policy restates: a BC_GMM_Agent whose model is a BC_GMM in eval mode (in train mode low_noise_eval is ignored) with a
+        ResidualMLPNetwork of plain ``nn.Linear`` layers and Mish blocks without norm and without spectral norm, mlp_output_dim = hidden_dim, Mish behind it, three
+        plain ``nn.Linear`` heads of G A, G A and G rows, no tanh-wrapped distribution, std_activation exp or softplus, 1 <= G <= 64, 1 <= A <= 8 and a scaler with
+        bounds?  Everything else stays on the row-by-row adapter, which runs the reference's own code."""
+        try:
+            m = agent.model
+            if type(agent).__name__ != "BC_GMM_Agent" or type(m).__name__ != "BC_GMM" or not hasattr(agent, "scaler") or agent.scaler.y_bounds is None:
+                return False
+            if m.training or m.use_tanh_wrapped_distribution or m.std_activation not in ("exp", "softplus") or not isinstance(m.mlp_output_act, nn.Mish):
+                return False
+            layers = list(m.mlp.layers)
+            if not ResidualMLP.is_plain(layers, strict=True) or layers[-1].out_features != layers[0].out_features:
+                return False
+            G, A, H = int(m.n_gaussians), int(m.output_dim), layers[0].out_features
+            heads = ((m.mean_mlp, G * A), (m.std_mlp, G * A), (m.logits_mlp, G))
+            if not all(type(l) is nn.Linear and not hasattr(l, "weight_orig") and l.bias is not None and l.in_features == H and l.out_features == rows for l, rows in heads):
+                return False
+            return 1 <= G <= 64 and 1 <= A <= 8
+        except (AttributeError, TypeError, ValueError, IndexError):
+            return False
+
+    # ---- the policy protocol of the Sims and SubBatchSet (NativePolicy; no per-lane state: the step word is all a capture puts back)
+    SWITCH, LAST = "D3IL_POLICY_BC_GMM_FUSED", ("last_comps", "last_u", "last_z", "last_probs")
+
+    def load_reference_state_dict(self, sd):
+        """``BC_GMM.state_dict()`` of the reference."""
+        self.model.load_state_dict(sd)
+
+    def _pack(self):
+        return pack_bc_gmm_weights(self.model)
+
+    def _kernel_shape(self) -> bool:
+        lin_in = self.model.mlp._parts()[0]
+        return lin_in.out_features in (128, 256) and 1 <= lin_in.in_features <= 28 and 1 <= self.G <= 64 and 1 <= self.A <= 8
+
+    # ---- the call
+    def _uniforms(self, n, dev, need_host: bool):
+        return self._draw(self.u_in, n, (n,), lambda t: bc_gmm_uniforms(self.seed, self.env_offset, n, t), need_host, dev)
+
+    def _normals(self, n, dev, need_host: bool):
+        return self._draw(self.z_in, n, (n, self.A), lambda t: bc_gmm_normals(self.seed, self.env_offset, n, t, self.A), need_host, dev)
+
+    def _predict_torch(self, s, u, z):
+        """Steps 1 - 8 of csrc/policy_bc_gmm.h as torch ops in the dtype of ``s`` and the parameters (f32 in the policy; the tests run it in f64 too), in the
+        kernel's order of operations where the order is defined (S is the last prefix sum; the product std z is rounded before the sum): returns (actions,
+        components i32, probabilities)."""
+        m, G, A, dt, dev = self.model, self.G, self.A, s.dtype, s.device
+        h = s
+        for layer in m.mlp.layers[:-1]:
+            h = layer(h)
+        f = F.mish(m.mlp.layers[-1](h))
+        logits = m.logits_mlp(f)
+        p = torch.exp(logits - logits.max(dim=1, keepdim=True).values)
+        c = torch.cumsum(p, dim=1)
+        S = c[:, -1:]
+        k = (c <= u.to(dev, dt).unsqueeze(1) * S).sum(dim=1).clamp_max(G - 1)
+        ar = torch.arange(s.shape[0], device=dev)
+        mraw = m.mean_mlp(f).reshape(-1, G, A)[ar, k]
+        mean = 0.01 * torch.tanh(mraw)
+        if self.low_noise_eval:
+            sraw, sd = torch.zeros_like(mraw), torch.full_like(mraw, BC_GMM_LOW_NOISE_STD)
+        else:
+            sraw = m.std_mlp(f).reshape(-1, G, A)[ar, k]
+            sd = (torch.exp(sraw) if self.std_activation == "exp" else F.softplus(sraw)) + self.min_std
+        z = z.to(dev, dt)
+        x = mean + sd * z
+        fin = lambda v: torch.isfinite(v).all(dim=1)
+        bad = ~(fin(s) & fin(f) & fin(logits) & fin(mraw) & fin(sraw) & fin(sd) & fin(z))
+        y = self._action_tail(x, bad, True, self.lo, self.hi)
+        return y, torch.where(bad, torch.full_like(k, -1), k).to(torch.int32), p / S
+
+    def _step_torch(self, s):
+        n = s.shape[0]
+        if self.u_in is None or self.z_in is None:
+            self._host_step_word()      # (raises under a capture before anything is drawn)
+        u, z = self._uniforms(n, s.device, True), self._normals(n, s.device, True)
+        y, self.last_comps, probs = self._predict_torch(s, u, z)
+        self.last_u, self.last_z, self.last_probs = u, z, probs if self.record else None
+        return y
+
+    def _step_kernel(self, s):
+        from . import capi
+        n, dev = s.shape[0], s.device
+        w = self._packed.current(self._pack_params(), self._pack)
+        y = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        comps = torch.empty(n, dtype=torch.int32, device=dev)
+        u_out = torch.empty(n, dtype=torch.float32, device=dev)
+        z_out = torch.empty(n, self.A, dtype=torch.float32, device=dev)
+        probs = torch.empty(n, self.G, dtype=torch.float32, device=dev) if self.record else None
+        lin_in, blocks, _ = self.model.mlp._parts()
+        low = self.low_noise_eval
+        d = self._draw_args()
+        capi.launch("d3il_bc_gmm", dev, n_env=n, t_device=d["t_device"], state=s, **resmlp_args(w), w_feat=w["w_feat"], b_feat=w["b_feat"], w_logit=w["w_logit"], b_logit=w["b_logit"],
+                    w_mean=w["w_mean"], b_mean=w["b_mean"], w_std=None if low else w["w_std"], b_std=None if low else w["b_std"], lo=d["lo"], hi=d["hi"], scale=d["scale"],
+                    shift=d["shift"], seed=self.seed, env_offset=self.env_offset, u_in=self._uniforms(n, dev, False), z_in=self._normals(n, dev, False), actions=y, comps=comps,
+                    u_out=u_out, z_out=z_out, probs=probs, obs_dim=self.obs_dim, G=self.G, A=self.A, hidden=lin_in.out_features, n_blocks=len(blocks), std_mode=self.std_mode,
+                    min_std=self.min_std)
+        self.last_comps, self.last_u, self.last_z, self.last_probs = comps, u_out, z_out, probs
+        return y
+
+    def _fallback_text(self):
+        return ("this network (hidden %d, %d inputs, %d mixture components, %d action components) is not one the kernel is built for; every call runs "
+                "torch's layers with the Philox numbers drawn on the host (a device synchronisation per call, no graph capture)"
+                % (self.model.mlp._parts()[0].out_features, self.obs_dim, self.G, self.A))
+
+    @classmethod
+    def random(cls, obs_dim: int, action_dim: int, device="cuda", seed: int = 0, hidden_dim: int = 128, n_blocks: int = 3, n_gaussians: int = 8, action_scale: float = 0.5,
+               policy_seed: int = 0, logit_std: float = 2.0, bound: float = 1.5, min_std: float = 1e-4, std_activation: str = "exp", low_noise_eval: bool = True, u_in=None,
+               z_in=None):
+        """A policy of the reference's shape with fixed random weights (there are no checkpoints offline): the shipped scripts use hidden 128 / 256 with 6 / 8 hidden
+        layers (3 / 4 blocks) and 8 .. 64 components; torch's default layer initialisation, the logit rows scaled so that the logits of standard-normal inputs have a
+        standard deviation of about ``logit_std`` (neither uniform nor one-hot), mean rows that use the range of the tanh, std rows around exp(-1), unit observation
+        scaling, actions of ``action_scale`` per unit of the scaled space (the means are at most 0.01 there), bounds +-``bound``."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            net = GMMNet(obs_dim, hidden_dim, 2 * n_blocks, action_dim, n_gaussians)
+        net.requires_grad_(False).eval()
+        with torch.no_grad():
+            x = torch.randn(256, obs_dim, generator=g)
+            for layer in net.mlp.layers:
+                x = layer(x)
+            rms = float(F.mish(x).pow(2).mean().sqrt())
+            net.logits_mlp.weight.copy_(torch.randn(n_gaussians, hidden_dim, generator=g) * (logit_std / (rms * hidden_dim ** 0.5)))
+            net.mean_mlp.weight.copy_(torch.randn(n_gaussians * action_dim, hidden_dim, generator=g) * (1.0 / (rms * hidden_dim ** 0.5)))
+            net.std_mlp.weight.copy_(torch.randn(n_gaussians * action_dim, hidden_dim, generator=g) * (0.5 / (rms * hidden_dim ** 0.5)))
+            net.std_mlp.bias.copy_(torch.randn(n_gaussians * action_dim, generator=g) * 0.1 - 1.0)
+        sc = Scaler.unit(obs_dim, action_dim, action_scale, bound, device)
+        return cls(net.to(device), sc, min_std, std_activation, low_noise_eval, seed=policy_seed, u_in=u_in, z_in=z_in)
+
+
 # ------------------------------------------------------------------------------------------------ BC-GPT: the minGPT trunk with a regression head
 class GPTBCPolicy(BeTPolicy):
     """Gpt_Agent.predict (agents/gpt_bc_agent.py:221-247) on a batch: scaled observation window (deque maxlen W; the window GROWS at episode start), the minGPT

@@ -372,6 +372,27 @@ int d3il_bet_mlp_f32(const float* state, const float* w_in, const float* b_in, c
                      const float* w_off, const float* b_off, const float* centers, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed,
                      uint64_t env_offset, const uint32_t* t_device, const float* u_in, float* actions, int32_t* bins, float* u_out, float* probs, long n_env, int obs_dim,
                      int V, int A, int hidden, int n_blocks, void* stream);
+/* The whole inference of the batched BC-GMM policy (policies.BCGMMPolicy; agents/models/gmm/bc_gmm.py:13-90 sampled once per step) in one launch, f32, on the Philox
+ * stream: per environment h = the input layer and the residual blocks of the ResidualMLPNetwork (Mish) on the scaled state row, f = Mish(w_feat h + b_feat) (the
+ * network's own output layer, hidden rows), logit_g = w_logit[g] . f + b_logit[g] for g < G, p = exp(logit - max) with inclusive prefix sums c and S = c_{G-1},
+ * u = u_in[n] or 24 bits of word 0 of Philox4x32-10 (key = seed, counter = (env_offset + n, *t_device, 0x474D0000)), comps[n] = k = min(#{g < G : c_g <= u S}, G - 1),
+ * mean_a = 0.01 tanh(w_mean[k A + a] . f + b_mean[k A + a]) (layout "(G A)"), std_a = 1e-4 (std_mode 0: w_std / b_std are never read and may be NULL) or
+ * act(w_std[k A + a] . f + b_std[k A + a]) + min_std with act = exp (std_mode 1) or softplus with the switch to the identity above 20 (std_mode 2), z_a =
+ * z_in[n][a] or Box-Muller normals as d3il_cvae_decode_f32 on the counter word 0x474D0000 | q, q = 1 + a / 4, component a = 4 (q - 1) + m from word m,
+ * actions[n][a] = clamp(mean_a + std_a z_a, lo_a, hi_a) scale_a + shift_a (f32 up to the clamp; product and sum in f64, rounded once).  t_device: DEVICE u32, read
+ * only.  state [n_env][obs_dim] (scaled); w_in, b_in, w_blocks, b_blocks as d3il_resmlp_f32 (input layer packed to 32 columns); w_feat [NT][NT][64][4] packed like a
+ * block layer (NT = hidden / 16), b_feat [hidden]; w_logit: the G logit rows padded to 64 with zeros and packed like d3il_bet_mlp_f32's, [4][NT][64][4], b_logit [64]
+ * (policies.pack_bc_gmm_weights); w_mean / w_std row-major [G A][hidden], b_mean / b_std [G A]; lo / hi (scaled space) / scale / shift [A].  u_in [n_env], z_in
+ * [n_env][A], u_out [n_env], z_out [n_env][A] (what was used) and probs [n_env][G] (p / S) may be NULL.  An environment with a NaN / Inf in its state row, in f, in a
+ * logit g < G, in a selected raw mean or std, in its std (an overflowing exp) or in a normal it uses gets comps = -1 and NaN in every action component; no other
+ * environment changes.  Built for hidden 128 / 256, 1 <= obs_dim <= 28, 1 <= G <= 64, 1 <= A <= 8, n_blocks >= 0, std_mode 0 / 1 / 2: D3IL_EUNSUPPORTED otherwise,
+ * answered before any launch.  Packed arrays, b_in .. b_logit, w_mean and w_std 16-byte aligned.  (No _f32 suffix and the row count first: capi.SIGNATURES4 holds this
+ * entry.) */
+int d3il_bc_gmm(long n_env, const uint32_t* t_device, const float* state, const float* w_in, const float* b_in, const float* w_blocks, const float* b_blocks,
+                const float* w_feat, const float* b_feat, const float* w_logit, const float* b_logit, const float* w_mean, const float* b_mean, const float* w_std,
+                const float* b_std, const float* lo, const float* hi, const float* scale, const float* shift, uint64_t seed, uint64_t env_offset, const float* u_in,
+                const float* z_in, float* actions, int32_t* comps, float* u_out, float* z_out, float* probs, int obs_dim, int G, int A, int hidden, int n_blocks,
+                int std_mode, float min_std, void* stream);
 /* The tail of the batched BC-GPT policy (policies.GPTBCPolicy; gpt_bc_agent.py:221-247 around gpt_policy.py MinGPT) in one launch: per row x = LayerNorm(h)
  * (biased variance), o_a = w_head[a] . x (no bias), actions[row][a] = clamp(o_a, lo_a, hi_a) scale_a + shift_a (clamp in f32; product and sum in f64, rounded once).
  * h [rows][C] (the last block's output at every environment's last token, before ln_f); ln_weight / ln_bias [C]; w_head [A][C] row-major; lo / hi (scaled space) /
