@@ -154,11 +154,15 @@ D3IL_HD double rcpd(double x) {
   return 1.0 / x;
 #endif
 }
-D3IL_HD double rsqrtd(double x) {   // 1 / sqrt(x), x > 0: v_rsq_f64 + two Newton steps on the device
+// 1 / sqrt(x), x > 0.  Device: v_rsq_f64 + two Newton steps in RESIDUAL form, y += y r with r = 1/2 - (x y) (y / 2) from one fma.  The last step rounds
+// three times (x y: 2^-53 of a value near 1, halved in r; r's own rounding is of a value ~1e-16; the closing fma: 2^-53), so the relative error is bounded
+// by 0.75 x 2^-52.  The earlier form y (1.5 - 0.5 x y y) rounded four times at full size and reached 1.02 x 2^-52 on MI355X (tests/test_gpu_ik_solve6.py).
+// Same four operations a step; the fused operations are explicit, so the bits do not depend on the contraction mode of the including file.
+D3IL_HD double rsqrtd(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double y = __builtin_amdgcn_rsq(x);
-  y = y * (1.5 - 0.5 * x * y * y);
-  y = y * (1.5 - 0.5 * x * y * y);
+  y = fma(y, fma(-(x * y), 0.5 * y, 0.5), y);
+  y = fma(y, fma(-(x * y), 0.5 * y, 0.5), y);
   return y;
 #else
   return 1.0 / sqrt(x);

@@ -77,6 +77,46 @@ void hc_ik_control(const void* c, const double* setpoint, const double* cur_q, c
   *flags = (int)f;
 }
 void hc_solve6(const double* A21, const double* b, double lo, double hi, double* x, int fast) { if (fast) ik_solve6<true>(A21, b, lo, hi, x); else ik_solve6<false>(A21, b, lo, hi, x); }
+// the solve as the kernels call it: vwarm (7 doubles, in/out, may be NULL) = the eigenvector accepted by the previous solve, [6] != 0 when valid
+void hc_solve6_warm(const double* A21, const double* b, double lo, double hi, double* x, int fast, double* vwarm) {
+  if (fast) ik_solve6<true>(A21, b, lo, hi, x, vwarm); else ik_solve6<false>(A21, b, lo, hi, x, vwarm);
+}
+// hc_ik_control in the kernels' calling form: vwarm (7 doubles) and trig (15 doubles: sin[7] cos[7] of ikq, [14] != 0 when valid), each in/out, each may be NULL
+void hc_ik_control_form(const void* c, const double* setpoint, const double* cur_q, const double* cur_v, double* ikq, double* ikqd, int* flags, int fast, double* tau,
+                        double* vwarm, double* trig) {
+  const PandaConsts& p = *(const PandaConsts*)c;
+  unsigned f = (unsigned)*flags;
+  double n = std::sqrt(setpoint[3] * setpoint[3] + setpoint[4] * setpoint[4] + setpoint[5] * setpoint[5] + setpoint[6] * setpoint[6]);
+  double dq[4] = {setpoint[3] / n, setpoint[4] / n, setpoint[5] / n, setpoint[6] / n};
+  if (fast) ik_update<true>(p, setpoint, dq, cur_q, f, ikq, ikqd, vwarm, trig); else ik_update<false>(p, setpoint, dq, cur_q, f, ikq, ikqd, vwarm, trig);
+  for (int k = 0; k < NARM; k++) tau[k] = p.pd_p[k] * (ikq[k] - cur_q[k]) + p.pd_d[k] * (ikqd[k] - cur_v[k]);
+  *flags = (int)f;
+}
+// the controller's linear system at the virtual joint target q (one iteration of ik_update, before the solve): A (packed lower triangle, 21) and its right-hand side
+void hc_ik_system(const void* c, const double* setpoint, const double* q, double* A21, double* rhs) {
+  const PandaConsts& p = *(const PandaConsts*)c;
+  double n = std::sqrt(setpoint[3] * setpoint[3] + setpoint[4] * setpoint[4] + setpoint[5] * setpoint[5] + setpoint[6] * setpoint[6]);
+  double dq[4] = {setpoint[3] / n, setpoint[4] / n, setpoint[5] / n, setpoint[6] / n};
+  double pos[3], R[9], ax[NARM][3], og[NARM][3], sq[NARM], cq[NARM], cq4[4], qe[3], target[6], J[6][NARM], qn[NARM];
+  for (int k = 0; k < NARM; k++) { sq[k] = std::sin(q[k]); cq[k] = std::cos(q[k]); }
+  ik_chain(p, sq, cq, pos, R, ax, og); mat2quat(R, cq4);
+  double dm = 0, dp = 0;
+  for (int k = 0; k < 4; k++) { dm += (cq4[k] - dq[k]) * (cq4[k] - dq[k]); dp += (cq4[k] + dq[k]) * (cq4[k] + dq[k]); }
+  if (dm > dp) for (int k = 0; k < 4; k++) dq[k] = -dq[k];
+  quat_error(cq4, dq, qe);
+  for (int k = 0; k < 3; k++) { target[k] = p.ik_ppos[k] * clampd(setpoint[k] - pos[k], -0.01, 0.01); target[3 + k] = p.ik_pquat[k] * clampd(qe[k], -0.1, 0.1); }
+  for (int k = 0; k < NARM; k++) { double d[3] = {pos[0] - og[k][0], pos[1] - og[k][1], pos[2] - og[k][2]}, cr[3]; cross3(ax[k], d, cr);
+    for (int r = 0; r < 3; r++) { J[r][k] = cr[r]; J[3 + r][k] = ax[k][r]; } }
+  for (int a = 0; a < 6; a++) for (int b = 0; b <= a; b++) { double s = a == b ? p.ik_Jreg : 0.0; for (int k = 0; k < NARM; k++) s += J[a][k] * J[b][k]; A21[tri(a, b)] = s; }
+  for (int k = 0; k < NARM; k++) qn[k] = p.ik_pnull[k] * clampd(p.ik_rest[k] - q[k], -0.2, 0.2);
+  for (int a = 0; a < 6; a++) { double s = target[a]; for (int k = 0; k < NARM; k++) s -= J[a][k] * qn[k]; rhs[a] = s; }
+}
+void hc_ik_params(const void* c, double* out /* ik_minsv, ik_maxsv, ik_Jreg, ik_lr, ik_iters, n_substeps, q_min[7], q_max[7], pd_p[7], pd_d[7], timestep */) {
+  const PandaConsts& p = *(const PandaConsts*)c;
+  out[0] = p.ik_minsv; out[1] = p.ik_maxsv; out[2] = p.ik_Jreg; out[3] = p.ik_lr; out[4] = p.ik_iters; out[5] = p.n_substeps;
+  for (int k = 0; k < NARM; k++) { out[6 + k] = p.q_min[k]; out[6 + NARM + k] = p.q_max[k]; out[6 + 2 * NARM + k] = p.pd_p[k]; out[6 + 3 * NARM + k] = p.pd_d[k]; }
+  out[6 + 4 * NARM] = p.timestep;
+}
 void hc_physics_substep(const void* c, double* s, int* f, const double* tau, const double* ffing) {
   EnvState st; unpack(s, f, st); double warm[6]; warm[5] = 0; physics_substep(*(const PandaConsts*)c, st, tau, ffing, warm); pack(st, s, f);
 }

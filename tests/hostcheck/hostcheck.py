@@ -31,6 +31,33 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def pack_sym6(A):
+    """The packed lower triangle (21, row by row) of a symmetric 6x6 - ik_solve6's matrix argument."""
+    A = np.asarray(A, float)
+    return np.ascontiguousarray(A[np.tril_indices(6)])
+
+
+def solve6(A21, b, lo, hi, fast):
+    """ik_solve6<fast> without a warm vector (hc_solve6)."""
+    A21, b, x = np.ascontiguousarray(A21, float), np.ascontiguousarray(b, float), np.zeros(6)
+    lib().hc_solve6(_p(A21), _p(b), C.c_double(lo), C.c_double(hi), _p(x), int(fast))
+    return x
+
+
+def solve6_warm(A21, b, lo, hi, fast, vwarm=None):
+    """ik_solve6<fast> as the kernels call it: vwarm (7 doubles, in/out) or None."""
+    A21, b, x = np.ascontiguousarray(A21, float), np.ascontiguousarray(b, float), np.zeros(6)
+    lib().hc_solve6_warm(_p(A21), _p(b), C.c_double(lo), C.c_double(hi), _p(x), int(fast), None if vwarm is None else _p(vwarm))
+    return x
+
+
+def stats(reset=False):
+    """Host counters: newton_calls, newton_iters, ls_iters, eig_calls, ik_calls, contact_calls."""
+    o = (C.c_long * 6)()
+    lib().hc_stats(o, int(reset))
+    return dict(zip(("newton_calls", "newton_iters", "ls_iters", "eig_calls", "ik_calls", "contact_calls"), o))
+
+
 class HostCheck:
     def __init__(self, blob):
         self.L = lib()
@@ -62,6 +89,28 @@ class HostCheck:
         tau = np.zeros(7)
         self.L.hc_ik_control(self.h, _p(sp), _p(cq), _p(cv), _p(ikq), _p(ikqd), C.byref(f), int(fast), _p(tau))
         return tau, f.value
+
+    def ik_control_form(self, setpoint, cur_q, cur_v, ikq, ikqd, flags, fast, vwarm=None, trig=None):
+        """ik_control in the kernels' calling form: vwarm (7 doubles) / trig (15 doubles) are carried in place, None = not passed."""
+        sp, cq, cv = (np.ascontiguousarray(x, float) for x in (setpoint, cur_q, cur_v))
+        f = C.c_int(flags)
+        tau = np.zeros(7)
+        self.L.hc_ik_control_form(self.h, _p(sp), _p(cq), _p(cv), _p(ikq), _p(ikqd), C.byref(f), int(fast), _p(tau),
+                                  None if vwarm is None else _p(vwarm), None if trig is None else _p(trig))
+        return tau, f.value
+
+    def ik_system(self, setpoint, q):
+        """A (packed lower triangle, 21) and right-hand side of the controller's solve at the virtual joint target q."""
+        sp, q = np.ascontiguousarray(setpoint, float), np.ascontiguousarray(q, float)
+        A, rhs = np.zeros(21), np.zeros(6)
+        self.L.hc_ik_system(self.h, _p(sp), _p(q), _p(A), _p(rhs))
+        return A, rhs
+
+    def ik_params(self):
+        o = np.zeros(35)
+        self.L.hc_ik_params(self.h, _p(o))
+        return dict(lo=o[0], hi=o[1], J_reg=o[2], lr=o[3], iters=int(o[4]), n_substeps=int(o[5]), q_min=o[6:13].copy(), q_max=o[13:20].copy(),
+                    pd_p=o[20:27].copy(), pd_d=o[27:34].copy(), timestep=o[34])
 
     def physics_substep(self, s, f, tau, ff):
         tau, ff = np.ascontiguousarray(tau, float), np.ascontiguousarray(ff, float)
