@@ -512,18 +512,28 @@ D3IL_HD void cube_integrate(BoxState& bx, const double* acc, double h) {
   }
 }
 
-D3IL_HD double push_tan_yaw(const double* q) {   // np.tan(quat2euler(q)[-1]); geometric_transformation.py:92-111,165-188
+// a b - c d with one rounding's worth of error (Kahan's difference of products: the rounding error of c d is recovered with an fma)
+D3IL_HD double push_dop(double a, double b, double c, double d) {
+  double cd = c * d, err = fma(-c, d, cd);
+  return fma(a, b, -cd) + err;
+}
+// np.tan(quat2euler(q)[-1]); geometric_transformation.py:92-111,165-188.  Same branches as that code (Nq <= FEPS: identity; cy <= 4 FEPS: the gimbal formula), but
+// tan(-atan2(n, d)) is formed as -n / d from n and d in factored form, 2 (xy - wz) and (w - z)(w + z) + (x - y)(x + y) (both times 1 / Nq, which cancels):
+// written as 1 - (yY + zZ), d cancels to |cos yaw| with an absolute error of 1e-16 and the f32 observation is several ulps off within 1e-9 of yaw = +-pi/2; and
+// tan(atan2(0, -1)) is -1.2e-16, not 0, at yaw = +-pi (tests/contact_leaf_cases.py).
+D3IL_HD double push_tan_yaw(const double* q) {
   const double FEPS = 2.220446049250313e-16;
   double w = q[0], x = q[1], y = q[2], z = q[3], Nq = w * w + x * x + y * y + z * z;
-  double m00 = 1, m01 = 0, m10 = 0, m11 = 1, m12 = 0, m22 = 1;
-  if (Nq > FEPS) {
-    double s = 2.0 / Nq, X = x * s, Y = y * s, Z = z * s;
-    double wX = w * X, wZ = w * Z, xX = x * X, xY = x * Y, yY = y * Y, yZ = y * Z, zZ = z * Z;
-    m00 = 1.0 - (yY + zZ); m01 = xY - wZ; m10 = xY + wZ; m11 = 1.0 - (xX + zZ); m12 = yZ - wX; m22 = 1.0 - (xX + yY);
-  }
+  if (!(Nq > FEPS)) return -0.0;      // identity matrix: tan(-atan2(0, 1))
+  double s = 2.0 / Nq, X = x * s, Y = y * s;
+  double wX = w * X, xX = x * X, yY = y * Y, yZ = y * (z * s);
+  double m12 = yZ - wX, m22 = 1.0 - (xX + yY);
   double cy = sqrt(m22 * m22 + m12 * m12);
-  double yaw = cy > 4 * FEPS ? -atan2(m01, m00) : -atan2(-m10, m11);
-  return tan(yaw);
+  double n, d;
+  if (cy > 4 * FEPS) { n = 2.0 * push_dop(x, y, w, z); d = fma(w - z, w + z, (x - y) * (x + y)); }      // m01 Nq, m00 Nq
+  else { n = -2.0 * push_dop(x, y, -w, z); d = fma(w - x, w + x, (y - z) * (y + z)); }                    // -m10 Nq, m11 Nq
+  if (d == 0) return tan(n > 0 ? -1.5707963267948966 : (n < 0 ? 1.5707963267948966 : -0.0));             // yaw = -+pi/2 exactly: what tan makes of the f64 pi/2, finite
+  return -n / d;
 }
 
 // joint PD on the set-point + finger PD (Scene.next_step after the IK update): arm torque without gravity compensation, raw finger force

@@ -34,6 +34,13 @@ def lib():
         _LIB.dc_scalar.argtypes = [V, V, V, I, V]
         _LIB.dc_trig_chain.argtypes = [V, V, V, I, I, V]
         _LIB.dc_ik_update.argtypes = [V, V, V, V, V, V, I, I, I, I, I, V]
+        _LIB.dc_box_box.argtypes = [V, V, V, V, V, V, V, I, V, V, I, V]
+        _LIB.dc_cyl_box.argtypes = [V, V, V, V, V, V, V, V, I, V]
+        _LIB.dc_cone_eval.argtypes = [V, V, V, I, V]
+        _LIB.dc_ldl.argtypes = [I, I, V, V, V, V, V, V, I, V]
+        _LIB.dc_cube_chain.argtypes = [V, V, V, I, V, I, V]
+        _LIB.dc_tan_yaw.argtypes = [V, V, I, V]
+        _LIB.dc_quat2mat.argtypes = [V, V, I, V]
     return _LIB
 
 
@@ -71,3 +78,37 @@ def trig_chain(dl, sn, cs, K, n):
 def ik_update(des, jpos, jvel, length, ikq_out, tau_out, use_vwarm, use_trig, period, fast, n):
     """des (position + unit quaternion), jpos, jvel [K, n, 7], length [n] int32 -> ikq_out, tau_out [K, n, 7] (rows k < length[e] of lane e are written)."""
     return lib().dc_ik_update(_p(des), _p(jpos), _p(jvel), _p(length), _p(ikq_out), _p(tau_out), int(use_vwarm), int(use_trig), int(period), int(fast), int(n), _stream())
+
+
+# ---------------------------------------------------------------- leaf routines of the contact engines (f64 tensors; count / hit / ok int32)
+def box_box(p1, R1, s1, p2, R2, s2, margin, cap, count, rec, n):
+    """p, s [n, 3], R [n, 9] row-major, margin [n] -> count [n] int32, rec [n, 8, 7] (pre-filled by the caller; rows >= count stay)."""
+    return lib().dc_box_box(_p(p1), _p(R1), _p(s1), _p(p2), _p(R2), _p(s2), _p(margin), int(cap), _p(count), _p(rec), int(n), _stream())
+
+
+def cyl_box(pc, axis, par, pb, Rb, sb, hit, out, n):
+    """pc, axis, pb, sb [n, 3], par [n, 3] = rad, half, margin, Rb [n, 9] -> hit [n] int32, out [n, 7] (written on a hit only)."""
+    return lib().dc_cyl_box(_p(pc), _p(axis), _p(par), _p(pb), _p(Rb), _p(sb), _p(hit), _p(out), int(n), _stream())
+
+
+def cone_eval(jar, par, out, n):
+    """jar [n, 3], par [n, 4] = Dn, Dt, mu, fric -> out [n, 2, 13] = cost, force3, Hc9 of cone_eval and of gt_cone_eval."""
+    return lib().dc_cone_eval(_p(jar), _p(par), _p(out), int(n), _stream())
+
+
+def ldl(order, twin, A, b, L, d, x, ok, n):
+    """A, L [n, order (order + 1) / 2], b, d, x [n, order], ok [n] int32."""
+    return lib().dc_ldl(int(order), int(twin), _p(A), _p(b), _p(L), _p(d), _p(x), _p(ok), int(n), _stream())
+
+
+def cube_chain(state, acc, h, K, qhist, n):
+    """state [n, 13] in/out, acc [n, 6], h [n]; qhist [K, n, 4] or None."""
+    return lib().dc_cube_chain(_p(state), _p(acc), _p(h), int(K), _p(qhist), int(n), _stream())
+
+
+def tan_yaw(q, out, n):
+    return lib().dc_tan_yaw(_p(q), _p(out), int(n), _stream())
+
+
+def quat2mat(q, R, n):
+    return lib().dc_quat2mat(_p(q), _p(R), int(n), _stream())

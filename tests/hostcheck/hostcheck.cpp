@@ -267,4 +267,38 @@ int hc_box_box(const double* p1, const double* q1, const double* s1, const doubl
   std::memcpy(out, rec, n * 7 * sizeof(double));
   return n;
 }
+// ---------------------------------------------------------------- leaf routines of the contact engines by themselves (tests/contact_leaf_cases.py)
+// box_box as the device check calls it: row-major R, the caller's cap, out [8][7] (rows >= the count are left as they were)
+int hc_box_box_R(const double* p1, const double* R1, const double* s1, const double* p2, const double* R2, const double* s2, double margin, int cap, double* out) {
+  return box_box(p1, R1, s1, p2, R2, s2, margin, (double (*)[7])out, cap);
+}
+int hc_cyl_box_axis(const double* pc, const double* axis, double rad, double half, const double* pb, const double* Rb, const double* sb, double margin, double* out) {
+  return cyl_box(pc, axis, rad, half, pb, Rb, sb, margin, out) ? 1 : 0;
+}
+// twin: gt_cone_eval (gen_tree.h)
+double hc_cone_eval(const double* jar, double Dn, double Dt, double mu, double fric, double* force, double* Hc, int twin) {
+  return twin ? gt_cone_eval(jar, Dn, Dt, mu, fric, force, Hc) : cone_eval(jar, Dn, Dt, mu, fric, force, Hc);
+}
+// A: packed lower triangle (n (n + 1) / 2), IN PLACE - its strict lower part becomes L; b -> x; d: the pivots.  Returns ok (1 / 0), -1 for another order.
+int hc_ldl(int n, double* A, const double* b, double* x, double* d, int twin) {
+  double id[6]; bool ok;
+  if (n != 5 && n != 6) return -1;
+  for (int i = 0; i < n; i++) x[i] = b[i];
+  if (n == 5) { if (twin) { ok = gt_ldl_n<5>(A, d, id); gt_ldl_solve_n<5>(A, id, x); } else { ok = ldl_n<5>(A, d, id); ldl_solve_n<5>(A, id, x); } }
+  else { if (twin) { ok = gt_ldl_n<6>(A, d, id); gt_ldl_solve_n<6>(A, id, x); } else { ok = ldl_n<6>(A, d, id); ldl_solve_n<6>(A, id, x); } }
+  return ok ? 1 : 0;
+}
+// state13 = pos3 quat4 vel6, in place; K calls
+void hc_cube_integrate(double* s, const double* acc, double h, int K) {
+  BoxState bx;
+  for (int k = 0; k < 3; k++) bx.pos[k] = s[k];
+  for (int k = 0; k < 4; k++) bx.quat[k] = s[3 + k];
+  for (int k = 0; k < 6; k++) bx.vel[k] = s[7 + k];
+  for (int c = 0; c < K; c++) cube_integrate(bx, acc, h);
+  for (int k = 0; k < 3; k++) s[k] = bx.pos[k];
+  for (int k = 0; k < 4; k++) s[3 + k] = bx.quat[k];
+  for (int k = 0; k < 6; k++) s[7 + k] = bx.vel[k];
+}
+double hc_tan_yaw(const double* q) { return push_tan_yaw(q); }
+void hc_quat2mat(const double* q, double* R) { quat2mat(q, R); }
 }

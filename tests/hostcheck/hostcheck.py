@@ -243,3 +243,63 @@ class StackHostCheck:
         out = np.zeros((48, 10))
         n = self.L.hc_stack_contacts(self.h, _p(out))
         return out[:min(n, ncon)]
+
+
+# ---------------------------------------------------------------- leaf routines of the contact engines by themselves (tests/contact_leaf_cases.py)
+def _f(a):
+    return np.ascontiguousarray(a, float)
+
+
+def box_box_R(p1, R1, s1, p2, R2, s2, margin, cap=8):
+    """box_box with row-major rotations: (count, rec [8, 7] pre-filled with NaN)."""
+    a = [_f(v) for v in (p1, R1, s1, p2, R2, s2)]
+    rec = np.full((8, 7), np.nan)
+    n = lib().hc_box_box_R(*[_p(v) for v in a], C.c_double(margin), int(cap), _p(rec))
+    return n, rec
+
+
+def cyl_box_axis(pc, axis, rad, half, pb, Rb, sb, margin):
+    """cyl_box: (hit, out [7] pre-filled with NaN)."""
+    a = [_f(v) for v in (pc, axis, pb, Rb, sb)]
+    out = np.full(7, np.nan)
+    hit = lib().hc_cyl_box_axis(_p(a[0]), _p(a[1]), C.c_double(rad), C.c_double(half), _p(a[2]), _p(a[3]), _p(a[4]), C.c_double(margin), _p(out))
+    return bool(hit), out
+
+
+def cone_eval(jar, Dn, Dt, mu, fric, twin=False):
+    """cone_eval (twin: gt_cone_eval) -> [cost, force3, Hc9]."""
+    L = lib()
+    L.hc_cone_eval.restype = C.c_double
+    jar, o = _f(jar), np.full(13, np.nan)
+    f, Hc = np.zeros(3), np.zeros(9)
+    o[0] = L.hc_cone_eval(_p(jar), C.c_double(Dn), C.c_double(Dt), C.c_double(mu), C.c_double(fric), _p(f), _p(Hc), int(twin))
+    o[1:4], o[4:] = f, Hc
+    return o
+
+
+def ldl(n, A, b, twin=False):
+    """ldl_n<n> + ldl_solve_n<n> (twin: gt_*) on the packed lower triangle A -> (ok, L packed, d, x)."""
+    A, b = _f(A).copy(), _f(b)
+    x, d = np.zeros(n), np.zeros(n)
+    ok = lib().hc_ldl(int(n), _p(A), _p(b), _p(x), _p(d), int(twin))
+    assert ok >= 0
+    return bool(ok), A, d, x
+
+
+def cube_integrate(state13, acc6, h, K=1):
+    s, a = _f(state13).copy(), _f(acc6)
+    lib().hc_cube_integrate(_p(s), _p(a), C.c_double(h), int(K))
+    return s
+
+
+def tan_yaw(q):
+    L = lib()
+    L.hc_tan_yaw.restype = C.c_double
+    q = _f(q)
+    return L.hc_tan_yaw(_p(q))
+
+
+def quat2mat(q):
+    q, R = _f(q), np.zeros(9)
+    lib().hc_quat2mat(_p(q), _p(R))
+    return R
