@@ -54,7 +54,7 @@ TAG_BC_GMM = 0x474D0000      # ... of d3il_bc_gmm (policies.BC_GMM_TAG), or-ed w
 HXG_CLIPPED, HXG_NONFINITE, HXG_LAUNCHES, HXG_N = 0, 1, 2, 4      # the counters of d3il_f16x3_set_guard (D3IL_HXG_*)
 
 EXPORTS = ["d3il_create", "d3il_destroy", "d3il_start", "d3il_reset", "d3il_step", "d3il_get_buffers", "d3il_get_state",
-           "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_beso_step", "d3il_ddpm_mlp_chain", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_bet_mlp_f32", "d3il_bc_gmm", "d3il_gpt_bc_head_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
+           "d3il_set_state", "d3il_policy_begin", "d3il_policy_action", "d3il_attention_causal_f32", "d3il_layernorm_f32", "d3il_mlp_gelu_residual_f32", "d3il_mlp_ln_gelu_residual_f32", "d3il_linear120_f32", "d3il_mlp_ln_gelu_residual_f16x3", "d3il_linear120_f16x3", "d3il_attn_half_f16x3", "d3il_gpt_trunk72_f16x3", "d3il_f16x3_set_guard", "d3il_bet_head_f32", "d3il_ddpm_gpt_step_f32", "d3il_beso_step", "d3il_ddpm_mlp_chain", "d3il_ibc_langevin_f32", "d3il_act_chunk_f32", "d3il_ddpm_act_chunk_f32", "d3il_cvae_decode_f32", "d3il_bet_mlp_f32", "d3il_bc_gmm", "d3il_gpt_bc_head_f32", "d3il_ddpm_mlp_f32", "d3il_resmlp_f32", "d3il_auto_reset", "d3il_set_tally", "d3il_count_metrics",
            "d3il_rccl_available", "d3il_comm_unique_id", "d3il_comm_init", "d3il_comm_count", "d3il_comm_destroy", "d3il_reduce_metrics", "d3il_set_timing",
            "d3il_last_step_ms", "d3il_timing_stats", "d3il_step_auto_reset", "d3il_random_rollout_step", "d3il_random_rollout_prepare", "d3il_group_create", "d3il_group_flush", "d3il_group_destroy", "d3il_group_set_option", "d3il_group_stats", "d3il_group_pipeline_stats", "d3il_set_option", "d3il_set_link_guard", "d3il_debug_stats", "d3il_debug_wave_stats", "d3il_debug_wave_counts", "d3il_debug_scratch", "d3il_debug_build_flags", "d3il_last_error", "d3il_blob_sizeof", "d3il_version"]
 
@@ -112,9 +112,15 @@ SIGNATURES4 = _table({
     "d3il_bc_gmm": "n_env:l t_device state " + _RESMLP + " w_feat b_feat w_logit b_logit w_mean b_mean w_std b_std " + _TAIL + " seed:q env_offset:q u_in z_in actions comps u_out z_out "
                    "probs obs_dim:i G:i A:i hidden:i n_blocks:i std_mode:i min_std:f",
 })
+# The policy kernel entries whose prototype has its return type on a line of its own (``int`` / ``d3il_*_f16x3(...)``: the first table's test pins the number of
+# one-line suffixed prototypes), in the same format; tests/test_capi_signatures5.py holds this table against the header.
+SIGNATURES5 = _table({
+    "d3il_gpt_trunk72_f16x3": "x w_packed vec ln_eps:f out n_seq:l T:i n_layer:i",
+})
+ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES2, **SIGNATURES3, **SIGNATURES4, **SIGNATURES5}
 # what launch() works from, resolved once per entry: the keywords it demands (everything but the stream), the same as a set, the positions of the pointers
 _LAUNCH = {name: (tuple(n for n, _ in sig[:-1]), frozenset(n for n, _ in sig[:-1]), tuple(i for i, (_, t) in enumerate(sig[:-1]) if t is C.c_void_p))
-           for name, sig in {**SIGNATURES, **SIGNATURES2, **SIGNATURES3, **SIGNATURES4}.items()}
+           for name, sig in ALL_SIGNATURES.items()}
 
 
 class D3ilError(RuntimeError):
@@ -149,7 +155,7 @@ def load():
         L.d3il_policy_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.d3il_policy_action.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.d3il_count_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        for name, sig in {**SIGNATURES, **SIGNATURES2, **SIGNATURES3, **SIGNATURES4}.items():
+        for name, sig in ALL_SIGNATURES.items():
             if hasattr(L, name):      # (an older build loaded through D3IL_LIB_PATH lacks the newest entries: skipped, not an error)
                 getattr(L, name).argtypes = [t for _, t in sig]
         L.d3il_f16x3_set_guard.argtypes = [C.c_void_p]

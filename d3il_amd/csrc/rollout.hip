@@ -26,6 +26,7 @@ constexpr int WAVE = 64;
 #include "stack_kernels.h"
 #include "policy_common.h"
 #include "policy_f16x3.h"
+#include "policy_trunk72.h"
 #include "policy_bet.h"
 #include "policy_ddpm_gpt.h"
 #include "policy_beso.h"
@@ -1447,6 +1448,27 @@ int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln
     hipLaunchKernelGGL((k_attn_half_f16x3<4, 16, true>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
   else
     hipLaunchKernelGGL((k_attn_half_f16x3<4, 16, false>), dim3((unsigned)((n_seq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (const hx_h8*)w_packed, b_qkv, b_proj, out, n_seq, T, ln_weight, ln_bias, ln_eps, counts);
+  HIPCHK(hipGetLastError());
+  return D3IL_OK;
+}
+int d3il_gpt_trunk72_f16x3(const float* x, const void* w_packed, const float* vec, float ln_eps, float* out, long n_seq, int T, int n_layer, void* stream) {
+  if (!x || !w_packed || !vec || !out) return fail(D3IL_EINVAL, "d3il_gpt_trunk72_f16x3: null argument");
+  if (T < 1 || T > 16 || n_layer < 1 || n_layer > T72_MAX_LAYERS || n_seq < 1)
+    return fail(D3IL_EUNSUPPORTED, "d3il_gpt_trunk72_f16x3: built for 1 <= T <= 16 tokens (whole sequences per matrix-core tile), 1 .. 8 layers and n_seq >= 1");
+  if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)vec | (uintptr_t)out) % 16 != 0) return fail(D3IL_EINVAL, "d3il_gpt_trunk72_f16x3: pointers must be 16-byte aligned");
+  if (x == out) return fail(D3IL_EINVAL, "d3il_gpt_trunk72_f16x3: out must not alias x (padding rows re-read a row another wave may have written)");
+  // tiles of floor(16 / T) sequences; eight waves per workgroup once every CU gets one, four below that (more workgroups to spread)
+  const long spt = 16 / T, tiles = (n_seq + spt - 1) / spt;
+  long long* const counts = g_hx_guard_counts;
+  const hx_h8* const wp = (const hx_h8*)w_packed;
+  if (tiles >= T72_WIDE_TILES && counts)
+    hipLaunchKernelGGL((k_gpt_trunk72_f16x3<8, true>), dim3((unsigned)((tiles + 7) / 8)), dim3(512), 0, (hipStream_t)stream, x, wp, vec, ln_eps, out, n_seq, T, n_layer, counts);
+  else if (tiles >= T72_WIDE_TILES)
+    hipLaunchKernelGGL((k_gpt_trunk72_f16x3<8, false>), dim3((unsigned)((tiles + 7) / 8)), dim3(512), 0, (hipStream_t)stream, x, wp, vec, ln_eps, out, n_seq, T, n_layer, counts);
+  else if (counts)
+    hipLaunchKernelGGL((k_gpt_trunk72_f16x3<4, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, wp, vec, ln_eps, out, n_seq, T, n_layer, counts);
+  else
+    hipLaunchKernelGGL((k_gpt_trunk72_f16x3<4, false>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, wp, vec, ln_eps, out, n_seq, T, n_layer, counts);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

@@ -576,12 +576,169 @@ for _name in ("wp_qkv", "wp_proj", "wp_mlp", "b_qkv", "hp_qkv", "hp_proj", "hp_m
     setattr(_Block, "_" + _name, property(lambda self, _name=_name: self._packed.buf[_name]))
 
 
+# ------------------------------------------------------------------------------------------------ the 72-wide trunk: the whole block chain in one launch
+TRUNK72_STAGES, TRUNK72_STAGE_V, TRUNK72_VEC = 28, 768, 936      # csrc/policy_trunk72.h: stages per layer, 16-byte vectors per stage, f32 vector entries per layer
+TRUNK72_WIDE_TILES = 2048      # (T72_WIDE_TILES: launches of that many 16-row tiles use workgroups of eight tiles, smaller ones of four)
+TRUNK72_DEFAULT = "1"          # D3IL_POLICY_TRUNK72 when unset (what the measurement chose)
+
+
+@_cached_index
+def trunk72_pack_index(device) -> torch.Tensor:
+    """Gather index [28 stages][6][64 lanes][8 e] into cat(Wqkv [216, 72], Wproj [72, 72], W1 [288, 72], W2 [72, 288], one zero) of ONE layer for
+    d3il_gpt_trunk72_f16x3 - without the half dimension (the packer interleaves hi / lo), lane = 16 g + i:
+    stages 0 .. 6 (q | k | v) and 7 .. 9 (projection): entry (u * 3 + s) = W[16 (2 stage + u) + i][32 s + 8 g + e]; stage 10 + 2 k: the same form with fc1's tiles 2 k + u;
+    stage 11 + 2 k: entry t = W2[16 t + i][32 k + 16 (e >> 2) + 4 g + (e & 3)]; zero beyond the matrices."""
+    C, H = 72, 288
+    bases = (0, 3 * C * C, 4 * C * C, 4 * C * C + H * C)
+    zero = 4 * C * C + 2 * H * C
+    s_ = torch.arange(3).view(1, -1, 1, 1, 1)
+    g = torch.arange(4).view(1, 1, -1, 1, 1)
+    i = torch.arange(16).view(1, 1, 1, -1, 1)
+    e = torch.arange(8).view(1, 1, 1, 1, -1)
+
+    def product(n_tiles, N, base):      # [n_tiles / 2 stages][6 = (u, s)][64][8]
+        t = torch.arange(n_tiles).view(-1, 1, 1, 1, 1)
+        row, k = 16 * t + i, 32 * s_ + 8 * g + e
+        return torch.where((row < N) & (k < C), base + row * C + k, torch.full_like(row + k, zero)).reshape(n_tiles // 2, 6, 64, 8)
+
+    k_ = torch.arange(H // 32).view(-1, 1, 1, 1, 1)
+    t6 = torch.arange(6).view(1, -1, 1, 1, 1)
+    row, hid = 16 * t6 + i, 32 * k_ + 16 * (e >> 2) + 4 * g + (e & 3)
+    fc2 = torch.where(row < C, bases[3] + row * H + hid, torch.full_like(row + hid, zero)).reshape(H // 32, 6, 64, 8)
+    mlp = torch.stack((product(H // 16, H, bases[2]), fc2), dim=1).reshape(2 * (H // 32), 6, 64, 8)
+    idx = torch.cat((product(14, 3 * C, bases[0]), product(6, C, bases[1]), mlp), dim=0)
+    assert idx.shape[0] == TRUNK72_STAGES
+    return idx.to(device)
+
+
+def trunk72_layer_matrices(blk):
+    """The four matrices of a block in the order trunk72_pack_index reads them: Wqkv (query | key | value rows), Wproj, W1, W2."""
+    a = blk.attn
+    return (torch.cat((a.query.weight, a.key.weight, a.value.weight), dim=0), a.proj.weight, blk.mlp[0].weight, blk.mlp[2].weight)
+
+
+def pack_trunk72_weights(blocks) -> dict:
+    """The chain's weights for d3il_gpt_trunk72_f16x3: ``w`` f16 [n_layer][28][768][8] (vector (entry * 2 + p) * 64 + lane of a stage: p = 0 the high half, 1 the low half
+    times 2^11; the layout is in include/d3il_rollout.h), ``vec`` f32 [n_layer][936] = ln1.w | ln1.b | b_qkv | b_proj | ln2.w | ln2.b | b1 | b2, ``w_oor`` the entries
+    of the matrices the split cannot carry (0-d int64, no synchronisation)."""
+    ws, vecs, oor = [], [], 0
+    for blk in blocks:
+        mats = trunk72_layer_matrices(blk)
+        idx = trunk72_pack_index(mats[0].device)
+        hi, lo = split_f16(torch.cat([m.reshape(-1) for m in mats] + [mats[0].new_zeros(1)]))
+        ws.append(torch.stack((hi[idx], lo[idx]), dim=2).reshape(TRUNK72_STAGES, TRUNK72_STAGE_V, 8))
+        a = blk.attn
+        vecs.append(torch.cat((blk.ln1.weight, blk.ln1.bias, a.query.bias, a.key.bias, a.value.bias, a.proj.bias, blk.ln2.weight, blk.ln2.bias, blk.mlp[0].bias,
+                               blk.mlp[2].bias)).detach().to(torch.float32))
+        oor = oor + sum(weights_out_of_range(m) for m in mats)
+    return {"w": torch.stack(ws).contiguous(), "vec": torch.stack(vecs).contiguous(), "w_oor": oor}
+
+
+def _trunk72_params(blocks):
+    out = []
+    for blk in blocks:
+        a = blk.attn
+        out += [a.query.weight, a.key.weight, a.value.weight, a.proj.weight, blk.mlp[0].weight, blk.mlp[2].weight, blk.ln1.weight, blk.ln1.bias, a.query.bias, a.key.bias,
+                a.value.bias, a.proj.bias, blk.ln2.weight, blk.ln2.bias, blk.mlp[0].bias, blk.mlp[2].bias]
+    return out
+
+
+def trunk72_packed(blocks) -> PackedWeights:
+    """The chain's PackedWeights, a plain attribute of the ``nn.Sequential`` of blocks (state_dict() keeps the reference's names; a deep copy gets its own)."""
+    pw = blocks.__dict__.get("_trunk72")
+    if pw is None:
+        pw = blocks.__dict__["_trunk72"] = PackedWeights()
+    return pw
+
+
+def trunk72_shape_refusal(blocks):
+    """Why the chain ``blocks`` is not the shape d3il_gpt_trunk72_f16x3 is built for (n_embd 72 in 4 heads, hidden 288, 1 .. 8 blocks, ONE LayerNorm epsilon), or None."""
+    if not isinstance(blocks, nn.Sequential) or not 1 <= len(blocks) <= 8:
+        return "needs 1 .. 8 blocks in an nn.Sequential"
+    for blk in blocks:
+        if not isinstance(blk, _Block) or tuple(blk.mlp[0].weight.shape) != (288, 72) or tuple(blk.mlp[2].weight.shape) != (72, 288) or blk.attn.n_head != 4:
+            return "a block is not (n_embd 72, 4 heads, hidden 288)"
+        if blk.ln1.eps != blocks[0].ln1.eps or blk.ln2.eps != blocks[0].ln1.eps:
+            return "the LayerNorms differ in eps"
+    return None
+
+
+def trunk72_switch_on() -> bool:
+    return policy_gemm_mode() == "f16x3" and os.environ.get("D3IL_POLICY_TRUNK72", TRUNK72_DEFAULT) != "0"
+
+
+def trunk72_static_ok(blocks) -> bool:
+    """The chain takes the one-launch trunk kernel wherever its input allows: shape, f32 on a HIP device, D3IL_POLICY_GEMM=f16x3 and D3IL_POLICY_TRUNK72 not 0."""
+    if not trunk72_switch_on() or trunk72_shape_refusal(blocks) is not None:      # (the switch first: two dictionary reads when it is off)
+        return False
+    return all(blk.mlp[0].weight.is_cuda and blk.mlp[0].weight.dtype == torch.float32 for blk in blocks)
+
+
+def trunk72_input_refusal(blocks, x):
+    """Why the input ``x`` cannot go through the trunk kernel (whatever the device), or None: contiguous f32 [B >= 1, T <= 16, 72], 16-byte aligned, no gradients wanted."""
+    if x.dim() != 3 or x.shape[2] != 72 or not 1 <= x.shape[1] <= 16 or x.shape[0] < 1:
+        return "x is not [B >= 1, 1 <= T <= 16, 72]"
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.data_ptr() % 16 != 0:
+        return "x is not contiguous, 16-byte aligned f32"
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in blocks.parameters())):
+        return "gradients are wanted (the kernel is inference only)"
+    return None
+
+
+def trunk72(blocks, x):
+    """The block chain on x [B, T, 72] through d3il_gpt_trunk72_f16x3 (the caller has checked trunk72_static_ok / trunk72_input_refusal)."""
+    from . import capi
+    if not _ENV_GUARD_TRIED:
+        _env_range_guard(x.device)
+    w = trunk72_packed(blocks).current(_trunk72_params(blocks), lambda: pack_trunk72_weights(blocks))
+    out = torch.empty_like(x)
+    capi.launch("d3il_gpt_trunk72_f16x3", x.device, x=x, w_packed=w["w"], vec=w["vec"], ln_eps=float(blocks[0].ln1.eps), out=out, n_seq=x.shape[0], T=x.shape[1],
+                n_layer=len(blocks))
+    return out
+
+
+def run_blocks(blocks, x, keep=None):
+    """The one place that walks a block chain: ``blocks`` (the nn.Sequential of _Block) on x [B, T, C]; with ``keep`` (token positions) the result is [B, len(keep), C].
+    A 72-wide chain of 4-head blocks on a HIP device runs as ONE launch (trunk72) and the rows are selected afterwards - everything behind the attention is row-wise,
+    the numbers are the same; every other chain runs block by block, the last one with ``keep``."""
+    if x.is_cuda and trunk72_static_ok(blocks) and trunk72_input_refusal(blocks, x) is None:
+        out = trunk72(blocks, x)
+        return out if keep is None else out.index_select(1, keep)
+    for blk in blocks[:-1]:
+        x = blk(x)
+    return blocks[-1](x, keep=keep)
+
+
 def ensure_blocks_packed(blocks) -> list:
-    """ensure_packed() of every block that can take the matrix-core kernels (OUTSIDE a captured chain: an EMA swap changes the packed copies); returns those blocks."""
+    """ensure_packed() of every block that can take the matrix-core kernels, and of the chain's own pack where it takes the trunk kernel (OUTSIDE a captured chain:
+    an EMA swap changes the packed copies); returns those blocks."""
     fused = [blk for blk in blocks if blk._fused_static_ok()]
     for blk in fused:
         blk.ensure_packed()
+    if trunk72_static_ok(blocks):
+        trunk72_packed(blocks).ensure(_trunk72_params(blocks), lambda: pack_trunk72_weights(blocks))
     return fused
+
+
+def invalidate_blocks_packed(blocks):
+    """Force a repack of the blocks' and the chain's packed weights at the next ensure (after ``param.data`` writes, which the version counters do not see)."""
+    for blk in blocks:
+        blk.invalidate_packed()
+    if isinstance(blocks, nn.Module) and "_trunk72" in blocks.__dict__:
+        blocks.__dict__["_trunk72"].invalidate()
+
+
+def blocks_f16x3(blocks) -> bool:
+    """Does the chain run split-f16 kernels the range guard instruments (the blocks' own or the trunk kernel)?"""
+    return policy_gemm_mode() == "f16x3" and (any(blk._fused_static_ok() for blk in blocks) or trunk72_static_ok(blocks))
+
+
+def blocks_w_oor(blocks) -> int:
+    """Entries of the chain's f16x3-packed matrices that are NaN / Inf or beyond +-65504 (packing first where needed); one synchronising read."""
+    n = sum(blk._w_oor for blk in ensure_blocks_packed(blocks))
+    if trunk72_static_ok(blocks):
+        n = n + trunk72_packed(blocks).buf["w_oor"]
+    return int(n)
 
 
 class DiffusionGPT(nn.Module):
@@ -618,18 +775,12 @@ class DiffusionGPT(nn.Module):
         b, t, xbuf = ctx["b"], ctx["t"], ctx["xbuf"]
         xbuf[:, 0] = ctx["emb_all"][i]
         xbuf[:, 2::2] = torch.addmm(ctx["bias_pos"], actions.reshape(b * t, -1), self.action_emb.weight.t(), alpha=c_in).view(b, t, -1)
-        x = xbuf
-        for blk in self.blocks[:-1]:
-            x = blk(x)
-        x = _layer_norm(self.ln_f, self.blocks[-1](x, keep=ctx["keep"]).contiguous())
+        x = _layer_norm(self.ln_f, run_blocks(self.blocks, xbuf, keep=ctx["keep"]).contiguous())
         return self.action_pred(x)
 
     def hidden(self, xbuf, keep):
         """The block chain on a token buffer [b, 2 t + 1, C]: the last block's output at the positions ``keep`` (before ln_f) - BESONativePolicy's form."""
-        x = xbuf
-        for blk in self.blocks[:-1]:
-            x = blk(x)
-        return self.blocks[-1](x, keep=keep)
+        return run_blocks(self.blocks, xbuf, keep=keep)
 
     def forward(self, states, actions, sigma):
         b, t, _ = states.size()
@@ -638,12 +789,10 @@ class DiffusionGPT(nn.Module):
         state_x, action_x = self.tok_emb(states) + pos, self.action_emb(actions) + pos
         sa = torch.stack([state_x, action_x], dim=1).permute(0, 2, 1, 3).reshape(b, 2 * t, self.embed_dim)
         x = torch.cat([emb_t, sa], dim=1)
-        for blk in self.blocks[:-1]:
-            x = blk(x)
         # only the action positions (tokens 2, 4, ..., 2 t) are decoded: the last block's output projection and MLP, the final LayerNorm and the head run
         # on those rows only (row-wise operations: the same numbers as decoding everything and slicing, score_gpts.py:340-361)
         keep = torch.arange(2, 2 * t + 1, 2, device=x.device)
-        x = _layer_norm(self.ln_f, self.blocks[-1](x, keep=keep).contiguous())
+        x = _layer_norm(self.ln_f, run_blocks(self.blocks, x, keep=keep).contiguous())
         return self.action_pred(x)
 
 
@@ -1066,7 +1215,7 @@ class BESOPolicy:
     def weights_out_of_range(self) -> int:
         """Entries of the blocks' f16x3-packed weight matrices that are NaN / Inf or beyond +-65504 (they saturate on the host, policies.split_f16); one
         synchronising read.  Blocks that have not been packed yet are packed first."""
-        return int(sum(blk._w_oor for blk in ensure_blocks_packed(self.inner.blocks)))
+        return blocks_w_oor(self.inner.blocks)
 
     def range_report(self) -> dict:
         """The active RangeGuard's counters (clipped / nonfinite / launches) plus ``weights_out_of_range``."""
@@ -1442,8 +1591,8 @@ def bet_uniforms(seed: int, env_offset: int, n: int, t: int):
 class MinGPTTrunk(nn.Module):
     """The GPT of the reference's BeT (agents/models/bet/libraries/mingpt/model.py:128-250; continuous input, eval mode) with the reference's parameter names -
     ``tok_emb``, ``pos_emb``, ``blocks.N.(ln1 | attn.key / query / value / proj | ln2 | mlp.0 / mlp.2)``, ``ln_f``, ``head`` (no bias, V (1 + A) outputs) - so
-    ``load_state_dict`` of a reference state dict works.  The blocks are ``_Block``: 120-wide trunks on the device take the matrix-core kernels of the DiffusionGPT,
-    every other width runs the same blocks through torch, batched.  ``hidden`` stops BEFORE ``ln_f``: the final LayerNorm and the head belong to the sampling tail."""
+    ``load_state_dict`` of a reference state dict works.  The blocks are ``_Block``, walked by ``run_blocks``: 120-wide trunks on the device take the matrix-core kernels
+    of the DiffusionGPT, 72-wide 4-head trunks the one-launch trunk kernel, every other shape runs the same blocks through torch, batched.  ``hidden`` stops BEFORE ``ln_f``: the final LayerNorm and the head belong to the sampling tail."""
 
     def __init__(self, input_dim, n_embd, n_layer, n_head, block_size, vocab_size=64, action_dim=0):
         super().__init__()
@@ -1460,9 +1609,7 @@ class MinGPTTrunk(nn.Module):
         t = x.shape[1]
         assert t <= self.block_size, "Cannot forward, model block size is exhausted."
         h = (self.tok_emb(x) + self.pos_emb[:, :t, :]).contiguous()
-        for blk in self.blocks[:-1]:
-            h = blk(h)
-        return self.blocks[-1](h, keep=keep)
+        return run_blocks(self.blocks, h, keep=keep)
 
     def forward(self, x):
         """The reference's GPT.forward without targets: [N, T, V (1 + A)]."""
@@ -1537,7 +1684,7 @@ class BeTPolicy(NativePolicy):
     @property
     def f16x3_blocks(self) -> bool:
         """The trunk runs the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
-        return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.trunk.blocks)
+        return blocks_f16x3(self.trunk.blocks)
 
     def _state(self, n):
         """The observation window for n lanes; a new size starts empty."""
@@ -1559,8 +1706,7 @@ class BeTPolicy(NativePolicy):
         return c
 
     def invalidate_packed(self):
-        for blk in self.trunk.blocks:
-            blk.invalidate_packed()
+        invalidate_blocks_packed(self.trunk.blocks)
 
     def ensure_packed(self):
         """The packed weights are the blocks' own."""
@@ -1707,10 +1853,7 @@ class DiffusionGPTDenoiser(nn.Module):
 
     def hidden(self, xbuf, keep):
         """The block chain on a token buffer [b, 2 t + 1, C]: the last block's output at the positions ``keep`` (before ln_f)."""
-        x = xbuf
-        for blk in self.blocks[:-1]:
-            x = blk(x)
-        return self.blocks[-1](x, keep=keep)
+        return run_blocks(self.blocks, xbuf, keep=keep)
 
     def forward(self, actions, time, states, goals=None):
         """The reference's forward without goals: eps [b, t, A] for actions [b, t, A], time [b] (integers) and states [b, t, state_dim]."""
@@ -1808,7 +1951,7 @@ class DDPMGPTPolicy(NativePolicy):
     @property
     def f16x3_blocks(self) -> bool:
         """The blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
-        return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.model.blocks)
+        return blocks_f16x3(self.model.blocks)
 
     def _state(self, n):
         """The observation window for n lanes; a new size starts empty."""
@@ -1847,8 +1990,7 @@ class DDPMGPTPolicy(NativePolicy):
 
     def invalidate_packed(self):
         super().invalidate_packed()
-        for blk in self.model.blocks:
-            blk.invalidate_packed()
+        invalidate_blocks_packed(self.model.blocks)
 
     def ensure_packed(self):
         """The packed tables (on the CPU too: the torch path reads them) and the blocks' packed weights follow the parameters (outside any capture)."""
@@ -2315,11 +2457,11 @@ class BESONativePolicy(NativePolicy):
     @property
     def f16x3_blocks(self) -> bool:
         """The blocks run the split-f16 kernels the range guard instruments (CapturedPolicy captures again when the guard changes)."""
-        return policy_gemm_mode() == "f16x3" and any(blk._fused_static_ok() for blk in self.model.blocks)
+        return blocks_f16x3(self.model.blocks)
 
     def weights_out_of_range(self) -> int:
         """As BESOPolicy.weights_out_of_range: entries of the blocks' f16x3-packed matrices that are NaN / Inf or beyond +-65504; one synchronising read."""
-        return int(sum(blk._w_oor for blk in ensure_blocks_packed(self.model.blocks)))
+        return blocks_w_oor(self.model.blocks)
 
     def range_report(self) -> dict:
         """The active RangeGuard's counters (clipped / nonfinite / launches) plus ``weights_out_of_range``."""
@@ -2371,8 +2513,7 @@ class BESONativePolicy(NativePolicy):
 
     def invalidate_packed(self):
         super().invalidate_packed()
-        for blk in self.model.blocks:
-            blk.invalidate_packed()
+        invalidate_blocks_packed(self.model.blocks)
 
     def ensure_packed(self):
         """The packed tables (on the CPU too: the torch path reads them) and the blocks' packed weights follow the parameters (outside any capture)."""

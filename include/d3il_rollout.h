@@ -214,6 +214,24 @@ int d3il_linear120_f16x3(const float* xin, const float* ln_weight, const float* 
  * (policies.pack_linear120_weights_f16x3 of both, concatenated).  out must not alias x. */
 int d3il_attn_half_f16x3(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* w_packed, const float* b_qkv, const float* b_proj, float* out,
                          long n_seq, int T, int n_head, int C, void* stream);
+/* The whole block chain of a 72-wide transformer trunk (n_embd 72, 4 heads of 18, hidden 288: the Avoiding / Aligning / Pushing / Sorting-2 configs) in one launch
+ * (csrc/policy_trunk72.h), split-f16 products as above: for l < n_layer
+ *     x = x + proj_l(causal_attention_4heads(LayerNorm1_l(x) Wqkv_l' + bqkv_l)) + bproj_l;   x = x + W2_l GELU(W1_l LayerNorm2_l(x) + b1_l) + b2_l     (exact GELU).
+ * x and out are f32 [n_seq][T][72]; one wave owns floor(16 / T) whole sequences, the residual stream never leaves the CU.  out must not alias x.
+ * w_packed: f16, n_layer x 28 stages x 768 vectors of 16 bytes (policies.pack_trunk72_weights), lane = 16 g + i, p = 0 the high half, 1 the low half times 2^11,
+ * zero beyond the matrices:
+ *   stages 0 .. 6, vector ((u * 3 + s) * 2 + p) * 64 + lane = Wqkv_p[16 (2 stage + u) + i][32 s + 8 g + e], Wqkv = query | key | value rows, 216 x 72;
+ *   stages 7 .. 9 the same form with the projection (stage - 7 for stage);
+ *   stage 10 + 2 k (k < 9), vector ((tile * 3 + s) * 2 + p) * 64 + lane = W1_p[32 k + 16 tile + i][32 s + 8 g + e];
+ *   stage 11 + 2 k, vector (t * 2 + p) * 64 + lane = W2_p[16 t + i][32 k + 16 (e >> 2) + 4 g + (e & 3)], t < 6.
+ * vec: f32, n_layer x 936: ln1.weight | ln1.bias | b_qkv (216) | b_proj | ln2.weight | ln2.bias | b1 (288) | b2.  ln_eps: the one epsilon of all 2 n_layer LayerNorms.
+ * Built for 1 <= T <= 16, 1 <= n_layer <= 8, n_seq >= 1: D3IL_EUNSUPPORTED otherwise; D3IL_EINVAL for a null pointer, one that is not 16-byte aligned, or out == x;
+ * both answered before any launch.  Under the range / NaN guard below the split sites per layer are the LayerNorm1 row, the attention output row, the LayerNorm2 row
+ * and the GELU outputs; a row is counted at most once per counter and LAUNCH (all layers); a non-finite operand makes its row and the later tokens of its own
+ * sequence NaN and changes no other sequence, those that share its tile included.
+ * (The return type stands on a line of its own: tests/test_capi_signatures.py pins the number of `int d3il_*_f16x3(` lines; tests/test_capi_signatures5.py reads this form.) */
+int
+d3il_gpt_trunk72_f16x3(const float* x, const void* w_packed, const float* vec, float ln_eps, float* out, long n_seq, int T, int n_layer, void* stream);
 /* Sampling head of the batched Behaviour-Transformer policy (policies.BeTPolicy; bet_agent.py:359-372, latent_generators/mingpt.py:155-186, k_means.py:111-138) in one
  * launch, f32 throughout.  Per row: x = LayerNorm(h); logit_v = w_head[v] . x (v < V); p = exp(logit - max), S = sum p, c = inclusive prefix sums; u = u_in[row] or
  * 24 bits of Philox4x32-10 with key = seed and counter = (env_offset + row, *t_device, a tag word other than the 0 of the random-policy harness), so 0 <= u <= 1 - 2^-24;
@@ -404,7 +422,7 @@ int d3il_gpt_bc_head_f32(const float* h, const float* ln_weight, const float* ln
 /* Range / NaN guard of the three split-f16 entry points above (opt-in; off = the kernels and results of a library without it).
  * counts_device: device i64[4] owned and zeroed by the caller, or NULL = guard off (the default).  Process-wide: ONE pointer, to the memory of ONE device - for a
  * process that drives one GPU (as every process of this project does); it is not synchronised - set it while no other thread launches these kernels.  Read at launch time by d3il_linear120_f16x3,
- * d3il_mlp_ln_gelu_residual_f16x3 and d3il_attn_half_f16x3, which then launch the guarded instantiation of their kernel.  The call itself touches no device.
+ * d3il_mlp_ln_gelu_residual_f16x3, d3il_attn_half_f16x3 and d3il_gpt_trunk72_f16x3, which then launch the guarded instantiation of their kernel.  The call itself touches no device.
  * Split sites: the input row after its LayerNorm (all three), the row's 480 GELU outputs (MLP), the row's 120 attention outputs (attention half).  At a site
  *   a finite operand with |x| > 65504 saturates exactly as without the guard - the row's output is bit-identical - and the row is marked clipped;
  *   a NaN / +-Inf operand goes to the matrix core as NaN: the row is NaN in every output column (as from the f32 entry points), no other row changes, and the row
