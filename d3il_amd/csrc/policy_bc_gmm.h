@@ -1,7 +1,7 @@
 // policy_bc_gmm.h - the whole inference of the batched BC-GMM policy (policies.BCGMMPolicy; agents/models/gmm/bc_gmm.py:13-90 around common/mlp.py ResidualMLPNetwork,
 // sampled once per step as BC_Agent.predict, agents/bc_agent.py:240-271, would with model(state).sample()) as ONE kernel.  Included by rollout.hip behind
-// policy_bet_mlp.h: the trunk is k_resmlp_f32's (mlp_f4, rm_layer, dd_mish), the categorical draw is k_bet_mlp's in the same order of operations (bet_wave_max), the
-// normals are policy_box_muller, the inverse scaling is policy_cvae.h's cvae_unscale (the random stream and the bit test: policy_common.h).
+// policy_bet_mlp.h: the trunk is built from the pieces of policy_resmlp.h, the categorical draw is k_bet_mlp's in the same order of operations (bet_wave_max), the
+// normals are policy_box_muller, the inverse scaling policy_unscale_f64 (with the random stream and the bit test: policy_common.h).
 //
 // For environment n (s = the scaled state row, H = hidden width = mlp_output_dim, G = n_gaussians <= 64, A = output_dim <= 8):
 //   1. h = input layer and residual blocks on s                                        (f32)
@@ -15,10 +15,9 @@
 //      a = 4 (q - 1) + m from word m - words 0, 1 -> the cos and sin of one pair, words 2, 3 the other, as the CVAE latent
 //   8. y_a = clamp(x_a, lo_a, hi_a) scale_a + shift_a                                  (clamp in f32; product and sum in f64 on the f32 operands, rounded once)
 //
-// Tiling: k_bet_mlp's.  A workgroup of eight waves owns 16 rows; the waves share the H / 16 output tiles of a layer, weights stream from L2 in the packed operand
-// order, the activations go from layer to layer through LDS in B-operand order, one barrier per layer, the block count is a loop bound, the input layer is 32
-// columns (7 steps).  One more square layer than k_bet_mlp - the trunk's output layer, no residual, Mish behind it.  The logit layer is ceil(G / 16) output tiles
-// (wave T < ceil(G / 16), one tile each; the waves up to 3 beyond write zeros, so that no LDS word is read unwritten); 16 x 64 logits go to a padded LDS array
+// Tiling: k_bet_mlp's, the trunk policy_resmlp.h's with the 28-column input layer.  One more square layer than k_bet_mlp - the trunk's output layer, no residual,
+// Mish behind it.  The logit layer is ceil(G / 16) output tiles (wave T < ceil(G / 16), one tile each; the waves up to 3 beyond write
+// zeros, so that no LDS word is read unwritten); 16 x 64 logits go to a padded LDS array
 // behind one more barrier.  Then every wave serves two of the 16 rows: lane = component for the draw, and for the head rows eight lanes per action component
 // (group a = lane / 8; lane sub = lane % 8 takes the float4 chunks sub, sub + 8, .. of row k A + a, read row-major from global memory - at most 2 x 512 x 256 x 4 B,
 // it stays in L2) against f read back from LDS, three shuffle steps per group; groups beyond A repeat component A - 1, every lane makes its group's Philox call.
@@ -49,22 +48,9 @@ struct BcGmmArgs {
   int obs, G, A, nblk, std_mode;
 };
 
-// the dot product of head row ``wr`` with row jr of the features in LDS (B-operand order): this lane's chunks sub, sub + 8, ..; the caller sums the eight lanes
-template <int HID>
-__device__ __forceinline__ float bg_row_part(const float* wr, const mlp_f4* xf, int sub, int jr) {
-  float part = 0.f;
-#pragma unroll
-  for (int jj = 0; jj < HID / 32; jj++) {
-    const int q = sub + 8 * jj;      // features 4 q .. 4 q + 3: tile q / 4, lane group q % 4
-    const mlp_f4 wv = *(const mlp_f4*)(wr + 4 * q), xv = xf[(q >> 2) * 64 + (q & 3) * 16 + jr];
-    part += fmaf(wv[3], xv[3], fmaf(wv[2], xv[2], fmaf(wv[1], xv[1], wv[0] * xv[0])));
-  }
-  return part;
-}
-
 template <int HID>
 __global__ __launch_bounds__(512) void k_bc_gmm(BcGmmArgs a) {
-  constexpr int NT = HID / 16, TPW = NT / 8, LAYER_F4 = NT * NT * 64;
+  constexpr int NT = HID / 16, TPW = NT / 8;
   __shared__ mlp_f4 xb[2][NT * 64];
   __shared__ float lg[16 * BG_LSTRIDE];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 15, g = lane >> 4;
@@ -74,64 +60,26 @@ __global__ __launch_bounds__(512) void k_bc_gmm(BcGmmArgs a) {
   const long rj = rowj < n ? rowj : (n - 1);
   // ---- 1. the trunk, as k_resmlp_f32: lane (g, j) holds feature 4 s2 + g of row j
   float in_k[7];
-#pragma unroll
-  for (int s2 = 0; s2 < 7; s2++) { const int f = 4 * s2 + g; in_k[s2] = f < OBS ? a.state[rj * OBS + f] : 0.f; }
+  rm_load_row28(a.state, rj, OBS, g, in_k);
   unsigned bad_in = 0u;
 #pragma unroll
   for (int s2 = 0; s2 < 7; s2++) bad_in |= (unsigned)policy_nonfinite(in_k[s2]);
-  bad_in |= (unsigned)__shfl_xor((int)bad_in, 16); bad_in |= (unsigned)__shfl_xor((int)bad_in, 32);      // every wave, every lane of column j: the verdict on row j's state
-  const mlp_f4* w_in4 = (const mlp_f4*)a.w_in;
+  bad_in = rm_row_or(bad_in);      // every wave, every lane of column j: the verdict on row j's state
   mlp_f4 xo[TPW];
-#pragma unroll
-  for (int q = 0; q < TPW; q++) {
-    const int To = TPW * w + q;
-    mlp_f4 acc = *(const mlp_f4*)(a.b_in + 16 * To + 4 * g);
-    const mlp_f4 a0 = w_in4[(To * 64 + lane) * 2], a1 = w_in4[(To * 64 + lane) * 2 + 1];
-#pragma unroll
-    for (int s2 = 0; s2 < 7; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(s2 < 4 ? a0[s2] : a1[s2 - 4], in_k[s2], acc, 0, 0, 0);
-    xo[q] = acc;
-  }
+  rm_input28<HID>(a.w_in, a.b_in, in_k, xo, w, lane, g);
   int buf = 0;
-#pragma clang loop unroll(disable)
-  for (int b = 0; b < nblk; b++) {
-    mlp_f4 y[TPW];
-#pragma unroll
-    for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(xo[q][0]), dd_mish(xo[q][1]), dd_mish(xo[q][2]), dd_mish(xo[q][3])};
-    __syncthreads();
-    rm_layer<HID, false>((const mlp_f4*)a.w_blk + (long)(2 * b) * LAYER_F4, a.b_blk + (2 * b) * HID, xb[buf], y, w, lane, g);
-    buf ^= 1;
-#pragma unroll
-    for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(y[q][0]), dd_mish(y[q][1]), dd_mish(y[q][2]), dd_mish(y[q][3])};
-    __syncthreads();
-    rm_layer<HID, true>((const mlp_f4*)a.w_blk + (long)(2 * b + 1) * LAYER_F4, a.b_blk + (2 * b + 1) * HID, xb[buf], xo, w, lane, g);
-    buf ^= 1;
-  }
+  rm_blocks<HID>(a.w_blk, a.b_blk, nblk, xb, xo, buf, w, lane, g);
   // ---- 2. the trunk's output layer on h as it is, Mish behind it: f
-#pragma unroll
-  for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = xo[q];
+  rm_store<HID, false>(xb[buf], xo, w, lane);
   __syncthreads();
   rm_layer<HID, false>((const mlp_f4*)a.w_feat, a.b_feat, xb[buf], xo, w, lane, g);
   buf ^= 1;
-#pragma unroll
-  for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(xo[q][0]), dd_mish(xo[q][1]), dd_mish(xo[q][2]), dd_mish(xo[q][3])};
+  rm_store<HID, true>(xb[buf], xo, w, lane);
   __syncthreads();
   // ---- 3. the logit layer: wave T < ceil(G / 16) owns components 16 T .. 16 T + 15; lane (g, j), register r = component 16 T + 4 g + r of row j
   if (w < 4) {
     mlp_f4 acc = mlp_f4{0.f, 0.f, 0.f, 0.f};
-    if (16 * w < G) {
-      const mlp_f4* wl = (const mlp_f4*)a.w_logit + (long)w * (NT * 64) + lane;
-      mlp_f4 acc2 = mlp_f4{0.f, 0.f, 0.f, 0.f};
-      acc = *(const mlp_f4*)(a.b_logit + 16 * w + 4 * g);
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        const mlp_f4 a4 = wl[t * 64], m4 = xb[buf][t * 64 + lane];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0], m4[0], acc, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1], m4[1], acc2, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[2], m4[2], acc, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[3], m4[3], acc2, 0, 0, 0);
-      }
-      acc += acc2;
-    }
+    if (16 * w < G) acc = rm_tile<HID>((const mlp_f4*)a.w_logit + (long)w * (NT * 64), xb[buf], *(const mlp_f4*)(a.b_logit + 16 * w + 4 * g), lane);
 #pragma unroll
     for (int r = 0; r < 4; r++) lg[j * BG_LSTRIDE + 16 * w + 4 * g + r] = acc[r];
   }
@@ -164,7 +112,7 @@ __global__ __launch_bounds__(512) void k_bc_gmm(BcGmmArgs a) {
     if (a.u_in) u = a.u_in[rr];
     else {
       unsigned r4[4];
-      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, BC_GMM_TAG, r4);
+      policy_philox(a.seed, ge, t, BC_GMM_TAG, r4);
       u = policy_uniform24(r4[0]);
     }
     const bool below = on && c <= u * S;
@@ -175,7 +123,7 @@ __global__ __launch_bounds__(512) void k_bc_gmm(BcGmmArgs a) {
     if (a.z_in) z = a.z_in[rr * A + cg];
     else {
       unsigned r4[4];
-      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, BC_GMM_TAG | (unsigned)(1 + (cg >> 2)), r4);
+      policy_philox(a.seed, ge, t, BC_GMM_TAG | (unsigned)(1 + (cg >> 2)), r4);
       const bool second = (cg & 2) != 0;
       float n0, n1;
       policy_box_muller(second ? r4[2] : r4[0], second ? r4[3] : r4[1], n0, n1);
@@ -183,8 +131,8 @@ __global__ __launch_bounds__(512) void k_bc_gmm(BcGmmArgs a) {
     }
     // ---- 5, 6. the head rows of the drawn component (no divergent branch in front of the shuffles: groups beyond A repeat component A - 1)
     const long hr = (long)k * A + cg;
-    float pm = bg_row_part<HID>(a.w_mean + hr * HID, xb[buf], sub, jr), ps = 0.f;
-    if (std_mode != BG_STD_LOW_NOISE) ps = bg_row_part<HID>(a.w_std + hr * HID, xb[buf], sub, jr);
+    float pm = rm_row_part<HID>(a.w_mean + hr * HID, xb[buf], sub, jr), ps = 0.f;
+    if (std_mode != BG_STD_LOW_NOISE) ps = rm_row_part<HID>(a.w_std + hr * HID, xb[buf], sub, jr);
     unsigned hb = 0u;
 #pragma unroll
     for (int jj = 0; jj < HID / 32; jj++) {
@@ -211,7 +159,7 @@ __global__ __launch_bounds__(512) void k_bc_gmm(BcGmmArgs a) {
     const float x = __fadd_rn(mean, __fmul_rn(sd, z));
     if (live) {
       if (comp && sub == 0) {
-        const unsigned yb = __float_as_uint(cvae_unscale(x, cl, ch, sc, sh));
+        const unsigned yb = __float_as_uint(policy_unscale_f64(x, cl, ch, sc, sh));
         ((unsigned*)a.actions)[row * A + grp] = bad ? 0x7FC00000u : yb;
         if (a.z_out) a.z_out[row * A + grp] = z;
       }

@@ -1,7 +1,7 @@
 // policy_bet_mlp.h - the whole inference of the batched BeT-MLP policy (policies.BeTMLPPolicy; agents/bet_mlp_agent.py:366-406 around BeTPolicy.generate_latents,
-// same file 114-147, KMeansDiscretizer.decode_actions and common/mlp.py ResidualMLPNetwork) as ONE kernel.  Included by rollout.hip behind policy_f32.h: the trunk
-// is k_resmlp_f32's (mlp_f4, rm_layer, dd_mish), the draw is steps 3 - 5 of policy_bet.h in the same order of operations (bet_wave_max; the random stream and the
-// bit test: policy_common.h), the inverse scaling is policy_cvae.h's cvae_unscale.
+// same file 114-147, KMeansDiscretizer.decode_actions and common/mlp.py ResidualMLPNetwork) as ONE kernel.  Included by rollout.hip behind policy_resmlp.h: the trunk
+// is k_resmlp_f32's, with rm_layer from that header and the rest as text of its own (see the note on k_resmlp_f32 there), the draw is steps 3 - 5 of policy_bet.h in
+// the same order of operations (bet_wave_max; the random stream, the bit test and the inverse scaling policy_unscale_f64: policy_common.h).
 //
 // For environment n (s = the scaled state row, H = hidden width, V = 64 bins, the network a Mish ResidualMLPNetwork with a V (1 + A)-row output layer WITH bias):
 //   1. h = input layer and residual blocks on s                                   (f32)
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(512) void k_bet_mlp(BetMlpArgs a) {
     else {
       const unsigned long long ge = a.env_offset + (unsigned long long)rr;
       unsigned r4[4];
-      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, BET_MLP_TAG, r4);
+      policy_philox(a.seed, ge, t, BET_MLP_TAG, r4);
       u = policy_uniform24(r4[0]);
     }
     const int cnt = __popcll(__ballot(c <= u * S));
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(512) void k_bet_mlp(BetMlpArgs a) {
     if (live) {
       if (comp && sub == 0) {
         const float v = a.centers[bin * A + grp] + (part + a.b_off[bin * A + grp]);
-        const unsigned yb = __float_as_uint(cvae_unscale(v, cl, ch, sc, sh));
+        const unsigned yb = __float_as_uint(policy_unscale_f64(v, cl, ch, sc, sh));
         ((unsigned*)a.actions)[row * A + grp] = bad ? 0x7FC00000u : yb;
       }
       if (a.probs) a.probs[row * BM_V + lane] = p / S;

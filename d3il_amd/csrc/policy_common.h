@@ -1,5 +1,6 @@
 // policy_common.h - what the policy kernels share (included by rollout.hip in front of the other policy_*.h): the Philox4x32-10 block behind every policy's
-// random stream and the random-policy harness, the conversions from its words to uniforms and normals, the non-finite bit test and the 64-lane sum.
+// random stream and the random-policy harness, the conversions from its words to uniforms and normals, the non-finite bit test, the two forms of the inverse
+// action scaling and the 64-lane sum.
 // The host forms are d3il_amd/policies.py philox4x32_10, philox_words, uniform24 and box_muller_f64.
 #pragma once
 
@@ -16,6 +17,10 @@ __device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned
     c0 = n0; c1 = n1; c2 = n2; c3 = n3; k0 += W0; k1 += W1;
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// the block of a policy's stream for the row with global index ge = env_offset + row: key = seed, counter = (lo32, hi32 of ge, step word t, tag)
+__device__ __forceinline__ void policy_philox(unsigned long long seed, unsigned long long ge, unsigned t, unsigned tag, unsigned* out) {
+  philox4x32_10((unsigned)seed, (unsigned)(seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), t, tag, out);
 }
 // the upper 24 bits of a word as a uniform in [0, 1 - 2^-24] (exact in f32)
 __device__ __forceinline__ float policy_uniform24(unsigned r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
@@ -34,6 +39,20 @@ __device__ __forceinline__ bool policy_nonfinite(float x) {
   unsigned b = __float_as_uint(x);
   asm("" : "+v"(b));
   return (b & 0x7F800000u) == 0x7F800000u;
+}
+// The inverse scaling of an action component, clamp(v) scale + shift, in its two forms.  f64: as the reference's f64 scaler computes it - f64 product and sum of f32
+// operands (no contraction: torch's f64 ops round twice), one rounding to f32.
+__device__ __forceinline__ float policy_unscale_f64(float v, float lo, float hi, float scale, float shift) {
+#pragma clang fp contract(off)
+  const double c = (double)fminf(fmaxf(v, lo), hi);
+  const double p = c * (double)scale;
+  return (float)(p + (double)shift);
+}
+// f32: the product and the sum each rounded (no contraction) - policies.NativePolicy._action_tail with f64 = False
+__device__ __forceinline__ float policy_unscale_f32(float v, float lo, float hi, float scale, float shift) {
+#pragma clang fp contract(off)
+  const float p = fminf(fmaxf(v, lo), hi) * scale;
+  return p + shift;
 }
 // sum over the 64 lanes of a wave, in every lane
 __device__ __forceinline__ float policy_wave_sum(float v) {

@@ -1,6 +1,6 @@
 // policy_cvae.h - the whole inference of the batched conditional-VAE policy (policies.CVAEPolicy; agents/cvae_agent.py:155-170 around
-// agents/models/vae/cvae.py:55-62 over common/mlp.py ResidualMLPNetwork) as ONE kernel.  Included by rollout.hip behind policy_f32.h: it reuses
-// k_resmlp_f32's operand scheme with mlp_f4, rm_layer and dd_mish (the random stream and the bit test: policy_common.h).
+// agents/models/vae/cvae.py:55-62 over common/mlp.py ResidualMLPNetwork) as ONE kernel.  Included by rollout.hip behind policy_resmlp.h, whose pieces the
+// decoder is built from (the random stream, the bit test and the inverse scaling: policy_common.h).
 //
 // For environment n (s = the scaled state row, L = latent width, the decoder a Mish ResidualMLPNetwork on [s | z], f32 throughout):
 //   1. z_a = clamp(z_in[n, a] or Box-Muller on philox4x32_10(seed, (env_offset + n, step word, CVAE_TAG | q)), -0.5, 0.5), component a = 4 q + m takes word m.
@@ -9,12 +9,11 @@
 //   3. actions[n, a] = clamp(out_a, lo_a, hi_a) scale_a + shift_a (the product and the sum in f64 on the f32 operands, as the reference's f64 scaler does;
 //      rounded to f32 once)
 //
-// Tiling: k_resmlp_f32's.  A workgroup of eight waves owns 16 rows; the waves share the HID / 16 output tiles of a layer (wave w: tiles TPW w .. TPW (w + 1) - 1),
-// the weights stream from L2, the activations go from layer to layer through LDS in B-operand order, one barrier per layer; the block count is a loop bound.
-// What differs: (a) the input row is assembled here - the latent is drawn ONCE per workgroup by waves 0 and 1 (thread (q, j): Philox call q of row j, two
-// Box-Muller pairs, four components) and shared through 2.3 KB of LDS behind one more barrier, because the alternative - every lane draws what it needs - costs each
+// Tiling: policy_resmlp.h's (16 rows per workgroup of eight waves, activations through LDS, one barrier per layer).  What differs from k_resmlp_f32: (a) the input
+// row is assembled here - the latent is drawn ONCE per workgroup by waves 0 and 1 (thread (q, j): Philox call q of row j, two Box-Muller pairs,
+// four components) and shared through 2.3 KB of LDS behind one more barrier, because the alternative - every lane draws what it needs - costs each
 // lane of each wave eight Philox calls and eight Box-Muller pairs for its sixteen input features (a lane's features 4 s + g - obs hit one word of up to eight
-// different calls): 4096 Philox calls per workgroup instead of 128, for the price of one barrier; (b) the input layer is 64 columns wide, 16 matrix-core steps on two accumulators; (c) the tail
+// different calls): 4096 Philox calls per workgroup instead of 128, for the price of one barrier; (b) the input layer is the 64-column one (rm_input64); (c) the tail
 // is fused: output bias, clamp, inverse scaling, bit tests; (d) the step word comes from device memory.
 //
 // LDS: xb 2 x NT x 64 float4 (16 / 32 KB), zs 16 x 36 words.  Vector stores only, no inline assembly beyond the empty register barrier of policy_nonfinite; every branch
@@ -28,14 +27,6 @@ namespace d3il {
 constexpr unsigned CVAE_TAG = 0x43560000u;      // fourth counter word = TAG | q (q < 8): never 0, never BET_TAG, never a DDPM_GPT_TAG, IBC_TAG or ACT_TAG word
 constexpr int CVAE_LMAX = 32, CVAE_INMAX = 64, CVAE_AMAX = 16, CVAE_ZSTRIDE = 36;
 
-// clamp(v) scale + shift as the reference computes it: f64 product and sum of f32 operands (no contraction: torch's f64 ops round twice), one rounding to f32
-__device__ __forceinline__ float cvae_unscale(float v, float lo, float hi, float scale, float shift) {
-#pragma clang fp contract(off)
-  const double c = (double)fminf(fmaxf(v, lo), hi);
-  const double p = c * (double)scale;
-  return (float)(p + (double)shift);
-}
-
 struct CvaeArgs {
   const float* state; const float* w_in; const float* b_in; const float* w_blk; const float* b_blk; const float* w_out; const float* b_out;
   const float* lo; const float* hi; const float* scale; const float* shift;
@@ -48,7 +39,7 @@ struct CvaeArgs {
 
 template <int HID>
 __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
-  constexpr int NT = HID / 16, TPW = NT / 8, LAYER_F4 = NT * NT * 64;
+  constexpr int NT = HID / 16, TPW = NT / 8;
   __shared__ mlp_f4 xb[2][NT * 64];
   __shared__ unsigned zs[16 * CVAE_ZSTRIDE];      // the 16 rows' clamped latents (bits; 0x7FC00000 where the unclamped value was NaN / Inf)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 15, g = lane >> 4;
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
       } else {
         const unsigned long long ge = a.env_offset + (unsigned long long)rz;
         unsigned r[4];
-        philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), *a.t_dev, CVAE_TAG | (unsigned)q, r);
+        policy_philox(a.seed, ge, *a.t_dev, CVAE_TAG | (unsigned)q, r);
         policy_box_muller(r[0], r[1], z[0], z[1]); policy_box_muller(r[2], r[3], z[2], z[3]);
       }
 #pragma unroll
@@ -94,53 +85,15 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
   unsigned bad = 0u;      // this lane's quarter of the input row, tested here: in_k is dead after the input layer
 #pragma unroll
   for (int s2 = 0; s2 < 16; s2++) bad |= (unsigned)policy_nonfinite(in_k[s2]);
-  const mlp_f4* w_in4 = (const mlp_f4*)a.w_in;
-  const mlp_f4* w_out4 = (const mlp_f4*)a.w_out;
+  // ---- the decoder's trunk (policy_resmlp.h): 64-column input layer from b_in, the residual blocks, the output tile by wave 0
   mlp_f4 xo[TPW];
-#pragma unroll
-  for (int q = 0; q < TPW; q++) {
-    const int To = TPW * w + q;
-    mlp_f4 acc = *(const mlp_f4*)(a.b_in + 16 * To + 4 * g), acc2 = mlp_f4{0.f, 0.f, 0.f, 0.f};
-    mlp_f4 aw[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) aw[c] = w_in4[(To * 64 + lane) * 4 + c];
-#pragma unroll
-    for (int s2 = 0; s2 < 16; s2 += 2) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[s2 >> 2][s2 & 3], in_k[s2], acc, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[(s2 + 1) >> 2][(s2 + 1) & 3], in_k[s2 + 1], acc2, 0, 0, 0);
-    }
-    xo[q] = acc + acc2;
-  }
-  // ---- the residual blocks x + l2(mish(l1(mish(x)))), as k_resmlp_f32
+  rm_input64<HID, true>(a.w_in, a.b_in, in_k, xo, w, lane, g);
   int buf = 0;
-#pragma clang loop unroll(disable)
-  for (int b = 0; b < nblk; b++) {
-    mlp_f4 y[TPW];
-#pragma unroll
-    for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(xo[q][0]), dd_mish(xo[q][1]), dd_mish(xo[q][2]), dd_mish(xo[q][3])};
-    __syncthreads();
-    rm_layer<HID, false>((const mlp_f4*)a.w_blk + (long)(2 * b) * LAYER_F4, a.b_blk + (2 * b) * HID, xb[buf], y, w, lane, g);
-    buf ^= 1;
-#pragma unroll
-    for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(y[q][0]), dd_mish(y[q][1]), dd_mish(y[q][2]), dd_mish(y[q][3])};
-    __syncthreads();
-    rm_layer<HID, true>((const mlp_f4*)a.w_blk + (long)(2 * b + 1) * LAYER_F4, a.b_blk + (2 * b + 1) * HID, xb[buf], xo, w, lane, g);
-    buf ^= 1;
-  }
-#pragma unroll
-  for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = xo[q];
+  rm_blocks<HID>(a.w_blk, a.b_blk, nblk, xb, xo, buf, w, lane, g);
+  rm_store<HID, false>(xb[buf], xo, w, lane);
   __syncthreads();
   if (w != 0) return;      // (after the last barrier) the output tile and the tail are one wave's work
-  mlp_f4 acc = mlp_f4{0.f, 0.f, 0.f, 0.f}, acc2 = mlp_f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    const mlp_f4 a4 = w_out4[t * 64 + lane], m4 = xb[buf][t * 64 + lane];
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0], m4[0], acc, 0, 0, 0);
-    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1], m4[1], acc2, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[2], m4[2], acc, 0, 0, 0);
-    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[3], m4[3], acc2, 0, 0, 0);
-  }
-  acc += acc2;
+  const mlp_f4 acc = rm_tile<HID>((const mlp_f4*)a.w_out, xb[buf], mlp_f4{0.f, 0.f, 0.f, 0.f}, lane);
   // ---- 3. the tail: lane (g, j), register r = component 4 g + r of row j.  The row's verdict is the OR over its four lanes: each saw a quarter of the input row.
   float v[4];
 #pragma unroll
@@ -148,14 +101,13 @@ __global__ __launch_bounds__(512) void k_cvae_decode(CvaeArgs a) {
     v[r] = acc[r] + a.b_out[4 * g + r];      // (b_out is padded to 16)
     bad |= 4 * g + r < A ? (unsigned)policy_nonfinite(v[r]) : 0u;
   }
-  bad |= __shfl_xor(bad, 16);
-  bad |= __shfl_xor(bad, 32);
+  bad = rm_row_or(bad);
   if (live) {
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int c = 4 * g + r;
       if (c < A) {
-        const unsigned yb = __float_as_uint(cvae_unscale(v[r], a.lo[c], a.hi[c], a.scale[c], a.shift[c]));
+        const unsigned yb = __float_as_uint(policy_unscale_f64(v[r], a.lo[c], a.hi[c], a.scale[c], a.shift[c]));
         ((unsigned*)a.actions)[row * A + c] = bad ? 0x7FC00000u : yb;
       }
     }

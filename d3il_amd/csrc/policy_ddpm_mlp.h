@@ -1,6 +1,6 @@
 // policy_ddpm_mlp.h - the whole reverse chain of the batched DDPM-MLP policy (policies.DDPMNativePolicy; agents/ddpm_agent.py:213-274 around gc_diffusion.py:101-216
-// over diffusion_models.py:20-118 and common/mlp.py ResidualMLPNetwork) as ONE kernel, on the Philox stream.  Included by rollout.hip behind policy_f32.h: it reuses
-// k_resmlp_f32's operand scheme with mlp_f4, rm_layer and dd_mish (the random stream and the bit test: policy_common.h).  k_ddpm_mlp_f32 (policy_f32.h) is the older
+// over diffusion_models.py:20-118 and common/mlp.py ResidualMLPNetwork) as ONE kernel, on the Philox stream.  Included by rollout.hip behind policy_resmlp.h, whose
+// pieces the denoiser is built from (the random stream, the bit test and the inverse scaling: policy_common.h).  k_ddpm_mlp_f32 (policy_f32.h) is the older
 // chain for one shape with its noise in an HBM tensor; it stays as it is.
 //
 // For environment n (s = the scaled state row, x the iterate of width A, f32 throughout; sched [T][5] = (sra, srm1, c1, c2, sig) of policies.ddpm_schedule, sig[0] = 0):
@@ -12,11 +12,10 @@
 // z_k: noise_in[k][n][a] or Box-Muller on philox4x32_10(seed, (env_offset + n, step word, DDPM_MLP_TAG | k << 1 | q)), component a = 4 q + m takes word m; the
 // second call (q = 1) is made only where A > 4.  T draws per call: k = 0 .. T - 1.
 //
-// Tiling: k_cvae_decode's.  A workgroup of eight waves owns 16 rows; the waves share the HID / 16 output tiles of a layer (wave w: tiles TPW w .. TPW (w + 1) - 1),
-// the weights stream from L2, the activations go from layer to layer through LDS in B-operand order, one barrier per layer; the block count is a loop bound.
-// What differs: (a) the input layer is split by what its columns depend on.  The time embedding's share W_in[:, temb] temb[i] + b_in is the same for every row: the
-// packer makes it a bias table tbias [T][HID].  The state's share W_in[:, state] s does not change along the chain: 16 matrix-core steps (64 columns) on two
-// accumulators once, held in TPW float4 per wave.  Per step the input layer is the A <= 8 columns of x: two matrix-core steps on weights held in registers.  That
+// Tiling: policy_resmlp.h's (16 rows per workgroup of eight waves, activations through LDS, one barrier per layer).  What differs from k_cvae_decode: (a) the input
+// layer is split by what its columns depend on.  The time embedding's share W_in[:, temb] temb[i] + b_in is the same for every row: the packer makes it a bias
+// table tbias [T][HID].  The state's share W_in[:, state] s does not change along the chain: the 64-column input layer without its bias (rm_input64) once, held
+// in TPW float4 per wave.  Per step the input layer is the A <= 8 columns of x: two matrix-core steps on weights held in registers.  That
 // changes the summation order of the input layer only.  (b) Every wave computes the output tile and every lane keeps its row's x (as k_ddpm_mlp_f32): no barrier
 // between the output layer and the next input layer.  (c) The noise is drawn ONCE per workgroup: wave 0 (lane j of each lane group: row j; one or two Philox calls,
 // two or four Box-Muller pairs) draws z_k in front of the barrier the step has anyway and shares it through 1 KB of LDS, double-buffered by the parity of k so that
@@ -32,7 +31,7 @@
 // the test.
 //
 // Resources (hipcc 7.2, gfx950, the flags of build.py, -Rpass-analysis=kernel-resource-usage):
-//   k_ddpm_mlp_chain<128>: 123 VGPRs, 0 AGPRs, 106 SGPRs (30 spilled to VGPR lanes), scratch 0, LDS 17408 B, occupancy 4 waves / SIMD (two workgroups per CU)
+//   k_ddpm_mlp_chain<128>: 125 VGPRs, 0 AGPRs, 106 SGPRs (12 spilled to VGPR lanes), scratch 0, LDS 17408 B, occupancy 4 waves / SIMD (two workgroups per CU)
 //   k_ddpm_mlp_chain<256>: 215 VGPRs, 0 AGPRs, 106 SGPRs (15 spilled to VGPR lanes), scratch 0, LDS 33792 B, occupancy 2 waves / SIMD (one workgroup per CU)
 // The SGPR spills are the per-component bounds and output biases (24 uniform values) next to 25 kernel arguments; they go to lanes of a VGPR, not to memory.
 #pragma once
@@ -41,13 +40,6 @@ namespace d3il {
 
 constexpr unsigned DDPM_MLP_TAG = 0x444D0000u;      // fourth counter word = TAG | k << 1 | q (k < 256, q < 2): an upper half no other tag has
 constexpr int DM_AMAX = 8, DM_INMAX = 64, DM_TMAX = 255;
-
-// clamp(v) scale + shift in f32, the product and the sum each rounded (no contraction): policies.NativePolicy._action_tail with f64 = False
-__device__ __forceinline__ float ddpm_mlp_unscale(float v, float lo, float hi, float scale, float shift) {
-#pragma clang fp contract(off)
-  const float p = fminf(fmaxf(v, lo), hi) * scale;
-  return p + shift;
-}
 
 struct DdpmMlpArgs {
   const unsigned* t_dev; const float* state; const float* w_x; const float* w_s; const float* tbias; const float* w_blk; const float* b_blk; const float* w_out;
@@ -60,7 +52,7 @@ struct DdpmMlpArgs {
 
 template <int HID>
 __global__ __launch_bounds__(512) void k_ddpm_mlp_chain(DdpmMlpArgs a) {
-  constexpr int NT = HID / 16, TPW = NT / 8, LAYER_F4 = NT * NT * 64;
+  constexpr int NT = HID / 16, TPW = NT / 8;
   __shared__ mlp_f4 xb[2][NT * 64];
   __shared__ mlp_f4 zs[2][16 * 2];      // the 16 rows' draw z_k, [k & 1][row][8]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 15, g = lane >> 4;
@@ -83,10 +75,10 @@ __global__ __launch_bounds__(512) void k_ddpm_mlp_chain(DdpmMlpArgs a) {
       const unsigned long long ge = a.env_offset + (unsigned long long)rr;
       const unsigned tag = DDPM_MLP_TAG | ((unsigned)k << 1);
       unsigned r[4];
-      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), tw, tag, r);
+      policy_philox(a.seed, ge, tw, tag, r);
       policy_box_muller(r[0], r[1], z[0], z[1]); policy_box_muller(r[2], r[3], z[2], z[3]);
       if (A > 4) {
-        philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)ge, (unsigned)(ge >> 32), tw, tag | 1u, r);
+        policy_philox(a.seed, ge, tw, tag | 1u, r);
         policy_box_muller(r[0], r[1], z[4], z[5]); policy_box_muller(r[2], r[3], z[6], z[7]);
       } else {
         z[4] = z[5] = z[6] = z[7] = 0.f;
@@ -118,25 +110,15 @@ __global__ __launch_bounds__(512) void k_ddpm_mlp_chain(DdpmMlpArgs a) {
     for (int s2 = 0; s2 < 16; s2++) { const int f = 4 * s2 + g; st_k[s2] = f < OBS ? a.state[rr * OBS + f] : 0.f; }
 #pragma unroll
     for (int s2 = 0; s2 < 16; s2++) bad |= (unsigned)policy_nonfinite(st_k[s2]);
-    const mlp_f4* w_s4 = (const mlp_f4*)a.w_s;
+    rm_input64<HID, false>(a.w_s, nullptr, st_k, xs, w, lane, g);      // (no bias: it is in tbias)
 #pragma unroll
     for (int q = 0; q < TPW; q++) {
       const int To = TPW * w + q;
-      mlp_f4 acc = mlp_f4{0.f, 0.f, 0.f, 0.f}, acc2 = mlp_f4{0.f, 0.f, 0.f, 0.f};
-      mlp_f4 aw[4];
-#pragma unroll
-      for (int c = 0; c < 4; c++) aw[c] = w_s4[(To * 64 + lane) * 4 + c];
-#pragma unroll
-      for (int s2 = 0; s2 < 16; s2 += 2) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[s2 >> 2][s2 & 3], st_k[s2], acc, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[(s2 + 1) >> 2][(s2 + 1) & 3], st_k[s2 + 1], acc2, 0, 0, 0);
-      }
-      xs[q] = acc + acc2;
       wx[q][0] = a.w_x[(To * 64 + lane) * 2];
       wx[q][1] = a.w_x[(To * 64 + lane) * 2 + 1];
     }
   }
-  bad |= (unsigned)__shfl_xor((int)bad, 16); bad |= (unsigned)__shfl_xor((int)bad, 32);      // the four lane groups of row j hold its features 4 s2 + g
+  bad = rm_row_or(bad);
   __syncthreads();
   // ---- 1. x = z_0: every lane keeps its row's iterate
   float x[DM_AMAX];
@@ -147,7 +129,6 @@ __global__ __launch_bounds__(512) void k_ddpm_mlp_chain(DdpmMlpArgs a) {
 #pragma unroll
     for (int c = 0; c < DM_AMAX; c++) bad |= (unsigned)policy_nonfinite(x[c]);
   }
-  const mlp_f4* w_out4 = (const mlp_f4*)a.w_out;
   int buf = 0;
   // ---- 2. the reverse chain
 #pragma clang loop unroll(disable)
@@ -163,35 +144,12 @@ __global__ __launch_bounds__(512) void k_ddpm_mlp_chain(DdpmMlpArgs a) {
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wx[q][1], xk1, acc, 0, 0, 0);
       xo[q] = acc + xs[q];
     }
-#pragma clang loop unroll(disable)
-    for (int b = 0; b < nblk; b++) {      // x + l2(mish(l1(mish(x))))
-      mlp_f4 y[TPW];
-#pragma unroll
-      for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(xo[q][0]), dd_mish(xo[q][1]), dd_mish(xo[q][2]), dd_mish(xo[q][3])};
-      __syncthreads();
-      rm_layer<HID, false>((const mlp_f4*)a.w_blk + (long)(2 * b) * LAYER_F4, a.b_blk + (2 * b) * HID, xb[buf], y, w, lane, g);
-      buf ^= 1;
-#pragma unroll
-      for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = mlp_f4{dd_mish(y[q][0]), dd_mish(y[q][1]), dd_mish(y[q][2]), dd_mish(y[q][3])};
-      __syncthreads();
-      rm_layer<HID, true>((const mlp_f4*)a.w_blk + (long)(2 * b + 1) * LAYER_F4, a.b_blk + (2 * b + 1) * HID, xb[buf], xo, w, lane, g);      // the residual rides in the accumulator
-      buf ^= 1;
-    }
-#pragma unroll
-    for (int q = 0; q < TPW; q++) xb[buf][(TPW * w + q) * 64 + lane] = xo[q];
+    rm_blocks<HID>(a.w_blk, a.b_blk, nblk, xb, xo, buf, w, lane, g);
+    rm_store<HID, false>(xb[buf], xo, w, lane);
     if (w == 0) draw(k);      // z_k of this step's update (k = T: zeros to noise_out only), in front of the barrier the output layer needs anyway
     __syncthreads();
-    mlp_f4 acc = mlp_f4{0.f, 0.f, 0.f, 0.f}, acc2 = mlp_f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      const mlp_f4 a4 = w_out4[t * 64 + lane], m4 = xb[buf][t * 64 + lane];
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0], m4[0], acc, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1], m4[1], acc2, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[2], m4[2], acc, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[3], m4[3], acc2, 0, 0, 0);
-    }
+    const mlp_f4 acc = rm_tile<HID>((const mlp_f4*)a.w_out, xb[buf], mlp_f4{0.f, 0.f, 0.f, 0.f}, lane);      // (every wave: each keeps its rows' x)
     buf ^= 1;
-    acc += acc2;
     // epsilon of row j sits in lanes (0, j) and (1, j), registers 0 .. 3: every lane group of every wave takes it and does the same update on its copy of x
     float e[DM_AMAX];
 #pragma unroll
@@ -221,7 +179,7 @@ __global__ __launch_bounds__(512) void k_ddpm_mlp_chain(DdpmMlpArgs a) {
 #pragma unroll
     for (int c = 0; c < DM_AMAX; c++) {
       if (c < A) {
-        const unsigned yb = __float_as_uint(ddpm_mlp_unscale(x[c], lo[c], hi[c], a.scale[c], a.shift[c]));
+        const unsigned yb = __float_as_uint(policy_unscale_f32(x[c], lo[c], hi[c], a.scale[c], a.shift[c]));
         ((unsigned*)a.actions)[row * A + c] = bad ? 0x7FC00000u : yb;
       }
     }

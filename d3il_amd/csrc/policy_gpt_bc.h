@@ -1,5 +1,5 @@
 // policy_gpt_bc.h - the tail of the batched BC-GPT policy (policies.GPTBCPolicy; agents/gpt_bc_agent.py:221-247 around agents/models/transformer/gpt_policy.py MinGPT,
-// the BeT library's GPT with vocab_size = action_dim) as ONE small kernel (included by rollout.hip behind policy_cvae.h, whose cvae_unscale it uses).
+// the BeT library's GPT with vocab_size = action_dim) as ONE small kernel (included by rollout.hip behind policy_common.h, whose policy_unscale_f64 it uses).
 //
 // Per row (= environment; h = the last block's output at the lane's last token):
 //   1. x = ln_f(h)                                         (nn.LayerNorm, biased variance; the order of operations of k_bet_head)
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * GB_NW) void k_gpt_bc_head(GptBcHeadArgs a) {
     const bool bad = bad_x | bad_o;
     // ---- 3. the action
     if (comp) {
-      const unsigned yb = __float_as_uint(cvae_unscale(mine, cl, ch, sc, sh));
+      const unsigned yb = __float_as_uint(policy_unscale_f64(mine, cl, ch, sc, sh));
       ((unsigned*)a.actions)[row * A + lane] = bad ? 0x7FC00000u : yb;
     }
     if (a.bad && lane == 0) a.bad[row] = bad ? 1 : 0;

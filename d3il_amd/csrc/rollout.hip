@@ -34,6 +34,7 @@ constexpr int WAVE = 64;
 #include "policy_act.h"
 #include "policy_ddpm_act.h"
 #include "policy_f32.h"
+#include "policy_resmlp.h"
 #include "policy_cvae.h"
 #include "policy_ddpm_mlp.h"
 #include "policy_bet_mlp.h"
@@ -812,6 +813,17 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(D3IL_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
+// What the entries of the ResidualMLPNetwork kernels (policy_resmlp.h and its users) share.  The float4 loads of the packed operands need every one of these
+// pointers on a 16-byte boundary (a null pointer passes: the entry has refused it already, or the kernel never reads it).
+template <class... P>
+static bool aligned16(const P*... p) { return ((... | (uintptr_t)p) % 16) == 0; }
+// One workgroup of eight waves per 16 rows, the last one may be partly filled; ``k128`` / ``k256`` are the kernel built for either hidden width (the entry has
+// refused every other).  n > 0.
+template <class... A, class... B>
+static void launch_rows16(void (*k128)(A...), void (*k256)(A...), int hidden, long n, void* stream, const B&... args) {
+  hipLaunchKernelGGL(hidden == 128 ? k128 : k256, dim3((unsigned)((n + 15) / 16)), dim3(512), 0, (hipStream_t)stream, args...);
+}
+
 extern "C" {
 
 // Step group: every library call on a member other than an eligible d3il_random_rollout_step ends the round first - the pending members run through the
@@ -1370,11 +1382,9 @@ int d3il_resmlp_f32(const float* x, const float* w_in, const float* b_in, const 
   if (hidden != 128 && hidden != 256) return fail(D3IL_EUNSUPPORTED, "d3il_resmlp_f32: built for hidden 128 and 256 (the ResidualMLPNetwork of the BC and DDPM configs)");
   if (in_dim < 1 || in_dim > 28 || out_dim < 1 || out_dim > 16) return fail(D3IL_EUNSUPPORTED, "d3il_resmlp_f32: at most 28 inputs and 16 outputs");
   if (n_blocks < 0 || rows < 0) return fail(D3IL_EINVAL, "d3il_resmlp_f32: bad counts");
-  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_out) % 16 != 0) return fail(D3IL_EINVAL, "d3il_resmlp_f32: weights and biases must be 16-byte aligned");
+  if (!aligned16(w_in, b_in, w_blocks, b_blocks, w_out)) return fail(D3IL_EINVAL, "d3il_resmlp_f32: weights and biases must be 16-byte aligned");
   if (rows == 0) return D3IL_OK;
-  const dim3 grid((unsigned)((rows + 15) / 16)), block(512);
-  if (hidden == 128) hipLaunchKernelGGL(k_resmlp_f32<128>, grid, block, 0, (hipStream_t)stream, x, w_in, b_in, w_blocks, b_blocks, w_out, b_out, out, rows, in_dim, out_dim, n_blocks);
-  else hipLaunchKernelGGL(k_resmlp_f32<256>, grid, block, 0, (hipStream_t)stream, x, w_in, b_in, w_blocks, b_blocks, w_out, b_out, out, rows, in_dim, out_dim, n_blocks);
+  launch_rows16(k_resmlp_f32<128>, k_resmlp_f32<256>, hidden, rows, stream, x, w_in, b_in, w_blocks, b_blocks, w_out, b_out, out, rows, in_dim, out_dim, n_blocks);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
@@ -1615,15 +1625,12 @@ int d3il_cvae_decode_f32(const float* state, const float* w_in, const float* b_i
   if (!state || !w_in || !b_in || !w_blocks || !b_blocks || !w_out || !b_out || !lo || !hi || !scale || !shift || !t_device || !actions)
     return fail(D3IL_EINVAL, "d3il_cvae_decode_f32: null argument");
   if (n_env < 0) return fail(D3IL_EINVAL, "d3il_cvae_decode_f32: negative environment count");
-  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_out) % 16 != 0)
+  if (!aligned16(w_in, b_in, w_blocks, b_blocks, w_out))
     return fail(D3IL_EINVAL, "d3il_cvae_decode_f32: the packed weights and biases must be 16-byte aligned");
   if (n_env == 0) return D3IL_OK;
   CvaeArgs a{state, w_in, b_in, w_blocks, b_blocks, w_out, b_out, lo, hi, scale, shift, t_device, z_in, actions, z_out, (unsigned long long)seed, (unsigned long long)env_offset,
              n_env, obs_dim, latent, A, n_blocks};
-  // one workgroup of eight waves per 16 environments; the last one may be partly filled
-  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
-  if (hidden == 128) hipLaunchKernelGGL(k_cvae_decode<128>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_cvae_decode<256>, grid, block, 0, (hipStream_t)stream, a);
+  launch_rows16(k_cvae_decode<128>, k_cvae_decode<256>, hidden, n_env, stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
@@ -1638,15 +1645,12 @@ int d3il_ddpm_mlp_chain(const uint32_t* t_device, const float* state, const floa
   if (!t_device || !state || !w_x || !w_state || !tbias || !w_blocks || !b_blocks || !w_out || !b_out || !sched || !lo || !hi || !scale || !shift || !actions || !bad)
     return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: null argument");
   if (n_env < 0) return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: negative environment count");
-  if (((uintptr_t)w_x | (uintptr_t)w_state | (uintptr_t)tbias | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_out) % 16 != 0)
+  if (!aligned16(w_x, w_state, tbias, w_blocks, b_blocks, w_out))
     return fail(D3IL_EINVAL, "d3il_ddpm_mlp_chain: the packed weights, the bias table and the block biases must be 16-byte aligned");
   if (n_env == 0) return D3IL_OK;
   DdpmMlpArgs a{t_device, state, w_x, w_state, tbias, w_blocks, b_blocks, w_out, b_out, sched, lo, hi, scale, shift, noise_in, actions, bad, noise_out,
                 (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, n_timesteps, n_blocks};
-  // one workgroup of eight waves per 16 environments; the last one may be partly filled
-  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
-  if (hidden == 128) hipLaunchKernelGGL(k_ddpm_mlp_chain<128>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_ddpm_mlp_chain<256>, grid, block, 0, (hipStream_t)stream, a);
+  launch_rows16(k_ddpm_mlp_chain<128>, k_ddpm_mlp_chain<256>, hidden, n_env, stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
@@ -1659,15 +1663,12 @@ int d3il_bet_mlp_f32(const float* state, const float* w_in, const float* b_in, c
   if (!state || !w_in || !b_in || !w_blocks || !b_blocks || !w_logit || !b_logit || !w_off || !b_off || !centers || !lo || !hi || !scale || !shift || !t_device || !actions || !bins)
     return fail(D3IL_EINVAL, "d3il_bet_mlp_f32: null argument");
   if (n_env < 0) return fail(D3IL_EINVAL, "d3il_bet_mlp_f32: negative environment count");
-  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_logit | (uintptr_t)b_logit | (uintptr_t)w_off) % 16 != 0)
+  if (!aligned16(w_in, b_in, w_blocks, b_blocks, w_logit, b_logit, w_off))
     return fail(D3IL_EINVAL, "d3il_bet_mlp_f32: the packed weights, their biases and the offset rows must be 16-byte aligned");
   if (n_env == 0) return D3IL_OK;
   BetMlpArgs a{state, w_in, b_in, w_blocks, b_blocks, w_logit, b_logit, w_off, b_off, centers, lo, hi, scale, shift, t_device, u_in, actions, bins, u_out, probs,
                (unsigned long long)seed, (unsigned long long)env_offset, n_env, obs_dim, A, n_blocks};
-  // one workgroup of eight waves per 16 environments; the last one may be partly filled
-  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
-  if (hidden == 128) hipLaunchKernelGGL(k_bet_mlp<128>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_bet_mlp<256>, grid, block, 0, (hipStream_t)stream, a);
+  launch_rows16(k_bet_mlp<128>, k_bet_mlp<256>, hidden, n_env, stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }
@@ -1682,16 +1683,12 @@ int d3il_bc_gmm(long n_env, const uint32_t* t_device, const float* state, const 
       (std_mode != BG_STD_LOW_NOISE && (!w_std || !b_std)))
     return fail(D3IL_EINVAL, "d3il_bc_gmm: null argument");
   if (n_env < 0) return fail(D3IL_EINVAL, "d3il_bc_gmm: negative environment count");
-  if (((uintptr_t)w_in | (uintptr_t)b_in | (uintptr_t)w_blocks | (uintptr_t)b_blocks | (uintptr_t)w_feat | (uintptr_t)b_feat | (uintptr_t)w_logit | (uintptr_t)b_logit | (uintptr_t)w_mean |
-       (uintptr_t)w_std) % 16 != 0)
+  if (!aligned16(w_in, b_in, w_blocks, b_blocks, w_feat, b_feat, w_logit, b_logit, w_mean, w_std))
     return fail(D3IL_EINVAL, "d3il_bc_gmm: the packed weights, their biases and the head rows must be 16-byte aligned");
   if (n_env == 0) return D3IL_OK;
   BcGmmArgs a{t_device, state, w_in, b_in, w_blocks, b_blocks, w_feat, b_feat, w_logit, b_logit, w_mean, b_mean, w_std, b_std, lo, hi, scale, shift, u_in, z_in, actions, comps, u_out, z_out,
               probs, (unsigned long long)seed, (unsigned long long)env_offset, n_env, min_std, obs_dim, G, A, n_blocks, std_mode};
-  // one workgroup of eight waves per 16 environments; the last one may be partly filled
-  const dim3 grid((unsigned)((n_env + 15) / 16)), block(512);
-  if (hidden == 128) hipLaunchKernelGGL(k_bc_gmm<128>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_bc_gmm<256>, grid, block, 0, (hipStream_t)stream, a);
+  launch_rows16(k_bc_gmm<128>, k_bc_gmm<256>, hidden, n_env, stream, a);
   HIPCHK(hipGetLastError());
   return D3IL_OK;
 }

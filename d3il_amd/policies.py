@@ -922,7 +922,7 @@ def resmlp_args(w) -> dict:
 
 
 class FusedResMLP:
-    """The device path of a ResidualMLPNetwork (csrc/policy_f32.h k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
+    """The device path of a ResidualMLPNetwork (csrc/policy_resmlp.h k_resmlp_f32 through d3il_resmlp_f32) on packed weights (PackedWeights).  Every call takes
     ``parts`` = (lin_in, [(l1, l2), ..], lin_out) of the module it serves (no reference to the module is kept).  Non-finite input: a row of x with a NaN / Inf comes
     out NaN in every column, as from torch's layers, and no other row changes (tests/test_gpu_policy_f32_edges.py)."""
 
